@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the Tango hot path on MI355X (see BASELINE.json / DESIGN.md).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one full pass of the hot path over one batch per GPU: the CFG denoise loop
@@ -11,6 +11,11 @@ batch 32, guidance 3).  Other BASELINE configs: `--batch 1 --denoise-steps 100` 
 --batch 8` (config 5's per-GPU shard); `config.workload` in the JSON line names what actually ran.  Inputs (text-encoder outputs, initial latents) are resident in HBM when the timed
 region starts; weights are seeded synthetic tensors of the real architecture (no checkpoint offline).
 Metric: audio-seconds generated per wall-second, whole job (all GPUs).  Weak scaling: per-GPU batch fixed.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes runs of its own: the CPU
+oracle baseline, the other BASELINE configs and the fp32 pass (`other_configs`, `roofline.same_precision`, only for the
+config-3 workload on one GPU), the text-encoder timing and the committed parity ladder (`parity`).  `--dump-outputs DIR`
+writes the last timed step's waveforms as DIR/wav.npy (float32; a fixed, seeded sample of rows when above 64 MB).
 """
 import argparse
 import json
@@ -93,10 +98,14 @@ def parse():
     ap.add_argument("--xl", action="store_true", help="FLAN-T5-XL cross-attention width (2048)")
     ap.add_argument("--fp8-attn", action="store_true", help="self-attention P.V on the fp8 MFMA (BASELINE config 5; 16-bit dtypes)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the `other_configs` sub-records (batch 1 / 8 and config 5's shard) the default config-3 run at N = 1 appends")
+                    help="with --full: skip the `other_configs` sub-records (batch 1 / 8 and config 5's shard) a config-3 run at N = 1 appends")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, other configs / precisions, text encoder and parity record (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (the int16 waveforms as float32) to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -307,6 +316,24 @@ def timed_single_gpu(wl, args, batch, denoise_steps, warm_steps=None):
     return rec
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, wav):
+    """--dump-outputs: what the timed path hands its caller in its last step -- the global int16 waveforms [B, n_samples] -- as
+    float32 `wav.npy`.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of whole rows is written instead, with their row indices in
+    `wav_rows.npy` (float64), so that two builds given the same arguments can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    wav = np.asarray(wav)
+    row_bytes = 4 * int(np.prod(wav.shape[1:]))
+    if wav.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+        k = max(1, DUMP_LIMIT_BYTES // max(row_bytes, 1) - 1)
+        rows = np.sort(np.random.default_rng(0).choice(wav.shape[0], size=k, replace=False))
+        np.save(os.path.join(out_dir, "wav_rows.npy"), rows.astype(np.float64))
+        wav = wav[rows]
+    np.save(os.path.join(out_dir, "wav.npy"), wav.astype(np.float32))
+
+
 def stub_main(args, world, rank):
     """TANGO_BENCH_STUB=1 (tests/test_bench_launch.py): the launch / rendezvous / sharding / gather / JSON plumbing of this
     script on CPU over gloo with a stand-in compute function.  Not a measurement: the line says "stub": true."""
@@ -334,8 +361,10 @@ def stub_main(args, world, rank):
     stage = dp.timing_summary()
     if rank == 0:
         assert wav.shape == (Bg, n_samples) and (wav[:, 0] == np.arange(Bg)).all()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, wav)
         print(json.dumps({"metric": "stub", "stub": True, "value": Bg * args.steps / dt, "n_gpus": world, "steps": args.steps,
-                          "warmup": args.warmup, "ranks": world, "config": {"global_batch": Bg},
+                          "warmup": args.warmup, "ms_per_step": 1000.0 * dt / args.steps, "ranks": world, "config": {"global_batch": Bg},
                           "per_rank_ms": stage["per_rank_ms"], "bcast_ms": stage["bcast_ms"], "gather_ms": stage["gather_ms"]}))
     if world > 1:
         dist.destroy_process_group()
@@ -398,6 +427,8 @@ def main():
 
     if rank == 0:
         assert wav.shape == (Bg, n_samples) and wav.dtype == np.int16
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, wav)
         audio_s = Bg * AUDIO_SECONDS_PER_SAMPLE * args.steps
         per_step_ms = float(np.mean([m[1] for m in denoise_ms])) if denoise_ms else float("nan")
         # roofline of the dominant launch = one hipGraph replay of the UNet step (MFMA-bound):
@@ -433,10 +464,10 @@ def main():
             # per_rank_ms.max - min, a slow collective as bcast_ms / gather_ms (no per-step collective exists)
             "per_rank_ms": stage["per_rank_ms"], "bcast_ms": stage["bcast_ms"], "gather_ms": stage["gather_ms"],
         }
-        par = parity_record() if args.dtype == "fp16" else None
+        par = parity_record() if args.full and args.dtype == "fp16" else None
         if par:
             out["parity"] = par
-        if world == 1 and not args.no_other_configs and workload_name(args) == "BASELINE config 3":
+        if args.full and world == 1 and not args.no_other_configs and workload_name(args) == "BASELINE config 3":
             # the other batch sizes north_star names, timed by the same process (one warm-up + one timed pass each, ~20 s in all):
             # sub-records only -- `value` above stays config 3
             oc = {}
@@ -461,7 +492,7 @@ def main():
             del wl32
             out["text_encoder_ms"] = text_encoder_timing(args, device, 32, args.text_len)
             out["other_configs"] = oc
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             keys = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "prediction_type", "clip_sample", "variance_type")
             out["cpu_baseline"] = cpu_baseline(args, unet_cfg, VAE_CONFIG, HIFIGAN_CONFIG, {k: SD21_SCHEDULER_CONFIG[k] for k in keys})
         print(json.dumps(out))

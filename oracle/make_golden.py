@@ -16,6 +16,11 @@ Every fixture is produced by importing the reference's own code (oracle/ref_impo
   music_unet_ref.npz   Mustango UNet2DConditionModelMusic.forward (unet_2d_condition_music.py:536-757) output slices, tiny widths
   stft_ref.npz         reference TacotronSTFT.mel_spectrogram (audioldm/audio/stft.py:164-186) outputs on a seeded test signal
                        (librosa stubbed by oracle/stft_oracle.py's restatements: pins everything downstream of the filterbank)
+  reference_diff.json / reference_diff.npz
+                       what tests/test_reference_diff.py and the stft "live" test compare against: the reference's state-dict
+                       inventories, SHA-256 digests of the tensors they check bit for bit (fork DDPMScheduler.step, the STFT
+                       bases) and, for the outputs they check to a tolerance (tiny UNet with a ragged mask, tiny Music UNet, STFT),
+                       a fixed sample of elements (see sample_fixture) with the full tensor's checksum and max |x|
 Inputs are re-derived from seeds by the tests; only small slices / checksums / tiny state_dicts are stored.
 """
 import json
@@ -298,11 +303,123 @@ def stft_golden():
     print("stft", mel.shape, checksum(mel), checksum(logmag))
 
 
+def digest(t):
+    """SHA-256 of a tensor's dtype, shape and bytes: a bitwise comparison against a stored value"""
+    import hashlib
+    a = t.detach().contiguous().cpu().numpy()
+    return hashlib.sha256(("%s%s" % (a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
+SUM_BLOCK = 16
+
+
+def block_sums(x):
+    """float64 sums of consecutive SUM_BLOCK-element blocks of x.flatten() (the last block may be shorter)"""
+    a = x.detach().flatten().double().numpy()
+    return np.add.reduceat(a, np.arange(0, a.size, SUM_BLOCK))
+
+
+def sample_fixture(store, name, ref, ours, n, top=1024, seed=0):
+    """`n` elements of the reference output `ref` for a tolerance check, stored exactly: the `top` elements where the oracle's
+    output `ours` (at fixture time) is farthest from `ref`, and a seeded uniform sample of the rest; with `ref`'s shape, checksum,
+    max |ref| and its SUM_BLOCK-element block sums (float32).  (A full fp32 output of these sizes would be megabytes.)"""
+    r = ref.detach().flatten()
+    worst = torch.topk((r.double() - ours.detach().flatten().double()).abs(), top).indices.numpy()
+    rest = np.setdiff1d(np.arange(r.numel()), worst)
+    idx = np.sort(np.concatenate([worst, np.random.default_rng(seed).choice(rest, n - top, replace=False)])).astype(np.int32)
+    store[name + "/idx"], store[name + "/val"] = idx, r[torch.from_numpy(idx).long()].numpy()
+    store[name + "/shape"], store[name + "/checksum"] = np.asarray(ref.shape), np.asarray(checksum(ref))
+    store[name + "/absmax"] = np.asarray(float(r.abs().max()))
+    store[name + "/block_sums"] = block_sums(ref).astype(np.float32)
+
+
+def sample_err(z, name, got, tol):
+    """max |got - ref| over a sample_fixture() sample, after checking `got`'s shape, and that its checksum and block sums agree
+    with the full reference within what max |got - ref| <= tol over ALL elements implies (sum, sum |x| within N tol; sum x^2
+    within tol (2 sum |ref| + N tol); a block's sum within its length x tol, plus the float32 rounding of the stored sum): a
+    non-finite element, or one off by more than ~SUM_BLOCK x tol, fails wherever it is"""
+    assert tuple(got.shape) == tuple(int(v) for v in z[name + "/shape"]), (tuple(got.shape), z[name + "/shape"])
+    n, c, ref_cs = got.numel(), checksum(got), z[name + "/checksum"]
+    bound = [n * tol, n * tol, tol * (2 * ref_cs[1] + n * tol)]
+    for i in range(3):
+        assert abs(c[i] - ref_cs[i]) <= bound[i] * (1 + 1e-9), (name, i, c[i], ref_cs[i], bound[i])
+    rs = z[name + "/block_sums"].astype(np.float64)
+    lens = np.diff(np.append(np.arange(0, n, SUM_BLOCK), n))
+    excess = np.abs(block_sums(got) - rs) - (lens * tol * (1 + 1e-9) + np.abs(rs) * 2.0 ** -23)
+    assert not (excess > 0).any() and np.isfinite(excess).all(), (name, "block", int(np.argmax(excess)), float(np.max(excess)))
+    idx = torch.from_numpy(z[name + "/idx"].astype(np.int64))
+    return (got.detach().flatten()[idx].double() - torch.from_numpy(z[name + "/val"]).double()).abs().max().item()
+
+
+def reference_diff_golden():
+    """the reference side of tests/test_reference_diff.py and test_stft_oracle.py's live test, on the same seeded inputs"""
+    from oracle import stft_oracle as S
+    js, arr = {}, {}
+    with torch.device("meta"):
+        unet = R.unet_cls()(**R.unet_config())
+    js["unet_large_inventory"] = {k: list(v.shape) for k, v in unet.state_dict().items()}
+    vae = R.autoencoder_cls()(**R.vae_config())
+    js["vae_inventory"] = {k: list(v.shape) for k, v in vae.state_dict().items()}
+    del unet, vae
+    # tiny UNet, ragged mask (test_unet_tiny_matches_fork_with_ragged_mask)
+    cfgo = O.UNET_CONFIG_TINY
+    cfg = dict(R.unet_config())
+    cfg.update({k: cfgo[k] for k in ("block_out_channels", "attention_head_dim", "cross_attention_dim")})
+    unet = R.unet_cls()(**cfg).eval()
+    unet.load_state_dict(W.synth_state_dict(W.unet_param_shapes(cfgo), 7))
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(3, 8, 256, 16, generator=g)
+    enc = torch.randn(3, 11, cfgo["cross_attention_dim"], generator=g)
+    mask = torch.ones(3, 11, dtype=torch.bool)
+    mask[0, 1:] = False
+    mask[2, 4:] = False
+    sample_fixture(arr, "unet_tiny_ragged", unet(x, torch.tensor(123), encoder_hidden_states=enc, encoder_attention_mask=mask).sample,
+                   O.unet_forward(W.synth_state_dict(W.unet_param_shapes(cfgo), 7), cfgo, x, 123, enc, mask), 8192)
+    # fork DDPMScheduler.step, bitwise (test_scheduler_step_matches_fork_bitwise)
+    sch = R.ddpm_cls()(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                       prediction_type="v_prediction", clip_sample=False, variance_type="fixed_small")
+    sch.set_timesteps(200)
+    g = torch.Generator().manual_seed(0)
+    x, v = torch.randn(2, 8, 256, 16, generator=g), torch.randn(2, 8, 256, 16, generator=g)
+    js["ddpm_step_sha256"] = {str(t): digest(sch.step(v, t, x, generator=torch.Generator().manual_seed(9)).prev_sample)
+                              for t in (995, 500, 5, 0)}
+    # Mustango's Music UNet: inventory at the real config, forward at tiny widths (test_music_unet_inventory_and_forward_match_mustango)
+    mcfg = json.load(open(os.path.join(R.REF, "mustango", "configs", "music_diffusion_model_config.json")))
+    mcfg = {k: v for k, v in mcfg.items() if not k.startswith("_")}
+    with torch.device("meta"):
+        big = R.unet_music_cls()(**dict(mcfg, **{k: O.UNET_CONFIG_MUSIC[k] for k in ("block_out_channels", "attention_head_dim",
+                                                                                         "cross_attention_dim")}))
+    js["music_unet_inventory"] = {k: list(v.shape) for k, v in big.state_dict().items()}
+    del big
+    cfgo = O.UNET_CONFIG_MUSIC_TINY
+    torch.manual_seed(0)
+    unet = R.unet_music_cls()(**dict(mcfg, **{k: cfgo[k] for k in ("block_out_channels", "attention_head_dim", "cross_attention_dim")})).eval()
+    unet.load_state_dict(W.synth_state_dict(W.unet_param_shapes(cfgo), 1234))
+    x, enc, beat, chord, em, bm, cm = music_inputs(cfgo, 4, 3)
+    want = unet(x, torch.tensor(801), encoder_hidden_states=enc, beat_features=beat, chord_features=chord,
+                encoder_attention_mask=em, beat_attention_mask=bm, chord_attention_mask=cm).sample
+    got = O.unet_forward(W.synth_state_dict(W.unet_param_shapes(cfgo), 1234), cfgo, x, 801, enc, em, "", beat_features=beat,
+                         chord_features=chord, beat_attention_mask=bm, chord_attention_mask=cm)
+    sample_fixture(arr, "music_unet_tiny", want, got, 8192)
+    # TacotronSTFT on an odd-length 3-clip batch (test_mel_spectrogram_matches_imported_reference_live)
+    ref = R.tacotron_stft_cls()(**S.AUDIOLDM_STFT_CONFIG).eval()
+    y = stft_wave(B=3, N=16000 * 2 + 123, seed=5)
+    m0, l0, e0 = ref.mel_spectrogram(y)
+    m1, l1, _ = S.mel_spectrogram(y, ref.mel_basis, ref.stft_fn.forward_basis)
+    sample_fixture(arr, "stft_odd_mel", m0, m1, 6144)
+    sample_fixture(arr, "stft_odd_logmag", l0, l1, 12288)
+    arr["stft_odd_energy"] = e0.numpy()
+    js["stft_mel_basis_sha256"], js["stft_forward_basis_sha256"] = digest(ref.mel_basis), digest(ref.stft_fn.forward_basis)
+    json.dump(js, open(os.path.join(OUT, "reference_diff.json"), "w"), separators=(",", ":"), sort_keys=True)
+    np.savez_compressed(os.path.join(OUT, "reference_diff.npz"), **arr)
+    print("reference_diff", {k: v.shape for k, v in arr.items() if not k.endswith(("/checksum", "/absmax"))})
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     assert R.available(), "needs /root/reference"
-    if len(sys.argv) > 1 and sys.argv[1] in ("stft", "music"):      # regenerate only a round-3 fixture
-        {"stft": stft_golden, "music": music_golden}[sys.argv[1]]()
+    if len(sys.argv) > 1 and sys.argv[1] in ("stft", "music", "reference_diff"):      # regenerate only one later fixture
+        {"stft": stft_golden, "music": music_golden, "reference_diff": reference_diff_golden}[sys.argv[1]]()
         sys.exit(0)
     sched_golden()
     kat_golden()
@@ -311,5 +428,6 @@ if __name__ == "__main__":
     vae_enc_golden()
     stft_golden()
     music_golden()
+    reference_diff_golden()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -45,3 +45,33 @@ def test_bench_under_an_external_launcher_does_not_relaunch():
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "1"])
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 2
+
+
+def test_bench_dump_outputs_and_ms_per_step(tmp_path):
+    """--dump-outputs DIR writes the last timed step's waveforms as float32 DIR/wav.npy, identical across runs with the same
+    arguments; --steps sets the timed steps and the line carries ms_per_step"""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        out = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "2", "--dump-outputs", str(d)])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0.0
+        w = np.load(d / "wav.npy")
+        assert w.dtype == np.float32 and w.shape == (2, 64) and (w[:, 0] == np.arange(2)).all()
+        dumps.append(w)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_dump_outputs_samples_rows_above_the_limit(tmp_path, monkeypatch):
+    """above 64 MB the dump is a fixed, seeded sample of whole rows, with their indices"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * 4 * 8)
+    wav = (np.arange(40, dtype=np.int16)[:, None] + np.zeros((1, 8), np.int16))
+    for run in range(2):
+        bench.dump_outputs(str(tmp_path / str(run)), wav)
+    a, rows = np.load(tmp_path / "0" / "wav.npy"), np.load(tmp_path / "0" / "wav_rows.npy")
+    assert a.dtype == np.float32 and rows.dtype == np.float64 and a.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert len(rows) == a.shape[0] > 0 and (a[:, 0] == rows).all() and (np.diff(rows) > 0).all()
+    assert np.array_equal(a, np.load(tmp_path / "1" / "wav.npy"))
