@@ -7,6 +7,7 @@
  *   tango_engine_denoise        AudioDiffusion.inference loop body        models.py:224-249
  *                               + DDPMScheduler.step                       mustango/diffusers/src/diffusers/schedulers/scheduling_ddpm.py:254-349
  *                               (+ DDIMScheduler.step                      .../scheduling_ddim.py:238-360)
+ *                               (+ DPMSolverMultistepScheduler.step        .../scheduling_dpmsolver_multistep.py:429-495)
  *   tango_engine_unet_forward   UNet2DConditionModel.forward               mustango/diffusers/src/diffusers/models/unet_2d_condition.py:520-707
  *   tango_engine_unet_forward_music  UNet2DConditionModelMusic.forward      mustango/diffusers/src/diffusers/models/unet_2d_condition_music.py:536-757
  *   tango_engine_vae_decode     AutoencoderKL.decode_first_stage           audioldm/variational_autoencoder/autoencoder.py:116-124,60-64
@@ -47,6 +48,20 @@ extern "C" {
 
 #define TANGO_RULE_DDPM 0
 #define TANGO_RULE_DDIM 1
+/* multistep DPM-Solver / DPM-Solver++ (mustango/diffusers/src/diffusers/schedulers/scheduling_dpmsolver_multistep.py:124-495):
+ * deterministic (no step noise, `noise` must be NULL, `clip_sample` 0), coefficient rows 16 floats wide (coef_width = 16):
+ *   [0] alpha_s0  [1] sigma_s0      conversion of the guided output (x0 for DPM-Solver++, eps for DPM-Solver)
+ *   [2] kx  [3] c0  [4] c1  [5] c2  signed update coefficients (the fork's subtracted terms stored negated)
+ *   [6] 1/r0  [7] 1/r1  [8] r0/(r0+r1)  [9] 1/(r0+r1)
+ *   [10] effective order of the step (1, 2 or 3)  [11] algorithm: 0 DPM-Solver++, 1 DPM-Solver (the same in every row)
+ *   [12..15] 0
+ * update: order 1  x' = kx*x + c0*D0
+ *         order 2  x' = (kx*x + c0*D0) + c1*D1                     D1 = (1/r0)*(m0 - m1)
+ *         order 3  x' = ((kx*x + c0*D0) + c1*D1) + c2*D2           D1_0 = (1/r0)*(m0 - m1), D1_1 = (1/r1)*(m1 - m2),
+ *                  D1 = D1_0 + (r0/(r0+r1))*(D1_0 - D1_1),  D2 = (1/(r0+r1))*(D1_0 - D1_1)
+ * with D0 = m0 the converted output of this step and m1, m2 those of the two steps before (tango_amd/scheduler.py
+ * DPMSolverMultistepScheduler.coef_table builds the table). */
+#define TANGO_RULE_DPM_MULTISTEP 2
 
 #define TANGO_MAX_LEVELS 8
 
@@ -122,7 +137,8 @@ typedef struct tango_denoise_args {
   int32_t text_len;            /* L */
   int32_t num_steps;           /* N */
   const int64_t* timesteps;    /* HOST [N] (DDPMScheduler.set_timesteps, scheduling_ddpm.py:184-204) */
-  const float* coef;           /* HOST [N][8]: sqrt(abar_t), sqrt(1-abar_t), coef_x0, coef_xt, sigma, sqrt(abar_prev), dir_coef, 0 */
+  const float* coef;           /* HOST [N][coef_width]; DDPM / DDIM: [N][8] sqrt(abar_t), sqrt(1-abar_t), coef_x0, coef_xt, sigma,
+                                * sqrt(abar_prev), dir_coef, 0; TANGO_RULE_DPM_MULTISTEP: [N][16] (layout above) */
   float guidance_scale;        /* CFG is on when > 1.0 (models.py:213) */
   int32_t prediction_type;     /* TANGO_PRED_* */
   int32_t rule;                /* TANGO_RULE_* */
@@ -145,6 +161,8 @@ typedef struct tango_denoise_args {
    * picks its plan from the mask's structure (the unconditional rows of a CFG batch keep one key, models.py:282-289); with the host
    * copy it does so without reading the device mask back, i.e. without a host sync on `stream`.  NULL: read-back (one sync). */
   const uint8_t* prompt_mask_host;
+  /* floats per row of `coef`: 0 means 8 (DDPM / DDIM); 16 for TANGO_RULE_DPM_MULTISTEP */
+  int32_t coef_width;
 } tango_denoise_args_t;
 
 const char* tango_last_error(void);
@@ -282,6 +300,13 @@ int tango_op_xattn_block(int dtype, const float* x, const float* gamma, const fl
                          const float* bias, const float* wo, const float* bo, float* out, int B, int HW, int L, float eps, void* stream);
 int tango_op_sched_step(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int HW,
                         int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, void* stream);
+
+/* one fused CFG + multistep DPM-Solver step (TANGO_RULE_DPM_MULTISTEP) at loop index `step` on caller-owned buffers: latents
+ * [B, C, HW] fp32 in/out, model_out_nchw [B2, C, HW] fp32 (B2 = 2B, [uncond; cond], when cfg), ring DEVICE [3][B][C][HW] fp32
+ * (the converted outputs of steps step - 1 and step - 2 in slots (step + 2) % 3 and (step + 1) % 3; this step's goes to
+ * step % 3), coef16 HOST [step + 1][16] (the table up to this step), algo 0 DPM-Solver++ / 1 DPM-Solver.  Synchronises. */
+int tango_op_sched_multistep(float* latents, const float* model_out_nchw, float* ring, const float* coef16, int step, int B, int C,
+                             int HW, int cfg, float guidance, int pred_type, int algo, void* stream);
 
 /* the N(0,1) values the denoise loop's device Philox generator injects at loop index `step` for global samples
  * [sample_offset, sample_offset + B): out fp32 [B, C, HW] (replaces randn_tensor inside DDPMScheduler.step,

@@ -13,7 +13,7 @@ MAX_LEVELS = 8
 
 DTYPES = {"fp32": 0, "float32": 0, "f32": 0, "fp16": 1, "float16": 1, "f16": 1, "bf16": 2, "bfloat16": 2}
 PRED = {"epsilon": 0, "sample": 1, "v_prediction": 2}
-RULE = {"ddpm": 0, "ddim": 1}
+RULE = {"ddpm": 0, "ddim": 1, "dpmsolver": 2}
 
 
 class TangoConfig(C.Structure):
@@ -94,6 +94,7 @@ class DenoiseArgs(C.Structure):
         ("chord_mask", C.c_void_p),
         ("chord_len", C.c_int32),
         ("prompt_mask_host", C.c_void_p),
+        ("coef_width", C.c_int32),
     ]
 
 
@@ -106,7 +107,7 @@ SYMBOLS = [
     "tango_engine_mel_frames", "tango_engine_mel_spectrogram",
     "tango_engine_last_denoise_ms", "tango_engine_last_step_gflop", "tango_engine_profile_unet", "tango_engine_profile_vae", "tango_engine_profile_vocoder", "tango_engine_set_plan_budget", "tango_engine_plan_stats", "tango_engine_drop_plans", "tango_op_conv2d", "tango_op_linear", "tango_op_linear_ln", "tango_op_ff_fused", "tango_op_qkv_stat", "tango_op_linear_qkv", "tango_op_linear_qkv_perm", "tango_op_conv1d",
     "tango_op_conv_transpose1d", "tango_op_groupnorm", "tango_op_layernorm", "tango_op_attention", "tango_op_attention_ex", "tango_op_xattn_block",
-    "tango_op_sched_step", "tango_op_philox_normal",
+    "tango_op_sched_step", "tango_op_sched_multistep", "tango_op_philox_normal",
 ]
 
 _lib = None
@@ -169,6 +170,7 @@ def load():
     lib.tango_op_attention_ex.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, vp]
     lib.tango_op_xattn_block.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, vp]
     lib.tango_op_sched_step.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, ci, ci, cf, vp]
+    lib.tango_op_sched_multistep.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp]
     lib.tango_op_philox_normal.argtypes = [vp, ci, ci, ci, ci, C.c_uint64, ci, vp]
     _lib = lib
     return lib

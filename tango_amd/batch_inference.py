@@ -84,6 +84,23 @@ def generate_and_save(generator, prompts: Sequence[str], num_steps: int = 200, g
     return rec
 
 
+def make_scheduler(name: str, config, solver_order: int = 2):
+    """the `--scheduler` choice built from a scheduler config (dict or `config` namespace); "ddpm" keeps the DDPM sampler"""
+    from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+    items = dict(config) if isinstance(config, dict) else dict(vars(config))
+    if name == "ddpm":
+        return DDPMScheduler.from_config({k: v for k, v in items.items() if k in _DDPM_KEYS})
+    if name == "ddim":
+        return DDIMScheduler.from_config({k: v for k, v in items.items() if k in _DDPM_KEYS and k != "variance_type"})
+    if name in ("dpmsolver++", "dpmsolver"):
+        return DPMSolverMultistepScheduler.from_config(dict(items, algorithm_type=name, solver_order=solver_order))
+    raise ValueError("unknown scheduler %r" % name)
+
+
+_DDPM_KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "prediction_type", "clip_sample", "variance_type",
+              "clip_sample_range")
+
+
 def parse_args(argv: Optional[Iterable[str]] = None):
     ap = argparse.ArgumentParser(description="Text-to-audio batch generation on the MI355X engine (generation + save half of inference.py).")
     ap.add_argument("--model", type=str, required=True, help="directory with the HF snapshot files (or a hub id)")
@@ -97,6 +114,10 @@ def parse_args(argv: Optional[Iterable[str]] = None):
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--dtype", type=str, default="fp16", choices=["fp32", "fp16", "bf16"])
     ap.add_argument("--out_root", type=str, default="outputs")
+    ap.add_argument("--scheduler", type=str, default="ddpm", choices=["ddpm", "ddim", "dpmsolver++", "dpmsolver"],
+                    help="sampler: ddpm (the reference's, 100-200 steps), ddim, or multistep DPM-Solver++ / DPM-Solver (20-25 steps); "
+                         "all built from the model's scheduler config")
+    ap.add_argument("--solver_order", type=int, default=2, choices=[1, 2, 3], help="order of the DPM-Solver schedulers")
     ap.add_argument("--text_encoder", type=str, default="torch", choices=["torch", "engine"],
                     help="torch: transformers T5EncoderModel under PyTorch-ROCm (the reference's module); engine: the checkpoint's "
                          "FLAN-T5 tensors on the HIP engine (tango_engine_encode_text)")
@@ -107,6 +128,7 @@ def main(argv: Optional[Iterable[str]] = None) -> dict:
     args = parse_args(argv)
     from .tango import Tango          # needs the HIP library and a GPU: fails loudly otherwise
     tango = Tango(args.model, device=args.device, dtype=args.dtype, text_encoder="engine" if args.text_encoder == "engine" else None)
+    tango.scheduler = make_scheduler(args.scheduler, tango.scheduler.config, args.solver_order)
     prompts = read_prompts(args.test_file, args.text_key, args.prefix)
     rec = generate_and_save(tango, prompts, args.num_steps, args.guidance, args.batch_size, args.num_samples, args.out_root,
                             tag="_".join(p for p in args.model.strip("/").split("/")[-2:] if p))

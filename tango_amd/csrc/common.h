@@ -383,9 +383,15 @@ struct SchedParams {
   int clip; float clip_range;
   unsigned long long seed;
   int sample_offset;     // global sample index of local sample 0 (multi-GPU invariant noise)
+  // multistep rule (rule 2, sched_multistep_kernel): fp32 ring of the converted model outputs of the last three steps,
+  // [3][B][C][HW] NCHW, slot = step % 3; `coef` rows are `coef_w` (16) floats wide (include/tango_engine.h)
+  float* ring;
+  int coef_w;
+  int algo;              // 0 DPM-Solver++ (x0 form), 1 DPM-Solver (eps form)
 };
-// `dev_params` is a DEVICE copy of SchedParams; the grid covers max_positions >= B*HW (one thread per latent position)
-int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s);
+// `dev_params` is a DEVICE copy of SchedParams; the grid covers max_positions >= B*HW (one thread per latent position).
+// `rule` (host copy of the block's rule) picks the kernel: 0 / 1 sched_step_kernel, 2 sched_multistep_kernel
+int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule = 0);
 int launch_step_inc(int* step_ptr, hipStream_t s);
 // test hook: the N(0,1) draws of sched_step at loop index `step` -> out fp32 [B][C][HW]
 int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned long long seed, int sample_offset, hipStream_t s);

@@ -122,8 +122,88 @@ int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned lo
   return 0;
 }
 
-int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s) {
+// ------------------------------------------------------------------------------------------
+// Fused CFG combine + multistep DPM-Solver / DPM-Solver++ update (rule 2; fork
+// mustango/diffusers/src/diffusers/schedulers/scheduling_dpmsolver_multistep.py:220-495).  One thread per (sample, position),
+// 8 channels.  Every scalar comes from the host table row (tango_amd/scheduler.py DPMSolverMultistepScheduler.coef_table,
+// computed as the fork's own fp32 0-dim expressions), and the tensor expressions keep the fork's association order with FMA
+// contraction off, so with fp32 inputs the step equals the fork's step() bit for bit.
+// row = {alpha_s0, sigma_s0, kx, c0, c1, c2, 1/r0, 1/r1, r0/(r0+r1), 1/(r0+r1), order, algo, 0...}
+// The converted output m0 of this step goes to ring slot step % 3; m1 / m2 (steps - 1, - 2) are read from the other two slots
+// only when the row's order asks for them, i.e. only once an earlier step of the same loop has written them.  No noise term.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void sched_multistep_kernel(const SchedParams* __restrict__ pp) {
+#pragma clang fp contract(off)
+  const SchedParams p = *pp;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.B * p.HW) return;
+  const int b = idx / p.HW, hw = idx - b * p.HW;
+  const int step = *p.step_ptr;
+  const float* cf = p.coef + (int64_t)step * p.coef_w;
+  const float a_s0 = cf[0], s_s0 = cf[1], kx = cf[2], c0 = cf[3], c1 = cf[4], c2 = cf[5];
+  const float ir0 = cf[6], ir1 = cf[7], q = cf[8], ir01 = cf[9];
+  const int order = (int)cf[10];
+  const int C = p.C;
+  const int64_t slot = (int64_t)p.B * C * p.HW;
+  float* r0 = p.ring + (int64_t)(step % 3) * slot;
+  const float* r1 = p.ring + (int64_t)((step + 2) % 3) * slot;   // step - 1
+  const float* r2 = p.ring + (int64_t)((step + 1) % 3) * slot;   // step - 2
+  const float* eu = p.eps + ((int64_t)b * p.HW + hw) * C;
+  const float* ec = p.cfg ? p.eps + ((int64_t)(p.B + b) * p.HW + hw) * C : nullptr;
+  T* xo0 = (T*)p.xin + ((int64_t)b * p.HW + hw) * p.xin_ld;
+  T* xo1 = p.cfg ? (T*)p.xin + ((int64_t)(p.B + b) * p.HW + hw) * p.xin_ld : nullptr;
+  for (int c = 0; c < C; ++c) {
+    const int64_t o = ((int64_t)b * C + c) * p.HW + hw;
+    const float x = p.lat[o];
+    float v = eu[c];
+    if (p.cfg) { const float dlt = ec[c] - v; const float gd = p.guidance * dlt; v = v + gd; }   // models.py:246
+    float m0;                                                                                  // convert_model_output
+    if (p.algo == 0) {                                                                         // x0
+      if (p.pred_type == 0) { const float t0 = s_s0 * v; const float d0 = x - t0; m0 = d0 / a_s0; }
+      else if (p.pred_type == 1) m0 = v;
+      else { const float t0 = a_s0 * x; const float t1 = s_s0 * v; m0 = t0 - t1; }
+    } else {                                                                                   // eps
+      if (p.pred_type == 0) m0 = v;
+      else if (p.pred_type == 1) { const float t0 = a_s0 * v; const float d0 = x - t0; m0 = d0 / s_s0; }
+      else { const float t0 = a_s0 * v; const float t1 = s_s0 * x; m0 = t0 + t1; }
+    }
+    float prev;
+    { const float t0 = kx * x; const float t1 = c0 * m0; prev = t0 + t1; }
+    if (order == 2) {
+      const float m1 = r1[o];
+      const float d = m0 - m1; const float D1 = ir0 * d;
+      const float t2 = c1 * D1; prev = prev + t2;
+    } else if (order == 3) {
+      const float m1 = r1[o], m2 = r2[o];
+      const float e0 = m0 - m1; const float D10 = ir0 * e0;
+      const float e1 = m1 - m2; const float D11 = ir1 * e1;
+      const float dd = D10 - D11;
+      const float t3 = q * dd; const float D1 = D10 + t3;
+      const float D2 = ir01 * dd;
+      const float t4 = c1 * D1; prev = prev + t4;
+      const float t5 = c2 * D2; prev = prev + t5;
+    }
+    r0[o] = m0;
+    p.lat[o] = prev;
+    const T tv = from_f<T>(prev);
+    xo0[c] = tv;
+    if (xo1) xo1[c] = tv;
+  }
+}
+
+int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule) {
   const unsigned nb = (unsigned)((max_positions + 255) / 256);   // >= B*HW of the block; surplus threads exit
+  if (rule == 2) {
+    switch (dtype) {
+      case DT_F32: hipLaunchKernelGGL((sched_multistep_kernel<float>), dim3(nb), dim3(256), 0, s, dev_params); break;
+      case DT_F16: hipLaunchKernelGGL((sched_multistep_kernel<f16>), dim3(nb), dim3(256), 0, s, dev_params); break;
+      case DT_BF16: hipLaunchKernelGGL((sched_multistep_kernel<bf16>), dim3(nb), dim3(256), 0, s, dev_params); break;
+      default: TANGO_FAIL("sched_multistep: bad dtype");
+    }
+    TANGO_HIP(hipGetLastError());
+    return 0;
+  }
   switch (dtype) {
     case DT_F32: hipLaunchKernelGGL((sched_step_kernel<float>), dim3(nb), dim3(256), 0, s, dev_params); break;
     case DT_F16: hipLaunchKernelGGL((sched_step_kernel<f16>), dim3(nb), dim3(256), 0, s, dev_params); break;

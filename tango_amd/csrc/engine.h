@@ -142,6 +142,13 @@ struct UNetPlan {
   hipGraph_t graph_k = nullptr;
   hipGraphExec_t exec_k = nullptr;
   int k_steps = 0;
+  // the same two graphs with the multistep update (TANGO_RULE_DPM_MULTISTEP): the update kernel is chosen at launch, so a graph
+  // captured for DDPM / DDIM cannot replay a multistep loop (and vice versa); everything else is shared
+  hipGraph_t graph_ms = nullptr;
+  hipGraphExec_t exec_ms = nullptr;
+  hipGraph_t graph_k_ms = nullptr;
+  hipGraphExec_t exec_k_ms = nullptr;
+  int k_steps_ms = 0;
   // Two independent chains (round 5; Engine::denoise): a "dual" plan owns only the UNet input / output buffers of the whole batch; its
   // two children run the first and the second half of the samples (no op of the UNet crosses samples) as two branches of the captured
   // graph, so that one branch's dispatch gaps and kernel tails are filled by the other's kernels.  A child takes xin / eps from its
@@ -303,7 +310,9 @@ class Engine {
   unsigned* d_sync = nullptr;   // barrier words of the cooperative kernels (common.h: coop_sync_words()), zeroed once at init
   SchedParams* d_sched = nullptr;   // device copy of the current call's scheduler parameter block
   int64_t* d_ts = nullptr;       // [max_steps]
-  float* d_coef = nullptr;       // [max_steps][8]
+  float* d_coef = nullptr;       // [max_steps][16] (DDPM / DDIM rows use the first 8 floats of a packed [N][8] table)
+  float* d_ring = nullptr;       // multistep history [3][ring_batch][C][HW] fp32 (hipMalloc'd, grown with the batch; not in `owned`)
+  int ring_batch = 0;
   float* d_sin = nullptr;        // [max_steps][ch0]
   float* d_t1 = nullptr;         // [max_steps][temb]
   float* d_temb = nullptr;       // [max_steps][temb]  silu(emb)

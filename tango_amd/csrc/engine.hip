@@ -505,6 +505,7 @@ Engine::~Engine() {
   for (auto& kv : t5_plans) if (kv.second->slab) (void)hipFree(kv.second->slab);
   for (auto& kv : stft_plans) if (kv.second->slab) (void)hipFree(kv.second->slab);
   for (void* p : owned) (void)hipFree(p);
+  if (d_ring) (void)hipFree(d_ring);
   for (auto& hs : hslots) {
     if (hs.ev) (void)hipEventDestroy(hs.ev);
     if (hs.buf) (void)hipHostFree(hs.buf);
@@ -604,6 +605,9 @@ void Engine::free_unet_plan(UNetPlan& P) {
   if (P.exec_k) (void)hipGraphExecDestroy(P.exec_k);
   if (P.graph_k) (void)hipGraphDestroy(P.graph_k);
   P.exec = P.exec_k = nullptr; P.graph = P.graph_k = nullptr;
+  for (hipGraphExec_t x : {P.exec_ms, P.exec_k_ms}) if (x) (void)hipGraphExecDestroy(x);
+  for (hipGraph_t g : {P.graph_ms, P.graph_k_ms}) if (g) (void)hipGraphDestroy(g);
+  P.exec_ms = P.exec_k_ms = nullptr; P.graph_ms = P.graph_k_ms = nullptr;
   for (auto& c : P.child) if (c) { free_unet_plan(*c); c.reset(); }
   release_slab(&P.slab, P.meta);
 }
@@ -1039,7 +1043,7 @@ int Engine::init() {
     d_step = (int*)dmalloc(256);
     d_sched = (SchedParams*)dmalloc(sizeof(SchedParams));
     d_ts = (int64_t*)dmalloc((size_t)max_steps * 8);
-    d_coef = (float*)dmalloc((size_t)max_steps * 8 * 4);
+    d_coef = (float*)dmalloc((size_t)max_steps * 16 * 4);
     d_sin = (float*)dmalloc((size_t)max_steps * cfg.unet_channels[0] * 4);
     d_t1 = (float*)dmalloc((size_t)max_steps * temb * 4);
     d_temb = (float*)dmalloc((size_t)max_steps * temb * 4);
@@ -1486,6 +1490,20 @@ int Engine::unet_chains_for(int B2) const {
 
 int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
   if (a.num_steps <= 0) TANGO_FAIL("denoise: num_steps must be positive");
+  if (a.rule != TANGO_RULE_DDPM && a.rule != TANGO_RULE_DDIM && a.rule != TANGO_RULE_DPM_MULTISTEP) TANGO_FAIL("denoise: unknown rule");
+  const bool ms = a.rule == TANGO_RULE_DPM_MULTISTEP;
+  const int coef_w = a.coef_width ? a.coef_width : 8;
+  if (coef_w != (ms ? 16 : 8)) TANGO_FAIL(ms ? "denoise: the multistep rule takes 16-float coefficient rows (coef_width 16)"
+                                             : "denoise: DDPM / DDIM take 8-float coefficient rows (coef_width 0 or 8)");
+  if (ms && a.noise) TANGO_FAIL("denoise: the multistep rule is deterministic: noise must be NULL");
+  if (ms && a.clip_sample) TANGO_FAIL("denoise: clip_sample is not supported by the multistep rule");
+  if (ms && a.coef[11] != 0.0f && a.coef[11] != 1.0f) TANGO_FAIL("denoise: multistep table column 11 (algorithm) must be 0 or 1");
+  if (ms) {
+    for (int i = 0; i < a.num_steps; ++i) {          // a row never reads a history slot this loop has not written
+      const float o = a.coef[(size_t)i * 16 + 10];
+      if (!(o == 1.0f || (o == 2.0f && i >= 1) || (o == 3.0f && i >= 2))) TANGO_FAIL("denoise: multistep table row with a bad order");
+    }
+  }
   const bool cfg_on = a.guidance_scale > 1.0f;
   const int B = a.batch, B2 = cfg_on ? 2 * B : B;
   UNetPlan* P;
@@ -1499,16 +1517,23 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
   TANGO_TRY(ensure_temb(a.timesteps, a.num_steps, s));
   const int HW = cfg.latent_h * cfg.latent_w;
   const int C = cfg.unet_in_channels;
+  if (ms && B > ring_batch) {
+    // outside any capture; every earlier use of the old ring (replays in flight on any stream) completes before it is freed
+    if (d_ring) { TANGO_HIP(hipDeviceSynchronize()); (void)hipFree(d_ring); d_ring = nullptr; ring_batch = 0; }
+    if (hipMalloc(&d_ring, (size_t)3 * B * C * HW * 4) != hipSuccess) { d_ring = nullptr; TANGO_FAIL("denoise: hipMalloc of the multistep ring failed"); }
+    ring_batch = B;
+  }
   SchedParams sp;
   sp.lat = a.latents; sp.eps = P->eps; sp.xin = P->xin; sp.xin_ld = 8;
   sp.noise = a.noise; sp.coef = d_coef; sp.step_ptr = d_step;
   sp.B = B; sp.C = C; sp.HW = HW; sp.cfg = cfg_on ? 1 : 0; sp.guidance = a.guidance_scale;
   sp.pred_type = a.prediction_type; sp.rule = a.rule; sp.clip = a.clip_sample; sp.clip_range = a.clip_sample_range;
   sp.seed = a.seed; sp.sample_offset = a.sample_offset;
+  sp.ring = ms ? d_ring : nullptr; sp.coef_w = coef_w; sp.algo = ms ? (int)a.coef[11] : 0;
   // per-call tables and the scheduler parameter block live in device memory, so the captured graph of one denoise
   // step (UNet + CFG/scheduler update + step counter) is independent of the call's pointers and scalars
   // (both sources are pageable / transient host memory: pinned staging slots, no host sync -- stage_h2d)
-  TANGO_TRY(stage_h2d(d_coef, a.coef, (size_t)a.num_steps * 8 * 4, s));
+  TANGO_TRY(stage_h2d(d_coef, a.coef, (size_t)a.num_steps * coef_w * 4, s));
   TANGO_TRY(stage_h2d(d_sched, &sp, sizeof(SchedParams), s));
   TANGO_HIP(hipMemsetAsync(d_step, 0, 4, s));
   {
@@ -1557,7 +1582,7 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
       TANGO_HIP(hipEventRecord(ej, st2));
       TANGO_HIP(hipStreamWaitEvent(st, ej, 0));
     }
-    TANGO_TRY(launch_sched_step(dt, d_sched, B2 * HW, st));
+    TANGO_TRY(launch_sched_step(dt, d_sched, B2 * HW, st, a.rule));
     return launch_step_inc(d_step, st);
   };
   // capture `n` steps once per plan; every per-step quantity is read through d_step / d_sched
@@ -1576,25 +1601,31 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
     TANGO_HIP(hipGraphInstantiate(x_out, g, nullptr, nullptr, 0));
     return 0;
   };
-  if (a.use_graph && !P->exec) TANGO_TRY(capture(1, &P->graph, &P->exec));
+  // the update kernel is fixed at capture: the multistep rule replays graphs of its own
+  hipGraph_t& graph1 = ms ? P->graph_ms : P->graph;
+  hipGraphExec_t& exec1 = ms ? P->exec_ms : P->exec;
+  hipGraph_t& graphk = ms ? P->graph_k_ms : P->graph_k;
+  hipGraphExec_t& execk = ms ? P->exec_k_ms : P->exec_k;
+  int& ksteps = ms ? P->k_steps_ms : P->k_steps;
+  if (a.use_graph && !exec1) TANGO_TRY(capture(1, &graph1, &exec1));
   // k steps per replay (round 5; north_star: "the 100-200 denoise steps captured as a hipGraph"): the same kernel sequence captured k
   // times back to back -- every per-step quantity is read through the device-side step counter, so a k-step graph is just k copies.
   // What it removes is the host-side launch of every replay and the gap between two replays, which only shows at small batches
   // (B = 1: a 7-ms step); the remainder of num_steps / k runs on the one-step graph.
   int kk = tuning().graph_steps > 0 ? tuning().graph_steps : graph_steps_default(B2);
   if (kk > a.num_steps) kk = a.num_steps;
-  if (a.use_graph && kk > 1 && (!P->exec_k || P->k_steps != kk)) {
-    if (P->exec_k) { TANGO_HIP(hipStreamSynchronize(s)); (void)hipGraphExecDestroy(P->exec_k); (void)hipGraphDestroy(P->graph_k); P->exec_k = nullptr; P->graph_k = nullptr; }
-    TANGO_TRY(capture(kk, &P->graph_k, &P->exec_k));
-    P->k_steps = kk;
+  if (a.use_graph && kk > 1 && (!execk || ksteps != kk)) {
+    if (execk) { TANGO_HIP(hipStreamSynchronize(s)); (void)hipGraphExecDestroy(execk); (void)hipGraphDestroy(graphk); execk = nullptr; graphk = nullptr; }
+    TANGO_TRY(capture(kk, &graphk, &execk));
+    ksteps = kk;
   }
   TANGO_HIP(hipEventRecord(ev0, s));
   {
     int i = 0;
     if (a.use_graph && kk > 1)
-      for (; i + kk <= a.num_steps; i += kk) TANGO_HIP(hipGraphLaunch(P->exec_k, s));
+      for (; i + kk <= a.num_steps; i += kk) TANGO_HIP(hipGraphLaunch(execk, s));
     for (; i < a.num_steps; ++i) {
-      if (a.use_graph) TANGO_HIP(hipGraphLaunch(P->exec, s));
+      if (a.use_graph) TANGO_HIP(hipGraphLaunch(exec1, s));
       else TANGO_TRY(run_step(s, aux_stream, ev_fork_e, ev_join_e));
     }
   }

@@ -608,11 +608,40 @@ int tango_op_sched_step(float* latents, const float* model_out_nchw, const float
   SchedParams p;
   p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = 8; p.noise = noise; p.coef = dcoef; p.step_ptr = dstep;
   p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = rule; p.clip = clip;
-  p.clip_range = clip_range; p.seed = 0; p.sample_offset = 0;
+  p.clip_range = clip_range; p.seed = 0; p.sample_offset = 0; p.ring = nullptr; p.coef_w = 8; p.algo = 0;
   SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
   if (!dp) TANGO_FAIL("op_sched_step: alloc");
   TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
   TANGO_TRY(launch_sched_step(DT_F32, dp, B * HW, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_sched_multistep(float* latents, const float* model_out_nchw, float* ring, const float* coef16, int step, int B, int C,
+                             int HW, int cfg, float guidance, int pred_type, int algo, void* stream) {
+  if (step < 0 || B <= 0 || C <= 0 || HW <= 0) TANGO_FAIL("op_sched_multistep: bad sizes");
+  if (algo != 0 && algo != 1) TANGO_FAIL("op_sched_multistep: algo must be 0 (DPM-Solver++) or 1 (DPM-Solver)");
+  const int order = (int)coef16[(size_t)step * 16 + 10];
+  if (order < 1 || order > 3 || order > step + 1) TANGO_FAIL("op_sched_multistep: row order must be in [1, min(3, step + 1)]");
+  hipStream_t s = (hipStream_t)stream;
+  Scratch sc;
+  const int B2 = cfg ? 2 * B : B;
+  float* eps = (float*)sc.get((size_t)B2 * HW * C * 4);
+  float* xin = (float*)sc.get((size_t)B2 * HW * C * 4);
+  float* dcoef = (float*)sc.get((size_t)(step + 1) * 16 * 4);
+  int* dstep = (int*)sc.get(256);
+  if (!eps || !xin || !dcoef || !dstep) TANGO_FAIL("op_sched_multistep: alloc");
+  TANGO_TRY(launch_nchw_to_nhwc(DT_F32, model_out_nchw, eps, C, B2, C, HW, 1, 1.0f, s));
+  TANGO_HIP(hipMemcpyAsync(dcoef, coef16, (size_t)(step + 1) * 16 * 4, hipMemcpyHostToDevice, s));
+  TANGO_HIP(hipMemcpyAsync(dstep, &step, 4, hipMemcpyHostToDevice, s));
+  SchedParams p;
+  p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = C; p.noise = nullptr; p.coef = dcoef; p.step_ptr = dstep;
+  p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = TANGO_RULE_DPM_MULTISTEP;
+  p.clip = 0; p.clip_range = 1.0f; p.seed = 0; p.sample_offset = 0; p.ring = ring; p.coef_w = 16; p.algo = algo;
+  SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
+  if (!dp) TANGO_FAIL("op_sched_multistep: alloc");
+  TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
+  TANGO_TRY(launch_sched_step(DT_F32, dp, B * HW, s, TANGO_RULE_DPM_MULTISTEP));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -259,7 +259,7 @@ class Engine:
                 rule="ddpm", clip_sample=False, clip_sample_range=1.0, noise=None, seed=0, sample_offset=0, use_graph=True,
                 beat_embeds=None, beat_mask=None, chord_embeds=None, chord_mask=None, prompt_mask_host=None):
         """In-place denoise of `latents` [B,8,256,16] (fp32 cuda).  `timesteps` int64 [N] and `coef`
-        float32 [N,8] are host tables from tango_amd.scheduler.  `prompt_mask_host`: the caller's CPU copy of a `prompt_mask`
+        float32 [N,8] ([N,16] for rule "dpmsolver") are host tables from tango_amd.scheduler.  `prompt_mask_host`: the caller's CPU copy of a `prompt_mask`
         that already lives on the device (the tokenizer's attention mask): the engine then picks its plan from it instead of
         reading the device mask back, i.e. the call does not synchronise the host."""
         assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
@@ -284,7 +284,13 @@ class Engine:
         self._check_cond("prompt_embeds", enc, mask, rows)
         ts = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int64))
         cf = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
-        assert cf.shape == (len(ts), 8)
+        width = 16 if rule == "dpmsolver" else 8
+        if cf.shape != (len(ts), width):
+            raise ValueError("rule %r takes a coefficient table [%d, %d], got %s" % (rule, len(ts), width, cf.shape))
+        if rule == "dpmsolver" and noise is not None:
+            raise ValueError("the multistep DPM-Solver rule is deterministic: it takes no step noise")
+        if rule == "dpmsolver" and clip_sample:
+            raise ValueError("clip_sample is not supported by the multistep DPM-Solver rule")
         if noise is not None:
             noise = self._f32(noise)
             if tuple(noise.shape) != (len(ts),) + tuple(latents.shape):
@@ -308,6 +314,7 @@ class Engine:
         a.seed = int(seed)
         a.sample_offset = int(sample_offset)
         a.use_graph = 1 if use_graph else 0
+        a.coef_width = width
         keep = []
         if self.unet_cfg.get("music"):
             if beat_embeds is None or chord_embeds is None:

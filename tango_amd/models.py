@@ -14,7 +14,8 @@ from typing import List, Optional
 import torch
 
 from .engine import Engine, normalize_unet_config
-from .scheduler import DDIMScheduler, DDPMScheduler  # noqa: F401  (re-exported like `from models import DDPMScheduler`)
+from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler  # noqa: F401  (re-exported like `from models import DDPMScheduler`)
+from .scheduler import from_diffusers
 
 _TEXT_BUCKETS = (16, 32, 64, 128, 256, 512)
 
@@ -220,6 +221,9 @@ class AudioDiffusion:
         tables, one engine call (`extra_conditions`: the Music UNet's beat / chord streams)"""
         cfg_on = guidance_scale > 1.0
         B = prompt_embeds.shape[0] // 2 if cfg_on else prompt_embeds.shape[0]
+        if not hasattr(inference_scheduler, "coef_table"):
+            # a diffusers / fork scheduler object (the reference's loop takes any): the engine's class of the same name and config
+            inference_scheduler = from_diffusers(inference_scheduler)
         inference_scheduler.set_timesteps(num_steps, device=self.device)
         timesteps = inference_scheduler.timesteps
         if latents is None:

@@ -152,3 +152,254 @@ class DDIMScheduler(_SchedulerBase):
             direction = (1 - a_prev - std ** 2) ** 0.5                       # :340
             rows.append([float(a_t ** 0.5), float(b_t ** 0.5), 0.0, 0.0, float(std), float(a_prev ** 0.5), float(direction), 0.0])
         return np.asarray(rows, dtype=np.float32)
+
+
+def _glide_cosine_betas(num_train_timesteps, max_beta=0.999):
+    """"squaredcos_cap_v2": the cosine schedule of Nichol & Dhariwal (2021), abar(t) = cos((t + 0.008) / 1.008 * pi / 2)^2, as
+    betas 1 - abar(t_{i+1}) / abar(t_i) clipped at `max_beta`, computed in Python floats and rounded to fp32 once"""
+    import math
+
+    def abar(x):
+        return math.cos((x + 0.008) / 1.008 * math.pi / 2) ** 2
+
+    T = num_train_timesteps
+    return torch.tensor([min(1 - abar((i + 1) / T) / abar(i / T), max_beta) for i in range(T)], dtype=torch.float32)
+
+
+class DPMSolverMultistepScheduler:
+    """Multistep DPM-Solver / DPM-Solver++ (Lu et al. 2022, arXiv 2206.00927 and 2211.01095), with the constructor, defaults and
+    step semantics of the fork's scheduling_dpmsolver_multistep.py:124-495: 20-25 UNet calls instead of DDPM's 100-200.
+
+    The update of step i is a linear combination of the current latent x, the converted model output m0 (x0 for `dpmsolver++`,
+    eps for `dpmsolver`) and the converted outputs m1, m2 of the two steps before, with scalars that depend only on the schedule.
+    `coef_table()` computes those scalars on the host, as the fork's own 0-dim fp32 tensor expressions, so the engine's fused
+    kernel (rule 2) reproduces the fork's `step()` bit for bit; `step()` here applies the same table row in torch (the tests' reference loop,
+    callers that drive their own loop).  Deterministic: there is no noise term.
+
+    Row layout of `coef_table()` ([N, 16] fp32, include/tango_engine.h): alpha_s0, sigma_s0, kx, c0, c1, c2, 1/r0, 1/r1,
+    r0/(r0+r1), 1/(r0+r1), order, algorithm (0 dpmsolver++, 1 dpmsolver), 0, 0, 0, 0.  The update is
+        order 1: kx*x + c0*D0
+        order 2: (kx*x + c0*D0) + c1*D1                 D1 = (1/r0)*(m0 - m1)
+        order 3: ((kx*x + c0*D0) + c1*D1) + c2*D2       D1_0 = (1/r0)*(m0 - m1), D1_1 = (1/r1)*(m1 - m2),
+                                                        D1 = D1_0 + (r0/(r0+r1))*(D1_0 - D1_1), D2 = (1/(r0+r1))*(D1_0 - D1_1)
+    with D0 = m0; the fork's subtracted terms are stored as negated coefficients (a - k*b == a + (-k)*b exactly)."""
+    order = 1
+    rule = "dpmsolver"
+    COEF_WIDTH = 16
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
+                 sample_max_value=1.0, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True):
+        if trained_betas is not None:
+            betas = torch.tensor(trained_betas, dtype=torch.float32)
+        elif beta_schedule == "linear":
+            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        elif beta_schedule == "scaled_linear":
+            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        elif beta_schedule == "squaredcos_cap_v2":
+            betas = _glide_cosine_betas(num_train_timesteps)
+        else:
+            raise NotImplementedError("%s does is not implemented for %s" % (beta_schedule, type(self).__name__))
+        if algorithm_type == "deis":                      # the fork's quirk: DEIS configs run as DPM-Solver++
+            algorithm_type = "dpmsolver++"
+        if algorithm_type not in ("dpmsolver", "dpmsolver++"):
+            raise NotImplementedError("%s does is not implemented for %s" % (algorithm_type, type(self).__name__))
+        if solver_type in ("logrho", "bh1", "bh2"):       # the fork's quirk: UniPC / DEIS solver types run as midpoint
+            solver_type = "midpoint"
+        if solver_type not in ("midpoint", "heun"):
+            raise NotImplementedError("%s does is not implemented for %s" % (solver_type, type(self).__name__))
+        if solver_order not in (1, 2, 3):
+            raise ValueError("solver_order must be 1, 2 or 3, got %r" % (solver_order,))
+        if prediction_type not in ("epsilon", "sample", "v_prediction"):
+            raise ValueError("prediction_type given as %s must be one of `epsilon`, `sample`, or `v_prediction` for the "
+                             "DPMSolverMultistepScheduler." % prediction_type)
+        if thresholding:
+            raise NotImplementedError("thresholding=True is not supported: dynamic thresholding needs a per-sample quantile of the "
+                                      "predicted x0 and is meant for pixel-space models, not this latent model")
+        T = num_train_timesteps
+        self.betas = betas
+        self.alphas = 1.0 - betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self.init_noise_sigma = 1.0
+        self.config = SimpleNamespace(num_train_timesteps=T, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                                      trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type,
+                                      thresholding=False, dynamic_thresholding_ratio=dynamic_thresholding_ratio,
+                                      sample_max_value=sample_max_value, algorithm_type=algorithm_type, solver_type=solver_type,
+                                      lower_order_final=lower_order_final, clip_sample=False, clip_sample_range=1.0)
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.linspace(0, T - 1, T, dtype=np.float32)[::-1].copy())
+        self.model_outputs = [None] * solver_order
+        self.lower_order_nums = 0
+
+    @classmethod
+    def from_config(cls, config):
+        """`config`: a dict or the `config` namespace of another scheduler (`DPMSolverMultistepScheduler.from_config(
+        tango.scheduler.config)`); keys the constructor does not take are ignored"""
+        items = config.items() if isinstance(config, dict) else vars(config).items()
+        accepted = _init_params(cls)
+        return cls(**{k: v for k, v in items if k in accepted})
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """N + 1 points evenly spaced over [0, T-1], rounded, descending, the final 0 dropped (scheduling_dpmsolver_multistep.py:
+        185-206).  The table stays on the host: the engine takes it as host data."""
+        T = self.config.num_train_timesteps
+        self.num_inference_steps = num_inference_steps
+        ts = np.linspace(0, T - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+        self.timesteps = torch.from_numpy(ts)
+        self.model_outputs = [None] * self.config.solver_order
+        self.lower_order_nums = 0
+
+    # ---- the per-step scalars ------------------------------------------------------------------------------------------------
+    def _step_order(self, i, lower_order_nums):
+        """the order the fork's step() runs at loop index i (scheduling_dpmsolver_multistep.py:464-487)"""
+        n = len(self.timesteps)
+        short = self.config.lower_order_final and n < 15
+        k = self.config.solver_order
+        if k == 1 or lower_order_nums < 1 or (short and i == n - 1):
+            return 1
+        if k == 2 or lower_order_nums < 2 or (short and i == n - 2):
+            return 2
+        return 3
+
+    def _row(self, i, order):
+        """row i of the table as 0-dim fp32 tensors, each computed in the fork's expression order"""
+        ts = self.timesteps
+        s0 = int(ts[i])
+        t = 0 if i == len(ts) - 1 else int(ts[i + 1])             # the final step targets timestep 0
+        z = torch.tensor(0.0)
+        lam_t, lam_s0 = self.lambda_t[t], self.lambda_t[s0]
+        alpha_t, alpha_s0 = self.alpha_t[t], self.alpha_t[s0]
+        sigma_t, sigma_s0 = self.sigma_t[t], self.sigma_t[s0]
+        h = lam_t - lam_s0
+        pp = self.config.algorithm_type == "dpmsolver++"
+        heun = self.config.solver_type == "heun"
+        if pp:
+            kx = sigma_t / sigma_s0
+            c0 = -(alpha_t * (torch.exp(-h) - 1.0))
+        else:
+            kx = alpha_t / alpha_s0
+            c0 = -(sigma_t * (torch.exp(h) - 1.0))
+        c1 = c2 = inv_r0 = inv_r1 = q = inv_r01 = z
+        if order >= 2:
+            lam_s1 = self.lambda_t[int(ts[i - 1])]
+            h_0 = lam_s0 - lam_s1
+            r0 = h_0 / h
+            inv_r0 = 1.0 / r0
+        if order == 2:
+            if pp:
+                c1 = (alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)) if heun else -(0.5 * (alpha_t * (torch.exp(-h) - 1.0)))
+            else:
+                c1 = -(sigma_t * ((torch.exp(h) - 1.0) / h - 1.0)) if heun else -(0.5 * (sigma_t * (torch.exp(h) - 1.0)))
+        elif order == 3:
+            lam_s2 = self.lambda_t[int(ts[i - 2])]
+            h_1 = lam_s1 - lam_s2
+            r1 = h_1 / h
+            inv_r1 = 1.0 / r1
+            q = r0 / (r0 + r1)
+            inv_r01 = 1.0 / (r0 + r1)
+            if pp:
+                c1 = alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)
+                c2 = -(alpha_t * ((torch.exp(-h) - 1.0 + h) / h ** 2 - 0.5))
+            else:
+                c1 = -(sigma_t * ((torch.exp(h) - 1.0) / h - 1.0))
+                c2 = -(sigma_t * ((torch.exp(h) - 1.0 - h) / h ** 2 - 0.5))
+        return [alpha_s0, sigma_s0, kx, c0, c1, c2, inv_r0, inv_r1, q, inv_r01]
+
+    def _check_distinct(self):
+        ts = self.timesteps.tolist()
+        if len(set(ts)) != len(ts):
+            raise ValueError("the schedule of %d steps repeats a timestep (%d distinct of %d training steps): a multistep solver "
+                             "cannot step between equal timesteps" % (len(ts), len(set(ts)), self.config.num_train_timesteps))
+
+    def coef_table(self) -> np.ndarray:
+        """[N, 16] fp32 per-step scalars of the fused update (layout: class docstring)"""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() before coef_table()")
+        self._check_distinct()
+        algo = 0.0 if self.config.algorithm_type == "dpmsolver++" else 1.0
+        rows = []
+        for i in range(len(self.timesteps)):
+            order = self._step_order(i, min(i, self.config.solver_order))
+            rows.append([float(v) for v in self._row(i, order)] + [float(order), algo, 0.0, 0.0, 0.0, 0.0])
+        return np.asarray(rows, dtype=np.float32)
+
+    # ---- torch step (the tests' reference loop, callers that drive their own loop) ----------------------------------------------
+    def convert_model_output(self, model_output, timestep, sample):
+        """x0 (dpmsolver++) or eps (dpmsolver) from the model's prediction (scheduling_dpmsolver_multistep.py:220-281)"""
+        a, s = self.alpha_t[timestep], self.sigma_t[timestep]
+        p = self.config.prediction_type
+        if self.config.algorithm_type == "dpmsolver++":
+            if p == "epsilon":
+                return (sample - s * model_output) / a
+            if p == "sample":
+                return model_output
+            return a * sample - s * model_output
+        if p == "epsilon":
+            return model_output
+        if p == "sample":
+            return (sample - a * model_output) / s
+        return a * model_output + s * sample
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        """one multistep update; keeps the fork's state (`model_outputs`, `lower_order_nums`) between calls"""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        hit = (self.timesteps == int(timestep)).nonzero()
+        if len(hit) > 1:
+            raise ValueError("timestep %d occurs %d times in the schedule" % (int(timestep), len(hit)))
+        i = len(self.timesteps) - 1 if len(hit) == 0 else int(hit[0, 0])
+        order = self._step_order(i, self.lower_order_nums)
+        alpha_s0, sigma_s0, kx, c0, c1, c2, inv_r0, inv_r1, q, inv_r01 = self._row(i, order)
+        m0 = self.convert_model_output(model_output, int(self.timesteps[i]), sample)
+        self.model_outputs = self.model_outputs[1:] + [m0]
+        x = kx * sample + c0 * m0
+        if order == 2:
+            x = x + c1 * (inv_r0 * (m0 - self.model_outputs[-2]))
+        elif order == 3:
+            m1, m2 = self.model_outputs[-2], self.model_outputs[-3]
+            d10, d11 = inv_r0 * (m0 - m1), inv_r1 * (m1 - m2)
+            x = (x + c1 * (d10 + q * (d10 - d11))) + c2 * (inv_r01 * (d10 - d11))
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+        return _StepOutput(x) if return_dict else (x,)
+
+
+_FROM_DIFFUSERS = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
+                   "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}
+
+
+def from_diffusers(obj):
+    """the engine's scheduler for a diffusers (or fork) scheduler object, chosen by class name and built from `obj.config`; the
+    engine's own scheduler objects are returned as they are"""
+    if hasattr(obj, "coef_table"):
+        return obj
+    name = type(obj).__name__
+    cls = _FROM_DIFFUSERS.get(name)
+    if cls is None:
+        raise TypeError("cannot run a %s on the engine: supported schedulers are %s" % (name, ", ".join(sorted(_FROM_DIFFUSERS))))
+    cfg = obj.config
+    items = dict(cfg.items()) if hasattr(cfg, "items") else dict(vars(cfg))
+    if cls is not DPMSolverMultistepScheduler:
+        if items.get("thresholding"):
+            raise NotImplementedError("thresholding=True is not supported by the engine's %s" % name)
+        if items.get("trained_betas") is not None:
+            raise NotImplementedError("trained_betas is not supported by the engine's %s" % name)
+    accepted = _init_params(cls)
+    return cls(**{k: v for k, v in items.items() if k in accepted})
+
+
+def _init_params(cls):
+    """the named constructor parameters of `cls` and its bases"""
+    import inspect
+    names = set()
+    for c in cls.__mro__:
+        if "__init__" in vars(c) and c is not object:
+            names |= {p.name for p in inspect.signature(c.__init__).parameters.values()
+                      if p.kind not in (p.VAR_KEYWORD, p.VAR_POSITIONAL)}
+    return names - {"self"}
