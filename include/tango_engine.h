@@ -163,6 +163,20 @@ typedef struct tango_denoise_args {
   const uint8_t* prompt_mask_host;
   /* floats per row of `coef`: 0 means 8 (DDPM / DDIM); 16 for TANGO_RULE_DPM_MULTISTEP */
   int32_t coef_width;
+  /* masked-latent inpainting (audioldm/ldm.py:724-818 generate_sample_masked, audioldm/latent_diffusion/ddim.py:210-217), any rule:
+   * before the UNet call of every loop index i (i = 0 included, on the initial latents; none after the last step)
+   *   x = (sqrt(abar_i) * x0 + sqrt(1 - abar_i) * n_i) * m + (1 - m) * x
+   * i.e. the fork's add_noise (scheduling_ddpm.py:351-371) of the known latents x0 at t_i, kept where m = 1.
+   * known_latents: device [B, C_lat, H, W] fp32 (scale_factor * posterior sample); NULL = no masking (the fields below unused).
+   * latent_mask:   device [B, 1, H, W] fp32 (broadcast over channels; 1 keeps the known audio, 0 regenerates it).
+   * blend_coef:    HOST [N][2] = sqrt(abar_t_i), sqrt(1 - abar_t_i) (tango_amd/scheduler.py blend_table()).
+   * blend_noise:   device [N][B, C_lat, H, W] fp32 n_i, or NULL -> device Philox on the step noise's key and counter layout with bit
+   *                31 of the step word set (tango_op_philox_normal_blend), a stream disjoint from the step noise.  Allowed with every
+   *                rule: it is not step noise. */
+  const float* known_latents;
+  const float* latent_mask;
+  const float* blend_coef;
+  const float* blend_noise;
 } tango_denoise_args_t;
 
 const char* tango_last_error(void);
@@ -312,6 +326,21 @@ int tango_op_sched_multistep(float* latents, const float* model_out_nchw, float*
  * [sample_offset, sample_offset + B): out fp32 [B, C, HW] (replaces randn_tensor inside DDPMScheduler.step,
  * mustango/diffusers/src/diffusers/schedulers/scheduling_ddpm.py:331-338, for throughput runs) */
 int tango_op_philox_normal(float* out, int B, int C, int HW, int step, uint64_t seed, int sample_offset, void* stream);
+
+/* loop index `step` of a masked (inpainting) loop on caller-owned buffers, fp32: at step 0 the pre-loop blend of latents with the
+ * known latents first, then the fused CFG + update of `rule` (TANGO_RULE_*), then -- when step + 1 < num_steps -- the blend for loop
+ * index step + 1 (tango_denoise_args_t.known_latents).  latents [B, C, HW] in/out, model_out_nchw [B2, C, HW], noise DEVICE
+ * [num_steps][B, C, HW] step noise or NULL (Philox; must be NULL for the multistep rule), ring DEVICE [3][B][C][HW] (multistep rule,
+ * as tango_op_sched_multistep; else may be NULL), coef HOST [num_steps][coef_width] (8 or 16), known / mask DEVICE [B, C, HW] /
+ * [B, HW], blend_coef HOST [num_steps][2], blend_noise DEVICE [num_steps][B, C, HW] or NULL (Philox).  Synchronises. */
+int tango_op_sched_masked(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
+                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
+                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
+                          int pred_type, int rule, void* stream);
+
+/* the N(0,1) values the masked loop's device Philox generator uses as the blend noise n_step of loop index `step` (the step noise's
+ * counter with bit 31 of the step word set): out fp32 [B, C, HW] */
+int tango_op_philox_normal_blend(float* out, int B, int C, int HW, int step, uint64_t seed, int sample_offset, void* stream);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,10 @@ class DenoiseArgs(C.Structure):
         ("chord_len", C.c_int32),
         ("prompt_mask_host", C.c_void_p),
         ("coef_width", C.c_int32),
+        ("known_latents", C.c_void_p),
+        ("latent_mask", C.c_void_p),
+        ("blend_coef", C.c_void_p),
+        ("blend_noise", C.c_void_p),
     ]
 
 
@@ -108,6 +112,7 @@ SYMBOLS = [
     "tango_engine_last_denoise_ms", "tango_engine_last_step_gflop", "tango_engine_profile_unet", "tango_engine_profile_vae", "tango_engine_profile_vocoder", "tango_engine_set_plan_budget", "tango_engine_plan_stats", "tango_engine_drop_plans", "tango_op_conv2d", "tango_op_linear", "tango_op_linear_ln", "tango_op_ff_fused", "tango_op_qkv_stat", "tango_op_linear_qkv", "tango_op_linear_qkv_perm", "tango_op_conv1d",
     "tango_op_conv_transpose1d", "tango_op_groupnorm", "tango_op_layernorm", "tango_op_attention", "tango_op_attention_ex", "tango_op_xattn_block",
     "tango_op_sched_step", "tango_op_sched_multistep", "tango_op_philox_normal",
+    "tango_op_sched_masked", "tango_op_philox_normal_blend",
 ]
 
 _lib = None
@@ -172,6 +177,8 @@ def load():
     lib.tango_op_sched_step.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, ci, ci, cf, vp]
     lib.tango_op_sched_multistep.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp]
     lib.tango_op_philox_normal.argtypes = [vp, ci, ci, ci, ci, C.c_uint64, ci, vp]
+    lib.tango_op_philox_normal_blend.argtypes = [vp, ci, ci, ci, ci, C.c_uint64, ci, vp]
+    lib.tango_op_sched_masked.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, C.c_uint64, ci, ci, ci, ci, ci, cf, ci, ci, vp]
     _lib = lib
     return lib
 

@@ -388,13 +388,24 @@ struct SchedParams {
   float* ring;
   int coef_w;
   int algo;              // 0 DPM-Solver++ (x0 form), 1 DPM-Solver (eps form)
+  // masked (inpainting) kernels only (include/tango_engine.h tango_denoise_args_t.known_latents): after the update of loop index i,
+  // when i + 1 < num_steps, x = (bc[i+1][0] * x0 + bc[i+1][1] * n_{i+1}) * m + (1 - m) * x
+  const float* x0;          // [B][C][HW] known latents
+  const float* mask;        // [B][HW]
+  const float* blend_coef;  // [steps][2] device: sqrt(abar_t), sqrt(1 - abar_t)
+  const float* blend_noise; // [steps][B*C*HW] or null -> philox, step word | 0x80000000
+  int num_steps;
 };
 // `dev_params` is a DEVICE copy of SchedParams; the grid covers max_positions >= B*HW (one thread per latent position).
-// `rule` (host copy of the block's rule) picks the kernel: 0 / 1 sched_step_kernel, 2 sched_multistep_kernel
-int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule = 0);
+// `rule` (host copy of the block's rule) picks the kernel: 0 / 1 sched_step_kernel, 2 sched_multistep_kernel; `masked` their
+// inpainting variants (the blend for the next loop index fused after the update)
+int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule = 0, bool masked = false);
+// the blend of loop index 0 (before the first UNet call): lat and both CFG halves of xin, from the block's step-0 entries
+int launch_inpaint_blend0(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s);
 int launch_step_inc(int* step_ptr, hipStream_t s);
-// test hook: the N(0,1) draws of sched_step at loop index `step` -> out fp32 [B][C][HW]
-int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned long long seed, int sample_offset, hipStream_t s);
+// test hook: the N(0,1) draws of sched_step at loop index `step` -> out fp32 [B][C][HW] (`blend`: the masked loop's blend noise)
+int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned long long seed, int sample_offset, hipStream_t s,
+                         bool blend = false);
 
 // latents fp32 NCHW [B,C,HW] -> T NHWC [rep*B, HW, ld] (replicated `rep` times along batch), zero-pads C..ld? no: writes C channels
 int launch_nchw_to_nhwc(int dtype, const float* src, void* dst, int64_t ld, int B, int C, int HW, int rep, float scale, hipStream_t s);

@@ -44,10 +44,35 @@ __device__ __forceinline__ void philox_normal4(int hw, int c4, int sample, int s
   box_muller(r[2], r[3], n[2], n[3]);
 }
 
+// Masked-latent inpainting (audioldm/latent_diffusion/ddim.py:210-217): x = q * m + (1 - m) * x with q the fork's add_noise of the known
+// latents, q = sqrt(abar_t) * x0 + sqrt(1 - abar_t) * n (scheduling_ddpm.py:351-371), both in the fork's unfused multiply / add order
+__device__ __forceinline__ float inpaint_blend(float x, float x0, float n, float sa, float sb, float m) {
+#pragma clang fp contract(off)
+  const float t0 = sa * x0; const float t1 = sb * n; const float q = t0 + t1;
+  const float u0 = q * m; const float om = 1.0f - m; const float u1 = om * x;
+  return u0 + u1;
+}
+// the blend noise of loop index `step`: the step noise's Philox counter with bit 31 of the step word set (disjoint stream, same key)
+__host__ __device__ __forceinline__ int blend_step_word(int step) { return (int)((unsigned)step | 0x80000000u); }
+
+// blend of loop index `step` for channel c of (b, hw): injected noise or the Philox draw cached per 4 channels in nb
+__device__ __forceinline__ float blend_at(const SchedParams& p, int step, int b, int hw, int c, int64_t o, float x, float m,
+                                          float (&nb)[4]) {
+  float n;
+  if (p.blend_noise) {
+    n = p.blend_noise[(int64_t)step * p.B * p.C * p.HW + o];
+  } else {
+    if ((c & 3) == 0) philox_normal4(hw, c >> 2, p.sample_offset + b, blend_step_word(step), p.seed, nb);
+    n = nb[c & 3];
+  }
+  return inpaint_blend(x, p.x0[o], n, p.blend_coef[2 * step], p.blend_coef[2 * step + 1], m);
+}
+
 // The parameter block is read from DEVICE memory (wave-uniform scalar loads): the launch itself then carries only one
 // pointer, so the captured hipGraph of a denoise step stays valid when the caller's latents / noise pointers, guidance
 // or prediction type change between calls (engine.hip refreshes the block with one hipMemcpyAsync per call).
-template <typename T>
+// MASK: the inpainting variant -- after the update, the blend of loop index step + 1 (none after the last step)
+template <typename T, bool MASK = false>
 __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __restrict__ pp) {
   // plain operators + contract(off): the HIP _rn intrinsics are inlined header operators that still fuse
 #pragma clang fp contract(off)
@@ -64,6 +89,9 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __re
   T* xo0 = (T*)p.xin + ((int64_t)b * p.HW + hw) * p.xin_ld;
   T* xo1 = p.cfg ? (T*)p.xin + ((int64_t)(p.B + b) * p.HW + hw) * p.xin_ld : nullptr;
   float nrm[4] = {0.f, 0.f, 0.f, 0.f};
+  float nb[4] = {0.f, 0.f, 0.f, 0.f};
+  const bool blend = MASK && step + 1 < p.num_steps;
+  const float m = MASK ? p.mask[(int64_t)b * p.HW + hw] : 0.f;
   for (int c = 0; c < C; ++c) {
     float* lp = p.lat + ((int64_t)b * C + c) * p.HW + hw;
     const float x = *lp;
@@ -95,6 +123,9 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __re
       { const float m0 = sap * x0; const float m1 = dirc * e; prev = m0 + m1; }
       if (sig > 0.f) { const float m2 = sig * nz; prev = prev + m2; }
     }
+    if constexpr (MASK) {
+      if (blend) prev = blend_at(p, step + 1, b, hw, c, ((int64_t)b * C + c) * p.HW + hw, prev, m, nb);
+    }
     *lp = prev;
     const T tv = from_f<T>(prev);
     xo0[c] = tv;
@@ -116,8 +147,10 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ 
     out[((int64_t)b * C + c) * HW + hw] = nrm[c & 3];
   }
 }
-int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned long long seed, int sample_offset, hipStream_t s) {
-  hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)((B * HW + 255) / 256)), dim3(256), 0, s, out, B, C, HW, step, seed, sample_offset);
+int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned long long seed, int sample_offset, hipStream_t s,
+                         bool blend) {
+  hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)((B * HW + 255) / 256)), dim3(256), 0, s, out, B, C, HW,
+                     blend ? blend_step_word(step) : step, seed, sample_offset);
   TANGO_HIP(hipGetLastError());
   return 0;
 }
@@ -132,7 +165,8 @@ int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned lo
 // The converted output m0 of this step goes to ring slot step % 3; m1 / m2 (steps - 1, - 2) are read from the other two slots
 // only when the row's order asks for them, i.e. only once an earlier step of the same loop has written them.  No noise term.
 // ------------------------------------------------------------------------------------------
-template <typename T>
+// MASK: the inpainting variant, as sched_step_kernel's (the blended sample is the next step's `sample`)
+template <typename T, bool MASK = false>
 __global__ __launch_bounds__(256) void sched_multistep_kernel(const SchedParams* __restrict__ pp) {
 #pragma clang fp contract(off)
   const SchedParams p = *pp;
@@ -153,6 +187,9 @@ __global__ __launch_bounds__(256) void sched_multistep_kernel(const SchedParams*
   const float* ec = p.cfg ? p.eps + ((int64_t)(p.B + b) * p.HW + hw) * C : nullptr;
   T* xo0 = (T*)p.xin + ((int64_t)b * p.HW + hw) * p.xin_ld;
   T* xo1 = p.cfg ? (T*)p.xin + ((int64_t)(p.B + b) * p.HW + hw) * p.xin_ld : nullptr;
+  float nb[4] = {0.f, 0.f, 0.f, 0.f};
+  const bool blend = MASK && step + 1 < p.num_steps;
+  const float m = MASK ? p.mask[(int64_t)b * p.HW + hw] : 0.f;
   for (int c = 0; c < C; ++c) {
     const int64_t o = ((int64_t)b * C + c) * p.HW + hw;
     const float x = p.lat[o];
@@ -185,6 +222,9 @@ __global__ __launch_bounds__(256) void sched_multistep_kernel(const SchedParams*
       const float t5 = c2 * D2; prev = prev + t5;
     }
     r0[o] = m0;
+    if constexpr (MASK) {
+      if (blend) prev = blend_at(p, step + 1, b, hw, c, o, prev, m, nb);
+    }
     p.lat[o] = prev;
     const T tv = from_f<T>(prev);
     xo0[c] = tv;
@@ -192,8 +232,61 @@ __global__ __launch_bounds__(256) void sched_multistep_kernel(const SchedParams*
   }
 }
 
-int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule) {
+// the blend of loop index 0, before the first UNet call (the engine launches it once per call, outside the captured step)
+template <typename T>
+__global__ __launch_bounds__(256) void inpaint_blend0_kernel(const SchedParams* __restrict__ pp) {
+  const SchedParams p = *pp;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.B * p.HW) return;
+  const int b = idx / p.HW, hw = idx - b * p.HW;
+  const int C = p.C;
+  T* xo0 = (T*)p.xin + ((int64_t)b * p.HW + hw) * p.xin_ld;
+  T* xo1 = p.cfg ? (T*)p.xin + ((int64_t)(p.B + b) * p.HW + hw) * p.xin_ld : nullptr;
+  const float m = p.mask[(int64_t)b * p.HW + hw];
+  float nb[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int c = 0; c < C; ++c) {
+    const int64_t o = ((int64_t)b * C + c) * p.HW + hw;
+    const float x = blend_at(p, 0, b, hw, c, o, p.lat[o], m, nb);
+    p.lat[o] = x;
+    const T tv = from_f<T>(x);
+    xo0[c] = tv;
+    if (xo1) xo1[c] = tv;
+  }
+}
+
+int launch_inpaint_blend0(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s) {
+  const unsigned nb = (unsigned)((max_positions + 255) / 256);
+  switch (dtype) {
+    case DT_F32: hipLaunchKernelGGL((inpaint_blend0_kernel<float>), dim3(nb), dim3(256), 0, s, dev_params); break;
+    case DT_F16: hipLaunchKernelGGL((inpaint_blend0_kernel<f16>), dim3(nb), dim3(256), 0, s, dev_params); break;
+    case DT_BF16: hipLaunchKernelGGL((inpaint_blend0_kernel<bf16>), dim3(nb), dim3(256), 0, s, dev_params); break;
+    default: TANGO_FAIL("inpaint_blend0: bad dtype");
+  }
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule, bool masked) {
   const unsigned nb = (unsigned)((max_positions + 255) / 256);   // >= B*HW of the block; surplus threads exit
+  if (masked) {
+    if (rule == 2) {
+      switch (dtype) {
+        case DT_F32: hipLaunchKernelGGL((sched_multistep_kernel<float, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
+        case DT_F16: hipLaunchKernelGGL((sched_multistep_kernel<f16, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
+        case DT_BF16: hipLaunchKernelGGL((sched_multistep_kernel<bf16, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
+        default: TANGO_FAIL("sched_multistep (masked): bad dtype");
+      }
+    } else {
+      switch (dtype) {
+        case DT_F32: hipLaunchKernelGGL((sched_step_kernel<float, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
+        case DT_F16: hipLaunchKernelGGL((sched_step_kernel<f16, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
+        case DT_BF16: hipLaunchKernelGGL((sched_step_kernel<bf16, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
+        default: TANGO_FAIL("sched_step (masked): bad dtype");
+      }
+    }
+    TANGO_HIP(hipGetLastError());
+    return 0;
+  }
   if (rule == 2) {
     switch (dtype) {
       case DT_F32: hipLaunchKernelGGL((sched_multistep_kernel<float>), dim3(nb), dim3(256), 0, s, dev_params); break;

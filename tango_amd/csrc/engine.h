@@ -149,6 +149,13 @@ struct UNetPlan {
   hipGraph_t graph_k_ms = nullptr;
   hipGraphExec_t exec_k_ms = nullptr;
   int k_steps_ms = 0;
+  // and the masked (inpainting) variants of both update kernels, [0] DDPM / DDIM, [1] multistep: the blend of the next loop index is
+  // fused into the update kernel, so an unmasked call never replays these (nor a masked call the four above)
+  hipGraph_t graph_mk[2] = {nullptr, nullptr};
+  hipGraphExec_t exec_mk[2] = {nullptr, nullptr};
+  hipGraph_t graph_k_mk[2] = {nullptr, nullptr};
+  hipGraphExec_t exec_k_mk[2] = {nullptr, nullptr};
+  int k_steps_mk[2] = {0, 0};
   // Two independent chains (round 5; Engine::denoise): a "dual" plan owns only the UNet input / output buffers of the whole batch; its
   // two children run the first and the second half of the samples (no op of the UNet crosses samples) as two branches of the captured
   // graph, so that one branch's dispatch gaps and kernel tails are filled by the other's kernels.  A child takes xin / eps from its
@@ -311,6 +318,7 @@ class Engine {
   SchedParams* d_sched = nullptr;   // device copy of the current call's scheduler parameter block
   int64_t* d_ts = nullptr;       // [max_steps]
   float* d_coef = nullptr;       // [max_steps][16] (DDPM / DDIM rows use the first 8 floats of a packed [N][8] table)
+  float* d_bcoef = nullptr;      // [max_steps][2] add_noise scalars of the masked loop's blend (tango_denoise_args_t.blend_coef)
   float* d_ring = nullptr;       // multistep history [3][ring_batch][C][HW] fp32 (hipMalloc'd, grown with the batch; not in `owned`)
   int ring_batch = 0;
   float* d_sin = nullptr;        // [max_steps][ch0]

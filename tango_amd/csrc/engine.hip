@@ -608,6 +608,11 @@ void Engine::free_unet_plan(UNetPlan& P) {
   for (hipGraphExec_t x : {P.exec_ms, P.exec_k_ms}) if (x) (void)hipGraphExecDestroy(x);
   for (hipGraph_t g : {P.graph_ms, P.graph_k_ms}) if (g) (void)hipGraphDestroy(g);
   P.exec_ms = P.exec_k_ms = nullptr; P.graph_ms = P.graph_k_ms = nullptr;
+  for (int r = 0; r < 2; ++r) {
+    for (hipGraphExec_t x : {P.exec_mk[r], P.exec_k_mk[r]}) if (x) (void)hipGraphExecDestroy(x);
+    for (hipGraph_t g : {P.graph_mk[r], P.graph_k_mk[r]}) if (g) (void)hipGraphDestroy(g);
+    P.exec_mk[r] = P.exec_k_mk[r] = nullptr; P.graph_mk[r] = P.graph_k_mk[r] = nullptr; P.k_steps_mk[r] = 0;
+  }
   for (auto& c : P.child) if (c) { free_unet_plan(*c); c.reset(); }
   release_slab(&P.slab, P.meta);
 }
@@ -1044,6 +1049,7 @@ int Engine::init() {
     d_sched = (SchedParams*)dmalloc(sizeof(SchedParams));
     d_ts = (int64_t*)dmalloc((size_t)max_steps * 8);
     d_coef = (float*)dmalloc((size_t)max_steps * 16 * 4);
+    d_bcoef = (float*)dmalloc((size_t)max_steps * 2 * 4);
     d_sin = (float*)dmalloc((size_t)max_steps * cfg.unet_channels[0] * 4);
     d_t1 = (float*)dmalloc((size_t)max_steps * temb * 4);
     d_temb = (float*)dmalloc((size_t)max_steps * temb * 4);
@@ -1504,6 +1510,10 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
       if (!(o == 1.0f || (o == 2.0f && i >= 1) || (o == 3.0f && i >= 2))) TANGO_FAIL("denoise: multistep table row with a bad order");
     }
   }
+  const bool mk = a.known_latents != nullptr;       // masked-latent inpainting
+  if (mk != (a.latent_mask != nullptr)) TANGO_FAIL("denoise: known_latents and latent_mask go together");
+  if (mk && !a.blend_coef) TANGO_FAIL("denoise: a masked call needs blend_coef [num_steps][2]");
+  if (!mk && (a.blend_coef || a.blend_noise)) TANGO_FAIL("denoise: blend_coef / blend_noise need known_latents and latent_mask");
   const bool cfg_on = a.guidance_scale > 1.0f;
   const int B = a.batch, B2 = cfg_on ? 2 * B : B;
   UNetPlan* P;
@@ -1530,10 +1540,13 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
   sp.pred_type = a.prediction_type; sp.rule = a.rule; sp.clip = a.clip_sample; sp.clip_range = a.clip_sample_range;
   sp.seed = a.seed; sp.sample_offset = a.sample_offset;
   sp.ring = ms ? d_ring : nullptr; sp.coef_w = coef_w; sp.algo = ms ? (int)a.coef[11] : 0;
+  sp.x0 = a.known_latents; sp.mask = a.latent_mask; sp.blend_coef = mk ? d_bcoef : nullptr; sp.blend_noise = mk ? a.blend_noise : nullptr;
+  sp.num_steps = a.num_steps;
   // per-call tables and the scheduler parameter block live in device memory, so the captured graph of one denoise
   // step (UNet + CFG/scheduler update + step counter) is independent of the call's pointers and scalars
   // (both sources are pageable / transient host memory: pinned staging slots, no host sync -- stage_h2d)
   TANGO_TRY(stage_h2d(d_coef, a.coef, (size_t)a.num_steps * coef_w * 4, s));
+  if (mk) TANGO_TRY(stage_h2d(d_bcoef, a.blend_coef, (size_t)a.num_steps * 2 * 4, s));
   TANGO_TRY(stage_h2d(d_sched, &sp, sizeof(SchedParams), s));
   TANGO_HIP(hipMemsetAsync(d_step, 0, 4, s));
   {
@@ -1563,6 +1576,9 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
   }
   TANGO_TRY(launch_fill_zero(P->xin, (size_t)B2 * HW * 8 * esz, s));
   TANGO_TRY(launch_nchw_to_nhwc(dt, a.latents, P->xin, 8, B, C, HW, cfg_on ? 2 : 1, 1.0f, s));
+  // the blend of loop index 0 on the initial latents (ddim.py:210-217 runs it before every UNet call, the first one included); the
+  // later ones are fused into the captured update kernel
+  if (mk) TANGO_TRY(launch_inpaint_blend0(dt, d_sched, B * HW, s));
 
   if (chains == 2 && !ev_fork) {
     TANGO_HIP(hipStreamCreateWithFlags(&cap_stream2, hipStreamNonBlocking));
@@ -1582,7 +1598,7 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
       TANGO_HIP(hipEventRecord(ej, st2));
       TANGO_HIP(hipStreamWaitEvent(st, ej, 0));
     }
-    TANGO_TRY(launch_sched_step(dt, d_sched, B2 * HW, st, a.rule));
+    TANGO_TRY(launch_sched_step(dt, d_sched, B2 * HW, st, a.rule, mk));
     return launch_step_inc(d_step, st);
   };
   // capture `n` steps once per plan; every per-step quantity is read through d_step / d_sched
@@ -1601,12 +1617,12 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
     TANGO_HIP(hipGraphInstantiate(x_out, g, nullptr, nullptr, 0));
     return 0;
   };
-  // the update kernel is fixed at capture: the multistep rule replays graphs of its own
-  hipGraph_t& graph1 = ms ? P->graph_ms : P->graph;
-  hipGraphExec_t& exec1 = ms ? P->exec_ms : P->exec;
-  hipGraph_t& graphk = ms ? P->graph_k_ms : P->graph_k;
-  hipGraphExec_t& execk = ms ? P->exec_k_ms : P->exec_k;
-  int& ksteps = ms ? P->k_steps_ms : P->k_steps;
+  // the update kernel is fixed at capture: the multistep rule and masked calls replay graphs of their own
+  hipGraph_t& graph1 = mk ? P->graph_mk[ms] : ms ? P->graph_ms : P->graph;
+  hipGraphExec_t& exec1 = mk ? P->exec_mk[ms] : ms ? P->exec_ms : P->exec;
+  hipGraph_t& graphk = mk ? P->graph_k_mk[ms] : ms ? P->graph_k_ms : P->graph_k;
+  hipGraphExec_t& execk = mk ? P->exec_k_mk[ms] : ms ? P->exec_k_ms : P->exec_k;
+  int& ksteps = mk ? P->k_steps_mk[ms] : ms ? P->k_steps_ms : P->k_steps;
   if (a.use_graph && !exec1) TANGO_TRY(capture(1, &graph1, &exec1));
   // k steps per replay (round 5; north_star: "the 100-200 denoise steps captured as a hipGraph"): the same kernel sequence captured k
   // times back to back -- every per-step quantity is read through the device-side step counter, so a k-step graph is just k copies.

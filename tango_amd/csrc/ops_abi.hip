@@ -609,6 +609,7 @@ int tango_op_sched_step(float* latents, const float* model_out_nchw, const float
   p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = 8; p.noise = noise; p.coef = dcoef; p.step_ptr = dstep;
   p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = rule; p.clip = clip;
   p.clip_range = clip_range; p.seed = 0; p.sample_offset = 0; p.ring = nullptr; p.coef_w = 8; p.algo = 0;
+  p.x0 = nullptr; p.mask = nullptr; p.blend_coef = nullptr; p.blend_noise = nullptr; p.num_steps = 1;
   SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
   if (!dp) TANGO_FAIL("op_sched_step: alloc");
   TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
@@ -638,6 +639,7 @@ int tango_op_sched_multistep(float* latents, const float* model_out_nchw, float*
   p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = C; p.noise = nullptr; p.coef = dcoef; p.step_ptr = dstep;
   p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = TANGO_RULE_DPM_MULTISTEP;
   p.clip = 0; p.clip_range = 1.0f; p.seed = 0; p.sample_offset = 0; p.ring = ring; p.coef_w = 16; p.algo = algo;
+  p.x0 = nullptr; p.mask = nullptr; p.blend_coef = nullptr; p.blend_noise = nullptr; p.num_steps = step + 1;
   SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
   if (!dp) TANGO_FAIL("op_sched_multistep: alloc");
   TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
@@ -649,6 +651,57 @@ int tango_op_sched_multistep(float* latents, const float* model_out_nchw, float*
 int tango_op_philox_normal(float* out, int B, int C, int HW, int step, uint64_t seed, int sample_offset, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   TANGO_TRY(launch_philox_normal(out, B, C, HW, step, seed, sample_offset, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_philox_normal_blend(float* out, int B, int C, int HW, int step, uint64_t seed, int sample_offset, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TANGO_TRY(launch_philox_normal(out, B, C, HW, step, seed, sample_offset, s, true));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_sched_masked(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
+                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
+                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
+                          int pred_type, int rule, void* stream) {
+  if (B <= 0 || C <= 0 || HW <= 0 || num_steps <= 0 || step < 0 || step >= num_steps) TANGO_FAIL("op_sched_masked: bad sizes");
+  if (!known_latents || !latent_mask || !blend_coef) TANGO_FAIL("op_sched_masked: known_latents, latent_mask and blend_coef are required");
+  const bool ms = rule == TANGO_RULE_DPM_MULTISTEP;
+  if (rule != TANGO_RULE_DDPM && rule != TANGO_RULE_DDIM && !ms) TANGO_FAIL("op_sched_masked: unknown rule");
+  if (coef_width != (ms ? 16 : 8)) TANGO_FAIL("op_sched_masked: coef_width must be 16 for the multistep rule, else 8");
+  int algo = 0;
+  if (ms) {
+    if (noise || !ring) TANGO_FAIL("op_sched_masked: the multistep rule takes a ring and no step noise");
+    const int order = (int)coef[(size_t)step * 16 + 10];
+    if (order < 1 || order > 3 || order > step + 1) TANGO_FAIL("op_sched_masked: row order must be in [1, min(3, step + 1)]");
+    algo = (int)coef[11];
+    if (algo != 0 && algo != 1) TANGO_FAIL("op_sched_masked: table column 11 (algorithm) must be 0 or 1");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  Scratch sc;
+  const int B2 = cfg ? 2 * B : B;
+  float* eps = (float*)sc.get((size_t)B2 * HW * C * 4);
+  float* xin = (float*)sc.get((size_t)B2 * HW * C * 4);
+  float* dcoef = (float*)sc.get((size_t)num_steps * coef_width * 4);
+  float* dbc = (float*)sc.get((size_t)num_steps * 2 * 4);
+  int* dstep = (int*)sc.get(256);
+  SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
+  if (!eps || !xin || !dcoef || !dbc || !dstep || !dp) TANGO_FAIL("op_sched_masked: alloc");
+  TANGO_TRY(launch_nchw_to_nhwc(DT_F32, model_out_nchw, eps, C, B2, C, HW, 1, 1.0f, s));
+  TANGO_HIP(hipMemcpyAsync(dcoef, coef, (size_t)num_steps * coef_width * 4, hipMemcpyHostToDevice, s));
+  TANGO_HIP(hipMemcpyAsync(dbc, blend_coef, (size_t)num_steps * 2 * 4, hipMemcpyHostToDevice, s));
+  TANGO_HIP(hipMemcpyAsync(dstep, &step, 4, hipMemcpyHostToDevice, s));
+  SchedParams p;
+  p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = C; p.noise = noise; p.coef = dcoef; p.step_ptr = dstep;
+  p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = rule;
+  p.clip = 0; p.clip_range = 1.0f; p.seed = seed; p.sample_offset = sample_offset; p.ring = ms ? ring : nullptr; p.coef_w = coef_width;
+  p.algo = algo;
+  p.x0 = known_latents; p.mask = latent_mask; p.blend_coef = dbc; p.blend_noise = blend_noise; p.num_steps = num_steps;
+  TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
+  if (step == 0) TANGO_TRY(launch_inpaint_blend0(DT_F32, dp, B * HW, s));
+  TANGO_TRY(launch_sched_step(DT_F32, dp, B * HW, s, rule, true));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -257,11 +257,17 @@ class Engine:
 
     def denoise(self, latents, prompt_embeds, prompt_mask, timesteps, coef, guidance_scale, prediction_type="v_prediction",
                 rule="ddpm", clip_sample=False, clip_sample_range=1.0, noise=None, seed=0, sample_offset=0, use_graph=True,
-                beat_embeds=None, beat_mask=None, chord_embeds=None, chord_mask=None, prompt_mask_host=None):
+                beat_embeds=None, beat_mask=None, chord_embeds=None, chord_mask=None, prompt_mask_host=None, known_latents=None,
+                latent_mask=None, blend_coef=None, blend_noise=None):
         """In-place denoise of `latents` [B,8,256,16] (fp32 cuda).  `timesteps` int64 [N] and `coef`
         float32 [N,8] ([N,16] for rule "dpmsolver") are host tables from tango_amd.scheduler.  `prompt_mask_host`: the caller's CPU copy of a `prompt_mask`
         that already lives on the device (the tokenizer's attention mask): the engine then picks its plan from it instead of
-        reading the device mask back, i.e. the call does not synchronise the host."""
+        reading the device mask back, i.e. the call does not synchronise the host.
+
+        Masked-latent inpainting (audioldm/ldm.py:724-818, ddim.py:210-217), any rule: `known_latents` [B,8,256,16] and `latent_mask`
+        [B,1,256,16] (1 keeps the known audio, 0 regenerates it), `blend_coef` the scheduler's `blend_table()` [N,2] and optionally
+        `blend_noise` [N,B,8,256,16] (else the device Philox generator's blend stream, keyed by `seed`).  Before the UNet call of every
+        loop index i, the latents become add_noise(known, n_i, t_i) * m + (1 - m) * latents; there is no blend after the last step."""
         assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
         self._check_latents("latents", latents)
         enc = self._f32(prompt_embeds)
@@ -295,6 +301,7 @@ class Engine:
             noise = self._f32(noise)
             if tuple(noise.shape) != (len(ts),) + tuple(latents.shape):
                 raise ValueError("noise must be [num_steps, %s], got %s" % (", ".join(map(str, latents.shape)), tuple(noise.shape)))
+        masked = self._check_inpaint(latents, len(ts), known_latents, latent_mask, blend_coef, blend_noise)
         a = _lib.DenoiseArgs()
         a.latents = latents.data_ptr()
         a.prompt_embeds = enc.data_ptr()
@@ -316,6 +323,12 @@ class Engine:
         a.use_graph = 1 if use_graph else 0
         a.coef_width = width
         keep = []
+        if masked is not None:
+            kl, lm, bc, bn = masked
+            keep += [kl, lm, bc, bn]
+            a.known_latents, a.latent_mask = kl.data_ptr(), lm.data_ptr()
+            a.blend_coef = bc.ctypes.data
+            a.blend_noise = bn.data_ptr() if bn is not None else None
         if self.unet_cfg.get("music"):
             if beat_embeds is None or chord_embeds is None:
                 raise ValueError("a Music UNet needs beat_embeds and chord_embeds")
@@ -329,6 +342,38 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.tango_engine_denoise(self._h, C.byref(a), _stream_ptr()), "denoise")
         return latents
+
+    def _check_inpaint(self, latents, n, known_latents, latent_mask, blend_coef, blend_noise):
+        """host-side validation of denoise()'s masking arguments: None when the call is not masked, else the device / host copies the
+        engine reads (known, mask, blend table, blend noise)"""
+        if known_latents is None and latent_mask is None:
+            if blend_coef is not None or blend_noise is not None:
+                raise ValueError("blend_coef / blend_noise need known_latents and latent_mask")
+            return None
+        if known_latents is None or latent_mask is None:
+            raise ValueError("known_latents and latent_mask go together")
+        shape = tuple(latents.shape)
+        for what, x in (("known_latents", known_latents), ("latent_mask", latent_mask)):
+            if not torch.is_tensor(x) or not x.is_floating_point():
+                raise ValueError("%s must be a floating-point tensor" % what)
+        if tuple(known_latents.shape) != shape:
+            raise ValueError("known_latents must be %s like the latents, got %s" % (shape, tuple(known_latents.shape)))
+        mshape = (shape[0], 1) + shape[2:]
+        if tuple(latent_mask.shape) != mshape:
+            raise ValueError("latent_mask must be %s, got %s" % (mshape, tuple(latent_mask.shape)))
+        if not latent_mask.is_cuda and latent_mask.numel() and not bool(((latent_mask >= 0) & (latent_mask <= 1)).all()):
+            raise ValueError("latent_mask values must lie in [0, 1]")
+        if blend_coef is None:
+            raise ValueError("a masked call needs blend_coef, the scheduler's blend_table() [num_steps, 2]")
+        bc = np.ascontiguousarray(np.asarray(blend_coef.cpu() if torch.is_tensor(blend_coef) else blend_coef, dtype=np.float32))
+        if bc.shape != (n, 2):
+            raise ValueError("blend_coef must be [%d, 2], got %s" % (n, bc.shape))
+        bn = None
+        if blend_noise is not None:
+            bn = self._f32(blend_noise)
+            if tuple(bn.shape) != (n,) + shape:
+                raise ValueError("blend_noise must be [num_steps, %s], got %s" % (", ".join(map(str, shape)), tuple(bn.shape)))
+        return self._f32(known_latents), self._f32(latent_mask), bc, bn
 
     def profile_unet(self, batch2: int, text_len: int):
         """per-op timing of one eager UNet step: list of (label, ms, gflop)"""

@@ -216,9 +216,10 @@ class AudioDiffusion:
         return pe, pm, mask_host
 
     def _denoise(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
-                 sample_offset, mask_host=None, **extra_conditions):
+                 sample_offset, mask_host=None, known_latents=None, latent_mask=None, blend_noise=None, **extra_conditions):
         """the shared body of the loop of models.py:224-249 / mustango/models.py:563-598: seed derivation, text bucketing, scheduler
-        tables, one engine call (`extra_conditions`: the Music UNet's beat / chord streams)"""
+        tables, one engine call (`extra_conditions`: the Music UNet's beat / chord streams; `known_latents` / `latent_mask` /
+        `blend_noise`: the masked loop of audioldm/ldm.py:724-818, Engine.denoise)"""
         cfg_on = guidance_scale > 1.0
         B = prompt_embeds.shape[0] // 2 if cfg_on else prompt_embeds.shape[0]
         if not hasattr(inference_scheduler, "coef_table"):
@@ -239,10 +240,17 @@ class AudioDiffusion:
             # Philox key from that generator, so torch.manual_seed() fixes the whole trajectory and calls differ
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.seed is None else (int(self.seed) << 20) + self._calls
         self._calls += 1
+        masking = {}
+        if known_latents is not None or latent_mask is not None:
+            masking = dict(known_latents=known_latents, latent_mask=latent_mask, blend_coef=inference_scheduler.blend_table(),
+                           blend_noise=blend_noise)
+        elif blend_noise is not None:
+            raise ValueError("blend_noise needs known_latents and latent_mask")
         self.engine.denoise(latents, pe, pm, timesteps.cpu().numpy(), inference_scheduler.coef_table(), guidance_scale,
                             prediction_type=c.prediction_type, rule=inference_scheduler.rule, clip_sample=c.clip_sample,
                             clip_sample_range=getattr(c, "clip_sample_range", 1.0), noise=noise, seed=seed,
-                            sample_offset=sample_offset, use_graph=self.use_graph, prompt_mask_host=mask_host, **extra_conditions)
+                            sample_offset=sample_offset, use_graph=self.use_graph, prompt_mask_host=mask_host, **masking,
+                            **extra_conditions)
         return latents
 
     @torch.no_grad()
@@ -266,6 +274,39 @@ class AudioDiffusion:
             pm = pm.repeat_interleave(num_samples_per_prompt, 0)
         return self.inference_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, mask_host=host)
 
+    # ---- masked-latent inpainting (audioldm/pipeline.py:249-301, ldm.py:724-818, ddim.py:207-233) ------------------------------
+    @torch.no_grad()
+    def inpaint_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
+                                known_latents, latent_mask, latents=None, noise=None, blend_noise=None, seed=None, sample_offset=0,
+                                mask_host=None):
+        """The loop of inference_from_embeddings with the region where `latent_mask` [B, 1, 256, 16] is 1 held to the known latents
+        `known_latents` [B, 8, 256, 16] (scale_factor * posterior sample of the encoded mel): before every UNet call the latents
+        become inference_scheduler.add_noise(known, n_i, t_i) * m + (1 - m) * latents (ddim.py:210-217), none after the last step.
+        `blend_noise` [N, B, 8, 256, 16] injects the n_i; by default they come from the engine's Philox generator under `seed`."""
+        return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
+                             sample_offset, mask_host=mask_host, known_latents=known_latents, latent_mask=latent_mask,
+                             blend_noise=blend_noise)
+
+    @torch.no_grad()
+    def inpaint(self, prompt, known_latents, latent_mask, inference_scheduler, num_steps=20, guidance_scale=3, num_samples_per_prompt=1):
+        """inference() with masking: `known_latents` [K, 8, 256, 16] and `latent_mask` [K, 1, 256, 16] for the K prompts; with
+        num_samples_per_prompt = S > 1, row k * S + j of the result pairs with clip k (the repeat_interleave order of the text
+        embeddings, not ldm.py:791's candidate-major cat).  Returns latents [K * S, 8, 256, 16]."""
+        S = num_samples_per_prompt
+        if known_latents.shape[0] != len(prompt) or latent_mask.shape[0] != len(prompt):
+            raise ValueError("known_latents and latent_mask need one row per prompt (%d), got %d and %d"
+                             % (len(prompt), known_latents.shape[0], latent_mask.shape[0]))
+        host = None
+        if guidance_scale > 1.0:
+            pe, pm, host = self._encode_text_classifier_free(prompt, S)
+        else:
+            pe, pm = self.encode_text(prompt)
+            pe = pe.repeat_interleave(S, 0)
+            pm = pm.repeat_interleave(S, 0)
+        return self.inpaint_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale,
+                                            known_latents=known_latents.repeat_interleave(S, 0),
+                                            latent_mask=latent_mask.repeat_interleave(S, 0), mask_host=host)
+
 
 class MusicAudioDiffusion(AudioDiffusion):
     """Inference side of Mustango's `MusicAudioDiffusion` (mustango/models.py:312-740) on the engine: the UNet is
@@ -287,13 +328,28 @@ class MusicAudioDiffusion(AudioDiffusion):
     @torch.no_grad()
     def inference_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3,
                                   latents=None, noise=None, seed=None, sample_offset=0, *, encoded_beats=None, beat_mask=None,
-                                  encoded_chords=None, chord_mask=None):
-        """mustango/models.py:540-598 given the three encoder outputs ([uncond; cond] when guidance > 1)."""
+                                  encoded_chords=None, chord_mask=None, known_latents=None, latent_mask=None, blend_noise=None):
+        """mustango/models.py:540-598 given the three encoder outputs ([uncond; cond] when guidance > 1); with `known_latents` /
+        `latent_mask` (/ `blend_noise`) the masked loop of AudioDiffusion.inpaint_from_embeddings."""
         if encoded_beats is None or encoded_chords is None:
             raise ValueError("encoded_beats and encoded_chords are required (mustango/models.py:548-550)")
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
-                             sample_offset, beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords,
-                             chord_mask=chord_mask)
+                             sample_offset, known_latents=known_latents, latent_mask=latent_mask, blend_noise=blend_noise,
+                             beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
+
+    @torch.no_grad()
+    def inpaint_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
+                                known_latents, latent_mask, latents=None, noise=None, blend_noise=None, seed=None, sample_offset=0,
+                                encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None):
+        """AudioDiffusion.inpaint_from_embeddings with the beat / chord streams of inference_from_embeddings"""
+        return self.inference_from_embeddings(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale,
+                                              latents, noise, seed, sample_offset, encoded_beats=encoded_beats, beat_mask=beat_mask,
+                                              encoded_chords=encoded_chords, chord_mask=chord_mask, known_latents=known_latents,
+                                              latent_mask=latent_mask, blend_noise=blend_noise)
+
+    def inpaint(self, *a, **k):
+        raise NotImplementedError("strings / beat and chord annotations are encoded by the caller's Mustango front-end modules; "
+                                  "pass their outputs to inpaint_from_embeddings()")
 
     def inference(self, *a, **k):
         raise NotImplementedError("strings / beat and chord annotations are encoded by the caller's Mustango front-end modules; "

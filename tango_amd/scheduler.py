@@ -26,7 +26,33 @@ class _StepOutput:
         self.prev_sample = prev_sample
 
 
-class _SchedulerBase:
+class _AddNoise:
+    """`add_noise` and the per-step table of its scalars, shared by every scheduler here: the fork's add_noise is one function in
+    scheduling_ddpm.py:351-371, scheduling_ddim.py:361-381 and scheduling_dpmsolver_multistep.py:510-530"""
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """sqrt(abar_t) * original_samples + sqrt(1 - abar_t) * noise per batch row, in the sample's dtype and device"""
+        ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
+        timesteps = torch.as_tensor(timesteps).to(original_samples.device)
+        sa = (ac[timesteps] ** 0.5).flatten()
+        while len(sa.shape) < len(original_samples.shape):
+            sa = sa.unsqueeze(-1)
+        sb = ((1 - ac[timesteps]) ** 0.5).flatten()
+        while len(sb.shape) < len(original_samples.shape):
+            sb = sb.unsqueeze(-1)
+        return sa * original_samples + sb * noise
+
+    def blend_table(self) -> np.ndarray:
+        """[N, 2] fp32: add_noise's scalars sqrt(abar_t), sqrt(1 - abar_t) at every set timestep (the masked loop's blend,
+        include/tango_engine.h tango_denoise_args_t.blend_coef)"""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() before blend_table()")
+        t = torch.as_tensor(self.timesteps).to(torch.int64)
+        ac = self.alphas_cumprod.to(torch.float32)
+        return torch.stack([ac[t] ** 0.5, (1 - ac[t]) ** 0.5], 1).numpy().astype(np.float32)
+
+
+class _SchedulerBase(_AddNoise):
     order = 1
     rule = "ddpm"
 
@@ -166,7 +192,7 @@ def _glide_cosine_betas(num_train_timesteps, max_beta=0.999):
     return torch.tensor([min(1 - abar((i + 1) / T) / abar(i / T), max_beta) for i in range(T)], dtype=torch.float32)
 
 
-class DPMSolverMultistepScheduler:
+class DPMSolverMultistepScheduler(_AddNoise):
     """Multistep DPM-Solver / DPM-Solver++ (Lu et al. 2022, arXiv 2206.00927 and 2211.01095), with the constructor, defaults and
     step semantics of the fork's scheduling_dpmsolver_multistep.py:124-495: 20-25 UNet calls instead of DDPM's 100-200.
 

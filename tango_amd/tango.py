@@ -9,17 +9,20 @@ import os
 import torch
 
 from .autoencoder import AutoencoderKL
+from .inpaint import TARGET_FRAMES, latent_mask, prepare_waveform
 from .models import AudioDiffusion
 from .scheduler import SD21_SCHEDULER_CONFIG, DDPMScheduler
+from .stft import wav_to_fbank
 
 _CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")
 
 
 class Tango:
     def __init__(self, name="declare-lab/tango", device="cuda:0", dtype="fp16", scheduler_config=None, text_encoder=None,
-                 tokenizer=None):
+                 tokenizer=None, with_encoder=False):
         """`text_encoder` / `tokenizer` (optional): already-built T5EncoderModel / tokenizer, e.g. from a local directory
-        on a box without hub access; the checkpoint's `text_encoder.*` tensors are loaded into it like the reference does."""
+        on a box without hub access; the checkpoint's `text_encoder.*` tensors are loaded into it like the reference does.
+        `with_encoder`: also build the mel-VAE encoder (the checkpoint holds its weights), which `inpaint` needs."""
         if os.path.isdir(name):
             path = name
         else:
@@ -27,7 +30,7 @@ class Tango:
             path = snapshot_download(repo_id=name)
         vae_config = json.load(open("{}/vae_config.json".format(path)))
         main_config = json.load(open("{}/main_config.json".format(path)))
-        self.vae = AutoencoderKL(**vae_config, dtype=dtype, device=device)
+        self.vae = AutoencoderKL(**vae_config, dtype=dtype, device=device, with_encoder=with_encoder)
         # tango.py:17-27: the wave -> mel front-end and its buffers (generation never calls it; training / evaluation callers
         # reach it as `tango.stft`, inference.py:81).  Snapshots without the two files simply have no `stft`.
         self.stft = None
@@ -54,10 +57,10 @@ class Tango:
         self.scheduler = DDPMScheduler.from_config(_ddpm_keys(scheduler_config or SD21_SCHEDULER_CONFIG))
 
     @classmethod
-    def from_components(cls, model: AudioDiffusion, vae: AutoencoderKL, scheduler=None):
+    def from_components(cls, model: AudioDiffusion, vae: AutoencoderKL, scheduler=None, stft=None):
         """Assemble from already-built components (synthetic-weight benchmarks, tests)."""
         self = cls.__new__(cls)
-        self.model, self.vae, self.stft = model, vae, None
+        self.model, self.vae, self.stft = model, vae, stft
         self.scheduler = scheduler or DDPMScheduler.from_config(_ddpm_keys(SD21_SCHEDULER_CONFIG))
         return self
 
@@ -124,6 +127,44 @@ class Tango:
             latents = self.model.inference_from_embeddings(prompt_embeds, boolean_prompt_mask, self.scheduler, steps, guidance, **kw)
             mel = self.vae.decode_first_stage(latents)
             return self.vae.decode_to_waveform(mel)
+
+    # ---- masked-latent inpainting (audioldm/pipeline.py:249-301 super_resolution_and_inpainting) ------------------------------
+    def inpaint(self, prompt, audio, time_range=(0.10, 0.15), freq_range=(1.0, 1.0), steps=100, guidance=3, samples=1):
+        """Regenerate the time span `time_range` and the mel band `freq_range` (fractions of the clip, ldm.py:773-777) of one 16 kHz
+        clip `audio` (1-D; reading and resampling are the caller's) under the text `prompt`; the rest keeps the clip's audio.
+        Returns np.int16 [samples, 163872]."""
+        with torch.no_grad():
+            known = self.encode_audio(audio)
+            mask = latent_mask(1, time_range, freq_range, known.shape[2], known.shape[3])
+            latents = self.model.inpaint([prompt], known, mask, self.scheduler, steps, guidance, samples)
+            mel = self.vae.decode_first_stage(latents)
+            return self.vae.decode_to_waveform(mel)
+
+    def inpaint_from_embeddings(self, prompt_embeds, boolean_prompt_mask, audio, time_range=(0.10, 0.15), freq_range=(1.0, 1.0),
+                                steps=100, guidance=3, samples=1, **kw):
+        """`inpaint` given the text-encoder outputs for the `samples` rows ([uncond; cond] when guidance > 1, like
+        generate_from_embeddings); `kw` goes to AudioDiffusion.inpaint_from_embeddings (latents, noise, blend_noise, seed, ...)."""
+        with torch.no_grad():
+            known = self.encode_audio(audio)
+            rows = prompt_embeds.shape[0] // 2 if guidance > 1.0 else prompt_embeds.shape[0]
+            if rows != samples:
+                raise ValueError("prompt_embeds hold %d rows, `samples` is %d" % (rows, samples))
+            mask = latent_mask(samples, time_range, freq_range, known.shape[2], known.shape[3])
+            latents = self.model.inpaint_from_embeddings(prompt_embeds, boolean_prompt_mask, self.scheduler, steps, guidance,
+                                                         known_latents=known.repeat_interleave(samples, 0), latent_mask=mask, **kw)
+            mel = self.vae.decode_first_stage(latents)
+            return self.vae.decode_to_waveform(mel)
+
+    def encode_audio(self, audio):
+        """one 1-D 16 kHz clip -> known latents [1, 8, 256, 16]: prepare_waveform -> wav_to_fbank -> encode_first_stage ->
+        get_first_stage_encoding (one posterior sample from torch's global generator, ldm.py:180-181)"""
+        if self.stft is None or not getattr(self.vae, "with_encoder", False):
+            raise RuntimeError("inpainting needs the mel front-end and the VAE encoder: build Tango(..., with_encoder=True) from a "
+                               "snapshot with stft_config.json / pytorch_model_stft.bin, or pass stft= and an AutoencoderKL(with_encoder=True) "
+                               "to from_components")
+        wav = prepare_waveform(audio)[None].to(self.model.device)
+        fbank, _, _ = wav_to_fbank(wav, TARGET_FRAMES, fn_STFT=self.stft)
+        return self.vae.get_first_stage_encoding(self.vae.encode_first_stage(fbank.unsqueeze(1)))
 
 
 def dp_initial_latents(seed, offset, count, channels=8, height=256, width=16):
