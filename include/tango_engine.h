@@ -268,6 +268,13 @@ const char* tango_debug_linear_route(int dtype, int M, int N, int K, int geglu, 
 /* ---- per-operator entry points (parity tests; fp32 reference-layout tensors on device) ---- */
 int tango_op_conv2d(int dtype, const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W,
                     int Cout, int stride, int upsample, void* stream);
+/* nearest x2 upsampling + 3x3 / pad 1 conv of a 16-bit engine (x [B][Cin][H][W] -> out [B][Cout][2H][2W]); bias2 [Cout] (may be null) is
+ * added like the per-step bias of the UNet.  phases = 1: as four 2x2-tap phase convolutions on the source grid (an error where that form
+ * does not take the problem), 0: the nine-tap gather form.  tango_op_conv2d(..., upsample = 1) picks as the engine does. */
+int tango_op_conv2d_ups(int dtype, const float* x, const float* w, const float* bias, const float* bias2, float* out, int B, int Cin,
+                        int H, int W, int Cout, int phases, void* stream);
+/* the summed phase weights of such a conv: w fp32 OIHW [Cout][Cin][3][3] -> out, 16-bit engine dtype, [4 phases][Cout][2x2 taps][Cin] */
+int tango_op_pack_ups_phase(int dtype, const float* w, void* out, int Cout, int Cin, void* stream);
 int tango_op_linear(int dtype, const float* x, const float* w, const float* bias, const float* residual, float* out, int M,
                     int N, int K, int a_act, int e_act, int geglu, void* stream);
 int tango_op_linear_ln(int dtype, const float* x, const float* w, const float* bias, const float* gamma, const float* beta,

@@ -160,6 +160,8 @@ enum Epi : int { EPI_NONE = 0, EPI_GEGLU = 1, EPI_I16 = 2, EPI_VT = 3 };
 struct GemmParams {
   const void* A = nullptr;   // T
   const void* W = nullptr;   // T  [N][Kp], K contiguous
+  const void* Wph = nullptr; // T  [4 phases][N][4 Cin]: summed 2x2-tap phase weights of a nearest-x2 upsampler conv (launch_pack_ups_phase);
+                             //    set = the conv runs as four phase convolutions on the source grid (conv_wide.hip PH; conv_ups_phase_ok)
   const float* bias = nullptr;      // [N] (or [M-rows] when bias_rows)
   const float* bias2 = nullptr;     // [bias2_stride * steps][N]: per-step bias (time embedding)
   const int* step_ptr = nullptr;    // device step counter used to index bias2
@@ -240,6 +242,13 @@ inline bool gemm_ln_fold_ok(int dtype, const GemmParams& p);
 bool conv_wide_ok(int dtype, const GemmParams& p);   // 3x3 halo-reuse conv on the 256 x 320 tile (conv_wide.hip)
 int launch_conv_wide(int dtype, const GemmParams& p, const unsigned char* zero_page, hipStream_t s);
 int conv_wide_pick_splitk(int dtype, const GemmParams& p);
+// the upsampler conv p (ups = 1, W = nine-tap weights; Wph is not looked at) can run as four 2x2-tap phase convolutions: the wide
+// conv takes it unsplit AND takes the stride-1 problem at the source resolution (TANGO_UPS_PHASES=0: never)
+bool conv_ups_phase_ok(int dtype, const GemmParams& p);
+// OIHW fp32 [O][I][3][3] -> T [4 phases][O][2x2 taps][I]: phase (py, px), tap (ty, tx) sums the original taps ky in rows(py, ty),
+// kx in rows(px, tx) with rows(0, 0) = {0}, rows(0, 1) = {1, 2}, rows(1, 0) = {0, 1}, rows(1, 1) = {2}; fp32 adds in ascending
+// (ky, kx) order, ONE rounding to T
+int launch_pack_ups_phase(int dtype, const float* src, void* dst, int O, int I, hipStream_t s);
 int launch_splitk_reduce(int dtype, const GemmParams& p, hipStream_t s);   // gemm.hip: sums ws [splits][M][N] and applies the epilogue
 bool gemm_dma_ok(int dtype, const GemmParams& p);
 int launch_gemm_dma(int dtype, const GemmParams& p, const unsigned char* zero_page, hipStream_t s);

@@ -48,7 +48,16 @@ static constexpr int CW_NA_TALL = 7;       // 8 waves x 7 x 16 rows >= 800
 // nearly free (staged once per chunk for nine items), so what an item streams through the DMA engine is its weight rows: 160
 // instead of 320 per item for the same 320 MFMAs per wave pair, and a halo of 512 pixels has fewer border pixels per output pixel --
 // 14.3 instead of 22.3 KiB of LDS-DMA per item at level 0.  Same MFMA order per accumulator, same epilogue: bit-identical results.
-template <typename T, bool RES, bool SK, int SCH, bool TALL>
+//
+// PH: the nearest x2 upsampler conv as four 2x2-tap phase convolutions over the SOURCE image.  Output pixel (2i + py, 2j + px) of the
+// upsampled grid reads source rows {i - 1, i, i} (py = 0) or {i, i, i + 1} (py = 1) and the same along x, so its nine products
+// collapse into four with summed weights (elementwise.hip ups_phase_pack_kernel: [phase][O][2x2 taps][I], Kp = 4 Cin).  The problem
+// the kernel sees is the stride-1 conv at the source resolution (p.H x p.Wd = source, p.ups = 0, p.M = source pixels); the grid
+// carries the phase in its two low bits (four consecutive workgroups = one halo tile, all on one XCD), the item loop walks four taps
+// per chunk at halo offsets (py + ty, px + tx), and the epilogue scatters row (b, i, j) to output pixel ((b 2H + 2i + py) 2W + 2j + px).
+// Halo pieces of the next chunk: taps 0, 1 issue two each (t and t + 3), tap 2 one, tap 3 none -- the read part of tap 3 is the last
+// wait in front of the next chunk's first read, and it lets only the weights of item i + 2 stay in flight.
+template <typename T, bool RES, bool SK, int SCH, bool TALL, bool PH = false>
 __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const GemmParams p, const unsigned char* zero_page, const int SR, const int nseg,
                                                            const int abytes, const int prio) {
   constexpr int BM = TALL ? 512 : 256, BN = TALL ? 160 : 320, CB = 64, NST = 4;
@@ -58,6 +67,8 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const GemmParams p, c
   constexpr int WRG = BN / 16;                  // 16-row DMA groups per weight item: 20
   constexpr int WRGW = (WRG + 7) / 8;           // per wave: 3 (waves 0-3) or 2; TALL: 2 (waves 0-1) or 1
   constexpr int TM = 4, TN = 10;
+  constexpr int NTAP = PH ? 4 : 9;              // (chunk, tap) items per channel chunk
+  static_assert(!PH || (SCH == 1 && !TALL && !SK && !RES), "phase form: the in-stream DMA schedule of the unsplit 256 x 320 tile");
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];   // [halo 0 | halo 1 | W stage 0..3]
   unsigned char* const As = dsm;
   unsigned char* const Ws = dsm + 2 * abytes;
@@ -68,6 +79,8 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const GemmParams p, c
     const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
+  const int phase = PH ? (bid & 3) : 0;         // (py, px) = (phase >> 1, phase & 1)
+  if (PH) bid >>= 2;
   const int m0 = (bid / NT) * BM, n0 = (bid % NT) * BN;
   const unsigned char* Ab = (const unsigned char*)p.A;
   const unsigned char* Wb = (const unsigned char*)p.W;
@@ -109,7 +122,7 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const GemmParams p, c
   const unsigned w_off0_init = (unsigned)(((int64_t)wrow_d * p.Kp) * (int64_t)sizeof(T) + ((slot ^ ((wrow_d >> 1) & 2)) * 16));
   aoff_lds[CW_NA * 512] = w_off0_init;
   const unsigned w_step = (unsigned)(128 * p.Kp * (int64_t)sizeof(T));
-  const unsigned char* const Wt = Wb + (int64_t)n0 * p.Kp * (int64_t)sizeof(T);
+  const unsigned char* const Wt = Wb + ((int64_t)phase * p.N + n0) * p.Kp * (int64_t)sizeof(T);
   const int my_w = wave < WRG - 8 * (WRGW - 1) ? WRGW : WRGW - 1;      // wave-uniform
 
   auto issue_a_off = [&](const int t, const int cc, const int buf, const unsigned off) {
@@ -181,7 +194,8 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const GemmParams p, c
     cc0 = (int)blockIdx.y * per;
     cc1 = cc1 < cc0 + per ? cc1 : cc0 + per;
   }
-  const int NI = (cc1 - cc0) * 9;                   // (chunk, tap) items of this workgroup
+  const int NI = (cc1 - cc0) * NTAP;                // (chunk, tap) items of this workgroup
+  const int ph_off = PH ? (phase >> 1) * HW2 + (phase & 1) : 0;
 
   const int half = wave >> 2;                       // one workgroup per CU: waves w and w + 4 share a SIMD (tools/simd_probe.hip)
   // prologue: halo of chunk 0, weight items 0..2; item 0 (and the halo) must have landed before the first read
@@ -197,27 +211,31 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const GemmParams p, c
   int st = 0, item = 0;
   int prev_h = 0;                                   // did the previous item issue a halo piece (it is younger than item i+1's weights)
   unsigned hoff = 0u;                               // source offset of the halo piece this item issues
+  unsigned hoff2 = 0u;                              // PH: of its second piece
   unsigned w_off0 = w_off0_init;                    // (one register; the rolled tap loop leaves room for it)
   asm volatile("" : "+v"(w_off0));
   for (int cc = cc0; cc < cc1; ++cc) {
     const unsigned char* Ah = As + (cc & 1) * abytes;
     const bool more_c = cc + 1 < cc1;
 #pragma unroll 1                                    // one loop body: unrolled, the nine bodies pushed the allocator over 256 VGPRs
-    for (int tap = 0; tap < 9; ++tap, ++item) {
+    for (int tap = 0; tap < NTAP; ++tap, ++item) {
       const unsigned char* Wst = Ws + st * WST;
-      const int toff = (tap / 3) * HW2 + (tap % 3);
-      // what this item issues: halo piece `tap` of chunk cc+1, weight rows of item i+3 into the stage of item i-1
-      const bool iss_h = more_c && tap < CW_NA && tap * 8 + wave < HALO_RG;
+      const int toff = PH ? ph_off + (tap >> 1) * HW2 + (tap & 1) : (tap / 3) * HW2 + (tap % 3);
+      // what this item issues: halo piece `tap` of chunk cc+1 (PH: pieces tap and tap + 3 during taps 0..2), weight rows of item i+3
+      // into the stage of item i-1
+      const bool iss_h = more_c && tap < (PH ? 3 : CW_NA) && tap * 8 + wave < HALO_RG;
+      const bool iss_h2 = PH && more_c && tap + 3 < CW_NA && (tap + 3) * 8 + wave < HALO_RG;     // (tap + 3 < 5: taps 0, 1)
       const bool iss_w = item + 3 < NI;
       const int st3 = st == 0 ? 3 : st - 1;         // (st + 3) % 4
       int koff3;
       {
         int t3 = tap + 3, c3 = cc;
-        if (t3 >= 9) { t3 -= 9; c3 = cc + 1; }
+        if (t3 >= NTAP) { t3 -= NTAP; c3 = cc + 1; }
         koff3 = (t3 * p.Cin + c3 * BK) * (int)sizeof(T);
       }
       // ---- read part ----
       if (SCH != 0) { if (iss_h) hoff = aoff_lds[tap * 512]; }
+      if (PH) { if (iss_h2) hoff2 = aoff_lds[(tap + 3) * 512]; }
       u32x4 wf[TN], xf[TM];
 #pragma unroll
       for (int a = 0; a < TN; ++a) wf[a] = *(const u32x4*)(Wst + wfoff + a * 16 * CB);
@@ -229,16 +247,17 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const GemmParams p, c
         xf[b] = *(const u32x4*)(Ah + h * CB + ((kg ^ ((h >> 1) & 2)) << 4));
       }
       // item i+1 must have landed before the barrier that precedes anybody's read of it.  Younger than its last DMA, in issue
-      // order: [halo piece of item i-1] [weights of item i+2]
-      if (item + 1 < NI) wait_n(prev_h + (item + 2 < NI ? my_w : 0));
-      prev_h = iss_h ? 1 : 0;
+      // order: [halo piece(s) of item i-1] [weights of item i+2].  PH, last tap of a chunk: item i+1 opens the next chunk, whose
+      // halo pieces (issued up to item i-1, in front of that item's weights) must all have landed as well
+      if (item + 1 < NI) wait_n((PH && tap == NTAP - 1 ? 0 : prev_h) + (item + 2 < NI ? my_w : 0));
+      prev_h = (iss_h ? 1 : 0) + (iss_h2 ? 1 : 0);
       pp_barrier();
       // ---- multiply part ----
       if (SCH == 0) {
         if (more_c && tap < CW_NA) issue_a(tap, cc + 1, (cc + 1) & 1);
         const int t3 = tap + 3;
-        if (t3 < 9) issue_w(t3, cc, st3);
-        else if (more_c) issue_w(t3 - 9, cc + 1, st3);
+        if (t3 < NTAP) issue_w(t3, cc, st3);
+        else if (more_c) issue_w(t3 - NTAP, cc + 1, st3);
       }
       if (prio == 0) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -249,7 +268,10 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const GemmParams p, c
           // after MFMAs 4, 12, 20, 28: [halo piece, weight groups 0, 1, 2]
           const int sl = a >> 1;
           __builtin_amdgcn_sched_barrier(0);
-          if (sl == 0) { if (iss_h) issue_a_off(tap, cc + 1, (cc + 1) & 1, hoff); }
+          if (sl == 0) {
+            if (iss_h) issue_a_off(tap, cc + 1, (cc + 1) & 1, hoff);
+            if (PH) { if (iss_h2) issue_a_off(tap + 3, cc + 1, (cc + 1) & 1, hoff2); }
+          }
           else if (iss_w) issue_w_one(sl - 1, koff3, st3, w_off0);
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -268,7 +290,7 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const GemmParams p, c
     return;
   }
   const float mean[TM] = {0.f, 0.f, 0.f, 0.f}, rstd[TM] = {1.f, 1.f, 1.f, 1.f};
-  wide_epilogue<T, false, RES, false>(p, acc, mean, rstd, m0 + wm * 64, n0 + wn * (TN * 16), lane, slice);
+  wide_epilogue<T, false, RES, false, PH>(p, acc, mean, rstd, m0 + wm * 64, n0 + wn * (TN * 16), lane, slice, phase);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -647,6 +669,25 @@ bool conv_wide_ok(int dtype, const GemmParams& p) {
   return tuning().force_big_kernels || tiles >= 224;
 }
 
+// the source-resolution stride-1 problem one phase of an upsampler conv solves (PH form of conv3x3_wide_kernel)
+static GemmParams ups_phase_problem(const GemmParams& p) {
+  GemmParams q = p;
+  q.W = p.Wph; q.Wph = nullptr;
+  q.Kp = 4 * (int64_t)p.Cin; q.K = 4 * p.Cin;
+  q.M = p.M / 4; q.H = p.Hin; q.Wd = p.Win; q.ups = 0;
+  return q;
+}
+
+bool conv_ups_phase_ok(int dtype, const GemmParams& p) {
+  if (!tuning().ups_phases || p.ups != 1 || p.splitk > 1 || p.R || p.M % 1024 != 0) return false;
+  if (!conv_wide_ok(dtype, p)) return false;            // (M counted per launch: four phases x M / 4 rows = the nine-tap form's tiles)
+  GemmParams q = ups_phase_problem(p);
+  q.W = p.W;                                            // (alignment checks only)
+  if ((int64_t)4 * p.N * q.Kp * 2 >= (int64_t)0xFFFF0000) return false;   // 32-bit weight offsets inside a phase; the phase base is 64-bit
+  WideHaloGeom g;
+  return wide_halo_geom(q, g);
+}
+
 // split-K factor the wide conv wants for a problem whose 256 x 320 tiling does not fill the chip (0: not a wide-conv problem)
 int conv_wide_pick_splitk(int dtype, const GemmParams& p) {
   GemmParams q = p;
@@ -683,6 +724,25 @@ static int launch_conv_wide_sch(const GemmParams& p, const unsigned char* zero_p
   return 0;
 }
 
+// the four phase convolutions of an upsampler conv in one launch: the phase is the two low bits of the (XCD-remapped) workgroup index
+template <typename T>
+static int launch_conv_wide_phase(int dtype, const GemmParams& p, const unsigned char* zero_page, hipStream_t s) {
+  if (!conv_ups_phase_ok(dtype, p) || ((uintptr_t)p.Wph & 15)) TANGO_FAIL("conv_wide: phase weights given for a problem the phase form does not take");
+  const GemmParams q = ups_phase_problem(p);
+  WideHaloGeom g;
+  if (!wide_halo_geom(q, g)) TANGO_FAIL("conv_wide: unsupported geometry");
+  const int abytes = ((g.halo + 15) / 16) * 1024;
+  int lds = 2 * abytes + 4 * 320 * 64 + (CW_NA_WIDE + 1) * 512 * 4;
+  const int epi_lds = 8 * (WIDE_STAGE_BYTES + 1280);
+  if (lds < epi_lds) lds = epi_lds;
+  auto kfn = conv3x3_wide_kernel<T, false, false, 1, false, true>;
+  TANGO_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(kfn), lds));
+  const int tiles = (q.M / 256) * (q.N / 320);
+  hipLaunchKernelGGL(kfn, dim3((unsigned)(4 * tiles)), dim3(512), lds, s, q, zero_page, g.SR, g.nseg, abytes, tuning().wide_prio);
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
 template <typename T, bool RES, bool SK>
 static int launch_conv_wide_pipe(const GemmParams& p, const unsigned char* zero_page, hipStream_t s) {
   WideHaloGeom g;
@@ -715,6 +775,7 @@ static int launch_conv_wide_cfg(const GemmParams& p, const unsigned char* zero_p
 
 int launch_conv_wide(int dtype, const GemmParams& p, const unsigned char* zero_page, hipStream_t s) {
   if (!zero_page) TANGO_FAIL("conv_wide: gemm_init() was not called (zero page for the LDS-DMA gather)");
+  if (p.Wph) return dtype == DT_F16 ? launch_conv_wide_phase<f16>(dtype, p, zero_page, s) : launch_conv_wide_phase<bf16>(dtype, p, zero_page, s);
   switch (dtype) {
     case DT_F16:
       if (p.splitk > 1) return launch_conv_wide_cfg<f16, false, true>(p, zero_page, s);

@@ -524,6 +524,38 @@ int launch_pack(int dtype, const float* src, void* dst, int O, int Tn, int I, in
   return 0;
 }
 
+// Phase weights of a nearest-x2 upsampler conv (conv_wide.hip PH; rule and layout: common.h launch_pack_ups_phase).  One thread per
+// destination element; the up to four original taps are added in fp32 in ascending (ky, kx) order and rounded once.
+template <typename T>
+__global__ __launch_bounds__(256) void ups_phase_pack_kernel(const float* __restrict__ src, T* __restrict__ dst, int O, int I) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)16 * O * I) return;
+  const int i = (int)(idx % I);
+  const int tap = (int)((idx / I) & 3);
+  const int o = (int)((idx / ((int64_t)4 * I)) % O);
+  const int ph = (int)(idx / ((int64_t)4 * I * O));
+  const int py = ph >> 1, px = ph & 1, ty = tap >> 1, tx = tap & 1;
+  // rows(0, 0) = {0}, rows(0, 1) = {1, 2}, rows(1, 0) = {0, 1}, rows(1, 1) = {2}
+  const int y0 = py ? (ty ? 2 : 0) : (ty ? 1 : 0), y1 = py ? (ty ? 2 : 1) : (ty ? 2 : 0);
+  const int x0 = px ? (tx ? 2 : 0) : (tx ? 1 : 0), x1 = px ? (tx ? 2 : 1) : (tx ? 2 : 0);
+  const float* w = src + ((int64_t)o * I + i) * 9;
+  float v = 0.f;
+  for (int ky = y0; ky <= y1; ++ky)
+    for (int kx = x0; kx <= x1; ++kx) v += w[ky * 3 + kx];
+  dst[idx] = from_f<T>(v);
+}
+
+int launch_pack_ups_phase(int dtype, const float* src, void* dst, int O, int I, hipStream_t s) {
+  const unsigned nb = (unsigned)(((int64_t)16 * O * I + 255) / 256);
+  switch (dtype) {
+    case DT_F16: hipLaunchKernelGGL((ups_phase_pack_kernel<f16>), dim3(nb), dim3(256), 0, s, src, (f16*)dst, O, I); break;
+    case DT_BF16: hipLaunchKernelGGL((ups_phase_pack_kernel<bf16>), dim3(nb), dim3(256), 0, s, src, (bf16*)dst, O, I); break;
+    default: TANGO_FAIL("pack_ups_phase: 16-bit dtypes only");
+  }
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
 
 // VAE: z * scale -> post_quant_conv (1x1, tiny C) fused with NCHW fp32 -> NHWC T
 // (audioldm/variational_autoencoder/autoencoder.py:121 and :61)

@@ -54,6 +54,7 @@ struct WMat {            // packed GEMM weight [N][Kp] (engine dtype) + fp32 bia
   int N = 0, K = 0, Cin = 0, taps = 1;
   int64_t Kp = 0;
   bool im2col = false;   // 3x3 conv with tiny Cin: K = 9*Cin zero-padded to Kp, A comes from im2col
+  void* Wph = nullptr;   // UNet upsampler convs, 16-bit engines: [4 phases][N][4 Cin] summed 2x2-tap phase weights (launch_pack_ups_phase)
   // LayerNorm-folded copy (linear_stream.hip): W' = W*gamma, b' = b + W.beta, wsum[n] = sum_k W'[n][k]
   void* Wln = nullptr;
   float* bln = nullptr;
@@ -247,7 +248,7 @@ class Engine {
   void reg_norm(const std::string& p, int C, float eps, WNorm& w);
   void reg_mat(const std::string& wname, int N, int K, WMat& w, bool alloc, int row_off, std::vector<int64_t> shape, bool geglu = false);
   void reg_linear(const std::string& p, int N, int K, WMat& w, bool bias);
-  void reg_conv3x3(const std::string& p, int Cout, int Cin, WMat& w);
+  void reg_conv3x3(const std::string& p, int Cout, int Cin, WMat& w, bool ups_phase = false);
   void reg_conv1x1(const std::string& p, int Cout, int Cin, WMat& w);
   void reg_conv1d(const std::string& p, int Cout, int Cin, int k, WMat& w);
   void reg_convt1d(const std::string& p, int Cin, int Cout, int k, int u, ConvTW& w);

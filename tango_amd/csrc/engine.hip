@@ -179,6 +179,15 @@ struct Builder {
     if (o.residual) { p.R = o.residual->p; p.ldr = o.residual->ld; }
     p.a_act = o.a_act; p.a_slope = o.a_slope; p.e_act = o.e_act; p.e_slope = o.e_slope; p.epi = o.epi;
     p.bias2 = o.bias2; p.bias2_stride = o.bias2_stride; p.step_ptr = o.bias2 ? E.d_step : nullptr;
+    if (ups && w.Wph && gemm_pick_splitk(dt, p) <= 1 && gemm_route(dt, p) == ROUTE_CONV_WIDE && conv_ups_phase_ok(dt, p)) {
+      // four 2x2-tap phase convolutions on the source grid: label and flop count say what is executed (K = 4 Cin)
+      p.Wph = w.Wph;
+      const int d = dt;
+      char buf[160];
+      snprintf(buf, sizeof buf, "conv3x3up(phase) M=%d N=%d K=%d", p.M, p.N, 4 * p.Cin);
+      push([p, d](hipStream_t s) { return launch_gemm(d, p, s); }, buf, 2.0 * p.M * (double)p.N * 4.0 * p.Cin);
+      return;
+    }
     gemm(p, stride == 2 ? "conv3x3s2" : (ups ? "conv3x3up" : "conv3x3"));
   }
 
@@ -699,7 +708,7 @@ void Engine::reg_conv1x1(const std::string& p, int Cout, int Cin, WMat& w) {
   reg_vec(p + ".bias", Cout, &w.b);
 }
 
-void Engine::reg_conv3x3(const std::string& p, int Cout, int Cin, WMat& w) {
+void Engine::reg_conv3x3(const std::string& p, int Cout, int Cin, WMat& w, bool ups_phase) {
   w.N = Cout;
   w.im2col = ((Cin * esz) % 64) != 0;
   if (w.im2col) {
@@ -713,8 +722,14 @@ void Engine::reg_conv3x3(const std::string& p, int Cout, int Cin, WMat& w) {
   const int64_t Kp = w.Kp;
   const int d = dt;
   // OIHW -> [O][tap][I]
-  reg_slot(p + ".weight", {Cout, Cin, 3, 3},
-           [=](const float* src, hipStream_t s) { return launch_pack(d, src, W, Cout, 9, Cin, (int64_t)Cin * 9, 1, 9, Kp, 0, s); });
+  // upsampler convs of the 16-bit engines additionally keep the summed phase weights (conv_wide.hip PH); both are rebuilt on reload
+  void* Wph = nullptr;
+  if (ups_phase && dt != DT_F32 && !w.im2col) w.Wph = Wph = dmalloc((size_t)16 * Cout * Cin * esz);
+  reg_slot(p + ".weight", {Cout, Cin, 3, 3}, [=](const float* src, hipStream_t s) {
+    TANGO_TRY(launch_pack(d, src, W, Cout, 9, Cin, (int64_t)Cin * 9, 1, 9, Kp, 0, s));
+    if (Wph) TANGO_TRY(launch_pack_ups_phase(d, src, Wph, Cout, Cin, s));
+    return 0;
+  });
   reg_vec(p + ".bias", Cout, &w.b);
 }
 
@@ -888,7 +903,7 @@ void Engine::build_unet_weights() {
     }
     if (i != nl - 1) {
       u.has_us = true;
-      reg_conv3x3(bp + ".upsamplers.0.conv", outc, outc, u.us);
+      reg_conv3x3(bp + ".upsamplers.0.conv", outc, outc, u.us, true);
     }
     prev_out = outc;
   }

@@ -419,6 +419,7 @@ int launch_gemm(int dtype, const GemmParams& p, hipStream_t s) {
   if (p.wb_rows && route != ROUTE_WIDE && route != ROUTE_DUO) TANGO_FAIL("gemm: per-sample weights are implemented by the 256 x 320 / 256 x 160 GEMMs only");
   if (p.glu_tanh && dtype != DT_F32 && route != ROUTE_WIDE && route != ROUTE_DUO)
     TANGO_FAIL("gemm: the tanh-GELU gate (T5 gated-gelu) is implemented by the fp32 kernels and the 256 x 320 / 256 x 160 GEMMs only");
+  if (p.Wph && route != ROUTE_CONV_WIDE) TANGO_FAIL("gemm: upsampler phase weights are implemented by the 256 x 320 conv only");
   switch (route) {
     case ROUTE_WIDE: return launch_gemm_wide(dtype, p, s);
     case ROUTE_DUO: return launch_gemm_duo(dtype, p, s);

@@ -37,9 +37,12 @@ __device__ __forceinline__ f32x4 wide_col_value(const f32x4 av, const float mean
 // LN: folded LayerNorm (see linear_stream.hip): y = rstd[m] * (acc - mean[m] * wsum[n]) + b'[n] with the row statistics the
 // main loop accumulated; acc - mean * wsum is the single-instruction form that linear_stream.hip's race notes call for.
 // The per-column constants (bias [+ bias2], wsum) sit in LDS behind the staging rows, not in 80 VGPRs.
-template <typename T, bool GEGLU, bool RES, bool LN>
+// UPH (conv_wide.hip PH): row m = (b, i, j) of the p.H x p.Wd source grid is output phase (py, px) = (phase >> 1, phase & 1) of the
+// x2-upsampled image and goes to output row (b 2H + 2i + py) 2W + 2j + px.
+template <typename T, bool GEGLU, bool RES, bool LN, bool UPH = false>
 __device__ __forceinline__ void wide_epilogue(const GemmParams& p, f32x4 (&acc)[10][4], const float (&mean)[4], const float (&rstd)[4],
-                                              const int m_base, const int n_base, const int lane, unsigned char* stage) {
+                                              const int m_base, const int n_base, const int lane, unsigned char* stage, const int phase = 0) {
+  static_assert(!UPH || (!GEGLU && !RES && !LN), "phase rows: plain epilogue only");
   constexpr int TN = 10, NIT = 5;
   constexpr int OC = GEGLU ? 80 : 160;                 // output columns of this wave
   constexpr int PITCH = OC * 4 + 16;                   // fp32 staging row
@@ -122,7 +125,14 @@ __device__ __forceinline__ void wide_epilogue(const GemmParams& p, f32x4 (&acc)[
       for (int e = 0; e < 8; ++e) tv[e] = from_f<T>(f[e]);
       u32x4 o;
       __builtin_memcpy(&o, tv, 16);
-      *(u32x4*)(Ob + (int64_t)(m_base + ps * RPP + prow[it]) * ldo + ocol0 + pcol[it]) = o;
+      int64_t orow = m_base + ps * RPP + prow[it];
+      if (UPH) {
+        const int m = (int)orow, hw = p.H * p.Wd;
+        const int bi = m / hw, r = m - bi * hw;
+        const int i = r / p.Wd, j = r - i * p.Wd;
+        orow = ((int64_t)bi * 2 * p.H + 2 * i + (phase >> 1)) * (2 * p.Wd) + 2 * j + (phase & 1);
+      }
+      *(u32x4*)(Ob + orow * ldo + ocol0 + pcol[it]) = o;
     }
     __builtin_amdgcn_wave_barrier();
   }

@@ -79,10 +79,9 @@ static int run_gemm(int dt, GemmParams& p, Scratch& sc, hipStream_t s) {
   return launch_gemm(dt, p, s);
 }
 
-extern "C" {
-
-int tango_op_conv2d(int dt, const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
-                    int stride, int upsample, void* stream) {
+// phases: -1 = as the engine decides (phase form where conv_ups_phase_ok), 0 = nine-tap form, 1 = phase form or an error
+static int op_conv2d_impl(int dt, const float* x, const float* w, const float* bias, const float* bias2, float* out, int B, int Cin, int H, int W,
+                          int Cout, int stride, int upsample, int phases, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const size_t esz = dtype_size(dt);
   Scratch sc;
@@ -97,6 +96,7 @@ int tango_op_conv2d(int dt, const float* x, const float* w, const float* bias, f
   TANGO_TRY(launch_nchw_to_nhwc(dt, x, xt, cpad, B, Cin, H * W, 1, 1.0f, s));
   GemmParams p;
   p.bias = bias; p.N = Cout; p.out = ot; p.ldo = Cout;
+  if (bias2) { p.bias2 = bias2; p.bias2_stride = Cout; }
   if (im2col) {
     if (stride != 1 || upsample) TANGO_FAIL("op_conv2d: small-Cin path supports stride 1 only");
     const int64_t Kp = ((9 * Cin + 31) / 32) * 32;
@@ -114,9 +114,37 @@ int tango_op_conv2d(int dt, const float* x, const float* w, const float* bias, f
     TANGO_TRY(launch_pack(dt, w, wt, Cout, 9, Cin, (int64_t)Cin * 9, 1, 9, Kp, 0, s));
     p.A = xt; p.lda = cpad; p.W = wt; p.Kp = Kp; p.M = B * Ho * Wo; p.K = 9 * Cin; p.Cin = Cin;
     p.mode = GATHER_2D; p.H = Ho; p.Wd = Wo; p.Hin = H; p.Win = W; p.stride = stride; p.ups = upsample;
+    const bool ph_ok = upsample == 1 && stride == 1 && phases != 0 && gemm_pick_splitk(dt, p) <= 1 &&
+                       gemm_route(dt, p) == ROUTE_CONV_WIDE && conv_ups_phase_ok(dt, p);
+    if (phases == 1 && !ph_ok) TANGO_FAIL("op_conv2d_ups: the phase form does not take this problem");
+    if (ph_ok) {
+      void* wph = sc.get((size_t)16 * Cout * Cin * esz);
+      if (!wph) TANGO_FAIL("op_conv2d: alloc");
+      TANGO_TRY(launch_pack_ups_phase(dt, w, wph, Cout, Cin, s));
+      p.Wph = wph;
+    }
   }
   TANGO_TRY(run_gemm(dt, p, sc, s));
   TANGO_TRY(launch_nhwc_to_nchw_f32(dt, ot, Cout, out, B, Cout, Ho * Wo, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" {
+
+int tango_op_conv2d(int dt, const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
+                    int stride, int upsample, void* stream) {
+  return op_conv2d_impl(dt, x, w, bias, nullptr, out, B, Cin, H, W, Cout, stride, upsample, -1, stream);
+}
+
+int tango_op_conv2d_ups(int dt, const float* x, const float* w, const float* bias, const float* bias2, float* out, int B, int Cin, int H,
+                        int W, int Cout, int phases, void* stream) {
+  return op_conv2d_impl(dt, x, w, bias, bias2, out, B, Cin, H, W, Cout, 1, 1, phases ? 1 : 0, stream);
+}
+
+int tango_op_pack_ups_phase(int dt, const float* w, void* out, int Cout, int Cin, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TANGO_TRY(launch_pack_ups_phase(dt, w, out, Cout, Cin, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -57,6 +57,7 @@ struct Tuning {
   int attn_x8_qb;           // TANGO_ATTN_X8_QB=1|2     MX fp8 P.V attention (unet_attn_fp8 = 2): 16 query rows per wave at three waves per SIMD, or 32 at two (round 6)
   int conv_tall;            // TANGO_CONV_TALL=0|1      3x3 wide conv on the 512-pixel x 160-channel form of the tile where the halo fits (round 6: half the weight DMA per MFMA)
   int wide_pipe;            // TANGO_WIDE_PIPE=0|1|2    256 x 320 GEMM: in-wave software pipeline (fragments of item i+1 requested under the MFMAs of item i) instead of the ping-pong read / multiply parts; 1 = staggered halves, two barriers per item, 2 = all waves in step, one barrier per item (round 6: both slower than ping-pong on the GEMMs)
+  bool ups_phases;          // TANGO_UPS_PHASES=0|1     nearest-x2 upsampler convs of the 16-bit engines as four 2x2-tap phase convolutions on the source grid (conv_wide.hip PH: 4/9 of the flops); 0 = the nine-tap gather form (A/B).  Decided when a plan is built
   int conv_pipe;            // TANGO_CONV_PIPE=0..3     256 x 320 conv: 0 = ping-pong kernel, 1 / 2 as above, 3 = one barrier per item with the halves half an item apart.  Default 2 (round 6: convs -1.4 %, bit-identical)
 };
 
@@ -98,6 +99,7 @@ inline Tuning read_tuning() {
   x.wide_pipe = num("TANGO_WIDE_PIPE", 0);
   x.conv_pipe = num("TANGO_CONV_PIPE", 2);
   x.conv_tall = num("TANGO_CONV_TALL", 0);
+  x.ups_phases = num("TANGO_UPS_PHASES", 1) != 0;
   x.attn_x8_qb = num("TANGO_ATTN_X8_QB", 2);
   x.attn_defer = num("TANGO_ATTN_DEFER", 0);
   x.attn_kdma = num("TANGO_ATTN_KDMA", 1);

@@ -317,3 +317,42 @@ def synth_state_dict(shapes: Shapes, seed: int = 1234) -> Dict[str, torch.Tensor
 def iter_synth(shapes: Shapes, seed: int = 1234) -> Iterator[Tuple[str, torch.Tensor]]:
     for k, s in shapes.items():
         yield k, synth_tensor(k, s, seed)
+
+
+# rows(p, t): the original 3x3 taps that tap t of output phase p of a nearest-x2 upsampled image folds into.  Output row 2i + p reads
+# source rows (2i + p + d) >> 1 for d = -1, 0, +1: i-1, i, i for p = 0 and i, i, i+1 for p = 1 -- two distinct rows per phase.
+UPS_PHASE_TAPS = {(0, 0): (0,), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2,)}
+
+
+def upsample_phase_weights(w: torch.Tensor) -> torch.Tensor:
+    """Tap folding of `conv2d(interpolate(x, 2, "nearest"), w, padding=1)` into four 2x2-tap convolutions over x itself.
+
+    w: [O, I, 3, 3] -> [4, O, 2, 2, I] in w's dtype: entry [2 py + px, o, ty, tx, i] multiplies source pixel
+    (i + py + ty - 1, j + px + tx - 1) for output pixel (2i + py, 2j + px).  The folded taps are added in ascending (ky, kx) order in
+    w's own precision (the engine: fp32, then ONE rounding to its 16-bit dtype), so the result is reproducible bit for bit."""
+    O, I = w.shape[:2]
+    out = torch.zeros(4, O, 2, 2, I, dtype=w.dtype)
+    for py in (0, 1):
+        for px in (0, 1):
+            for ty in (0, 1):
+                for tx in (0, 1):
+                    acc = torch.zeros(O, I, dtype=w.dtype)
+                    for ky in UPS_PHASE_TAPS[(py, ty)]:
+                        for kx in UPS_PHASE_TAPS[(px, tx)]:
+                            acc = acc + w[:, :, ky, kx]
+                    out[2 * py + px, :, ty, tx, :] = acc
+    return out
+
+
+def upsample_phase_conv(x: torch.Tensor, wp: torch.Tensor, bias=None) -> torch.Tensor:
+    """The four phase convolutions of `upsample_phase_weights` applied to x [B, I, H, W] -> [B, O, 2H, 2W] (reference statement)."""
+    import torch.nn.functional as F
+    B, _, H, W = x.shape
+    O = wp.shape[1]
+    out = torch.zeros(B, O, 2 * H, 2 * W, dtype=x.dtype)
+    for py in (0, 1):
+        for px in (0, 1):
+            k = wp[2 * py + px].permute(0, 3, 1, 2).contiguous()                 # [O, I, 2, 2]
+            xp = F.pad(x, (1 - px, px, 1 - py, py))                              # rows i + py - 1 .. i + py, same along x
+            out[:, :, py::2, px::2] = F.conv2d(xp, k, bias)
+    return out
