@@ -302,6 +302,47 @@ int tango_op_conv1d(int dtype, const float* x, const float* w, const float* bias
                     int Cin, int L, int Cout, int k, int dilation, int a_act, float a_slope, int e_act, float e_slope, void* stream);
 int tango_op_conv_transpose1d(int dtype, const float* x, const float* w, const float* bias, float* out, int B, int Cin, int L,
                               int Cout, int k, int stride, int padding, int a_act, float a_slope, void* stream);
+/* ---- the gather-GEMM modes and epilogues only the mel-VAE (audioldm/variational_autoencoder/modules.py) and HiFi-GAN (audioldm/hifigan/models.py)
+ * plans use, and the elementwise kernels around them (tests/test_vae_voc_ops_gpu.py) ---- */
+/* 3x3 conv, stride 1 | 2, no upsampling.  pad 1: F.conv2d(x, w, b, stride, padding=1); pad 0: F.conv2d(F.pad(x, (0,1,0,1)), w, b, stride), the
+ * VAE Downsample (modules.py:87-91).  residual [B][Cout][Ho][Wo] or NULL is added after the epilogue activation e_act (0 none, 1 SiLU,
+ * 2 leaky-ReLU with e_slope, 4 tanh).  out_f32: the GEMM itself writes fp32 rows of Cout channels, as the VAE plan does for conv_out */
+int tango_op_conv2d_ex(int dtype, const float* x, const float* w, const float* bias, const float* residual, float* out, int B, int Cin, int H,
+                       int W, int Cout, int stride, int pad, int e_act, float e_slope, int out_f32, void* stream);
+/* out[b] = alpha * A[b] W[b]^T + bias, fp32 [batch][M][N]: GemmParams::batch as Builder::vae_attn uses it.  a [batch][M][lda] (a_shared: [M][lda],
+ * one A for every batch item, stride 0); w [batch][N][ldw], or NULL: W[b] is the view of a[b] that starts w_col_off columns in (N == M,
+ * ldw == lda: the k half of a q | k buffer).  bias [N], or [M] indexed by output row when bias_rows; may be NULL */
+int tango_op_gemm_batched(int dtype, const float* a, const float* w, const float* bias, float* out, int batch, int M, int N, int K, int lda,
+                          int ldw, int w_col_off, int a_shared, float alpha, int bias_rows, void* stream);
+/* out = softmax(x * scale) over each row of x [rows][cols], computed in place on the engine-dtype copy (csrc/norm.hip softmax_rows_kernel) */
+int tango_op_softmax_rows(int dtype, const float* x, float* out, int rows, int cols, float scale, void* stream);
+/* HiFi-GAN conv_post + tanh + the int16 conversion of hifigan/utilities.py:81 in the GEMM epilogue (EPI_I16, out_scale 32768: C truncation,
+ * int16 wrap): out int16 DEVICE, channels-last [B][L][Cout] (Cout = 1: [B][L]) */
+int tango_op_conv1d_i16(int dtype, const float* x, const float* w, const float* bias, int16_t* out, int B, int Cin, int L, int Cout, int k,
+                        int dilation, void* stream);
+/* out = act(((a + b) + c) * scale) on n engine-dtype elements (the resblock average of hifigan/models.py:153-161); n must be a multiple of
+ * the 16-byte vector: an error otherwise */
+int tango_op_avg3_act(int dtype, const float* a, const float* b, const float* c, float* out, int64_t n, float scale, int act, float slope,
+                      void* stream);
+/* 1x1 conv of scale * x, x fp32 [B][Cin][HW] (Cin <= 16), into engine-dtype channels-last rows of ld channels; out fp32 [B*HW][Cout]
+ * (post_quant_conv of z / scale_factor, autoencoder.py:121) */
+int tango_op_pointwise_small(int dtype, const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW, int ld,
+                             float scale, void* stream);
+/* 1x1 conv of fp32 channels-last rows x [B*HW][ld] (first Cin <= 32 channels) into fp32 NCHW out [B][Cout][HW] (quant_conv, autoencoder.py:56) */
+int tango_op_pointwise_out_nchw(const float* x, int ld, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
+                                void* stream);
+/* host-side queries beside tango_debug_linear_route, no GPU needed: the kernel family that takes the problem tango_op_conv2d[_ex] builds for
+ * these arguments -- "tile", "dma", "conv_wide", "conv_halo", "wide", "duo", "stream" -- with "+splitk" when the wrappers' split-K policy
+ * splits it (*splitk, if not NULL, receives the factor; 1 = unsplit) and "+phase" for an upsampler conv in the four-phase form */
+const char* tango_debug_conv2d_route(int dtype, int B, int Cin, int H, int W, int Cout, int stride, int ups, int pad, int residual, int e_act,
+                                     int out_f32, int* splitk);
+/* ... for a conv1d or transposed-conv1d phase: rows_pb output rows per batch item, row q reads inputs q + in_off + tap * tap_step of L and
+ * writes row q * out_mul + out_off.  tango_op_conv1d(k, dilation d) is taps = k, tap_step = d, in_off = -d (k - 1) / 2, rows_pb = L, out_mul 1 */
+const char* tango_debug_conv1d_route(int dtype, int B, int Cin, int L, int Cout, int taps, int tap_step, int in_off, int rows_pb, int out_mul,
+                                     int out_off, int a_act, int residual, int e_act, int* splitk);
+/* phase r of the decomposition tango_op_conv_transpose1d runs: geom6 = {taps, tap_step, in_off, rows_pb, out_mul, out_off} for the query above;
+ * returns 0 when the phase is empty */
+int tango_debug_conv_transpose1d_phase(int B, int Cin, int L, int Cout, int k, int stride, int padding, int r, int* geom6);
 int tango_op_groupnorm(int dtype, const float* x, const float* gamma, const float* beta, float* out, int B, int C, int HW,
                        int groups, float eps, int act, void* stream);
 int tango_op_layernorm(int dtype, const float* x, const float* gamma, const float* beta, float* out, int rows, int C, float eps,

@@ -79,41 +79,98 @@ static int run_gemm(int dt, GemmParams& p, Scratch& sc, hipStream_t s) {
   return launch_gemm(dt, p, s);
 }
 
+// ---- the GemmParams of the op wrappers without their pointers.  The wrappers AND the host-only route queries (tango_debug_*_route)
+// build their problems here, so a query answers for exactly the problem the wrapper launches ----
+static int conv_out_dim(int n, int stride, int pad) { return (n + pad + 1 - 3) / stride + 1; }   // pad 1: symmetric; pad 0: zero row / column at the far edge only
+
+// 3x3 gather conv on NHWC (Cin * esz a multiple of 64 bytes); H, W are the SOURCE dims
+static GemmParams conv2d_problem(int B, int Cin, int H, int W, int Cout, int stride, int upsample, int pad) {
+  const int Hc = H << upsample, Wc = W << upsample;
+  const int Ho = conv_out_dim(Hc, stride, pad), Wo = conv_out_dim(Wc, stride, pad);
+  GemmParams p;
+  p.N = Cout; p.ldo = Cout;
+  p.lda = Cin; p.Kp = 9 * (int64_t)Cin; p.M = B * Ho * Wo; p.K = 9 * Cin; p.Cin = Cin;
+  p.mode = GATHER_2D; p.H = Ho; p.Wd = Wo; p.Hin = H; p.Win = W; p.stride = stride; p.ups = upsample; p.pad = pad;
+  return p;
+}
+// the same conv for tiny Cin: im2col rows [B*H*W][Kp] and a plain GEMM (stride 1, pad 1 only)
+static GemmParams conv2d_im2col_problem(int B, int Cin, int H, int W, int Cout) {
+  const int64_t Kp = ((9 * Cin + 31) / 32) * 32;
+  GemmParams p;
+  p.N = Cout; p.ldo = Cout;
+  p.lda = Kp; p.Kp = Kp; p.M = B * H * W; p.K = (int)Kp; p.Cin = (int)Kp;
+  p.mode = GATHER_1D; p.rows_pb = p.M; p.Lin = p.M; p.Lout = p.M;
+  return p;
+}
+// conv1d taps / transposed-conv1d phase taps on channels-last [B][Lin][Cin]: row q of a batch item reads q + in_off + tap * tap_step
+// and writes row q * out_mul + out_off of [B][Lout][Cout]
+static GemmParams gather1d_problem(int B, int Cin, int Lin, int Cout, int taps, int tap_step, int in_off, int rows_pb, int Lout, int out_mul,
+                                   int out_off) {
+  GemmParams p;
+  p.lda = Cin; p.Kp = (int64_t)taps * Cin; p.M = B * rows_pb; p.N = Cout; p.K = taps * Cin; p.Cin = Cin;
+  p.mode = GATHER_1D; p.rows_pb = rows_pb; p.Lin = Lin; p.taps = taps; p.tap_step = tap_step; p.in_off = in_off;
+  p.Lout = Lout; p.out_mul = out_mul; p.out_off = out_off; p.ldo = Cout;
+  return p;
+}
+static GemmParams conv1d_problem(int B, int Cin, int L, int Cout, int k, int dilation) {
+  return gather1d_problem(B, Cin, L, Cout, k, dilation, -dilation * (k - 1) / 2, L, L, 1, 0);
+}
+// phase r of ConvTranspose1d(k, stride u, padding pd): outputs t = u * q + r - pd read inputs q - tap; false: the phase has no taps or no rows
+static bool convt_phase_problem(int B, int Cin, int L, int Cout, int k, int u, int pd, int r, GemmParams& p) {
+  const int Lo = (L - 1) * u - 2 * pd + k;
+  const int T = (k - r + u - 1) / u;
+  if (T <= 0) return false;
+  const int qmin = (pd > r) ? (pd - r + u - 1) / u : 0;
+  const int qmax = (Lo - 1 + pd - r) / u;
+  const int Q = qmax - qmin + 1;
+  if (Q <= 0) return false;
+  p = gather1d_problem(B, Cin, L, Cout, T, -1, qmin, Q, Lo, u, u * qmin + r - pd);
+  return true;
+}
+
 // phases: -1 = as the engine decides (phase form where conv_ups_phase_ok), 0 = nine-tap form, 1 = phase form or an error
+// residual [B][Cout][Ho][Wo] or null; out_f32: the GEMM writes fp32 rows (ldo = Cout) itself, as the VAE plans do for conv_out
 static int op_conv2d_impl(int dt, const float* x, const float* w, const float* bias, const float* bias2, float* out, int B, int Cin, int H, int W,
-                          int Cout, int stride, int upsample, int phases, void* stream) {
+                          int Cout, int stride, int upsample, int phases, void* stream, int pad = 1, const float* residual = nullptr,
+                          int e_act = ACT_NONE, float e_slope = 0.f, int out_f32 = 0) {
   hipStream_t s = (hipStream_t)stream;
   const size_t esz = dtype_size(dt);
   Scratch sc;
   const int Hc = H << upsample, Wc = W << upsample;
-  const int Ho = stride == 2 ? (Hc + 2 - 3) / 2 + 1 : Hc, Wo = stride == 2 ? (Wc + 2 - 3) / 2 + 1 : Wc;
+  const int Ho = conv_out_dim(Hc, stride, pad), Wo = conv_out_dim(Wc, stride, pad);
+  if (Ho <= 0 || Wo <= 0) TANGO_FAIL("op_conv2d: empty output");
   const bool im2col = ((Cin * esz) % 64) != 0;
   const int cpad = im2col ? ((Cin + 7) / 8) * 8 : Cin;
+  const size_t osz = out_f32 ? 4 : esz;
   void* xt = sc.get((size_t)B * H * W * cpad * esz);
-  void* ot = sc.get((size_t)B * Ho * Wo * Cout * esz);
-  if (!xt || !ot) TANGO_FAIL("op_conv2d: alloc");
+  void* ot = sc.get((size_t)B * Ho * Wo * Cout * osz);
+  void* rt = residual ? sc.get((size_t)B * Ho * Wo * Cout * esz) : nullptr;
+  if (!xt || !ot || (residual && !rt)) TANGO_FAIL("op_conv2d: alloc");
   TANGO_HIP(hipMemsetAsync(xt, 0, (size_t)B * H * W * cpad * esz, s));
   TANGO_TRY(launch_nchw_to_nhwc(dt, x, xt, cpad, B, Cin, H * W, 1, 1.0f, s));
+  if (residual) TANGO_TRY(launch_nchw_to_nhwc(dt, residual, rt, Cout, B, Cout, Ho * Wo, 1, 1.0f, s));
   GemmParams p;
-  p.bias = bias; p.N = Cout; p.out = ot; p.ldo = Cout;
-  if (bias2) { p.bias2 = bias2; p.bias2_stride = Cout; }
   if (im2col) {
-    if (stride != 1 || upsample) TANGO_FAIL("op_conv2d: small-Cin path supports stride 1 only");
-    const int64_t Kp = ((9 * Cin + 31) / 32) * 32;
+    if (stride != 1 || upsample || pad != 1) TANGO_FAIL("op_conv2d: small-Cin path supports stride 1 / pad 1 only");
+    p = conv2d_im2col_problem(B, Cin, H, W, Cout);
+    const int64_t Kp = p.Kp;
     void* wt = sc.get((size_t)Cout * Kp * esz);
     void* col = sc.get((size_t)B * H * W * Kp * esz);
     if (!wt || !col) TANGO_FAIL("op_conv2d: alloc");
     TANGO_TRY(launch_pack(dt, w, wt, Cout, 9, Cin, (int64_t)Cin * 9, 1, 9, Kp, 0, s));
     TANGO_TRY(launch_im2col3x3(dt, xt, cpad, col, Kp, B, H, W, Cin, s));
-    p.A = col; p.lda = Kp; p.W = wt; p.Kp = Kp; p.M = B * H * W; p.K = (int)Kp; p.Cin = (int)Kp;
-    p.mode = GATHER_1D; p.rows_pb = p.M; p.Lin = p.M; p.Lout = p.M;
+    p.A = col; p.W = wt;
   } else {
-    const int64_t Kp = 9 * Cin;
-    void* wt = sc.get((size_t)Cout * Kp * esz);
+    p = conv2d_problem(B, Cin, H, W, Cout, stride, upsample, pad);
+    void* wt = sc.get((size_t)Cout * p.Kp * esz);
     if (!wt) TANGO_FAIL("op_conv2d: alloc");
-    TANGO_TRY(launch_pack(dt, w, wt, Cout, 9, Cin, (int64_t)Cin * 9, 1, 9, Kp, 0, s));
-    p.A = xt; p.lda = cpad; p.W = wt; p.Kp = Kp; p.M = B * Ho * Wo; p.K = 9 * Cin; p.Cin = Cin;
-    p.mode = GATHER_2D; p.H = Ho; p.Wd = Wo; p.Hin = H; p.Win = W; p.stride = stride; p.ups = upsample;
+    TANGO_TRY(launch_pack(dt, w, wt, Cout, 9, Cin, (int64_t)Cin * 9, 1, 9, p.Kp, 0, s));
+    p.A = xt; p.W = wt;
+  }
+  p.bias = bias; p.out = ot; p.out_f32 = out_f32; p.e_act = e_act; p.e_slope = e_slope;
+  if (rt) { p.R = rt; p.ldr = Cout; }
+  if (bias2) { p.bias2 = bias2; p.bias2_stride = Cout; }
+  if (!im2col) {
     const bool ph_ok = upsample == 1 && stride == 1 && phases != 0 && gemm_pick_splitk(dt, p) <= 1 &&
                        gemm_route(dt, p) == ROUTE_CONV_WIDE && conv_ups_phase_ok(dt, p);
     if (phases == 1 && !ph_ok) TANGO_FAIL("op_conv2d_ups: the phase form does not take this problem");
@@ -125,9 +182,31 @@ static int op_conv2d_impl(int dt, const float* x, const float* w, const float* b
     }
   }
   TANGO_TRY(run_gemm(dt, p, sc, s));
-  TANGO_TRY(launch_nhwc_to_nchw_f32(dt, ot, Cout, out, B, Cout, Ho * Wo, s));
+  TANGO_TRY(launch_nhwc_to_nchw_f32(out_f32 ? (int)DT_F32 : dt, ot, Cout, out, B, Cout, Ho * Wo, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
+}
+
+// ---- host-only route queries: never-dereferenced aligned pointers, the wrappers' split-K policy (run_gemm), then the dispatcher's pick ----
+static void* const kRouteDummy = (void*)(uintptr_t)0x10000;
+static const char* route_answer(int dt, GemmParams p, int* splitk_out, const char* suffix = "") {
+  static thread_local std::string out;
+  const int sk = gemm_pick_splitk(dt, p);
+  if (sk > 1) { p.splitk = sk; p.ws = (float*)kRouteDummy; }
+  if (splitk_out) *splitk_out = sk;
+  switch (gemm_route(dt, p)) {
+    case ROUTE_WIDE: out = "wide"; break;
+    case ROUTE_DUO: out = "duo"; break;
+    case ROUTE_STREAM: out = "stream"; break;
+    case ROUTE_CONV_WIDE: out = "conv_wide"; break;
+    case ROUTE_CONV_HALO: out = "conv_halo"; break;
+    case ROUTE_DMA: out = "dma"; break;
+    case ROUTE_TILE: out = "tile"; break;
+    default: out = "none"; break;
+  }
+  if (sk > 1) out += "+splitk";
+  out += suffix;
+  return out.c_str();
 }
 
 extern "C" {
@@ -447,10 +526,8 @@ int tango_op_conv1d(int dt, const float* x, const float* w, const float* bias, c
   TANGO_TRY(launch_nchw_to_nhwc(dt, x, xt, Cin, B, Cin, L, 1, 1.0f, s));
   if (residual) TANGO_TRY(launch_nchw_to_nhwc(dt, residual, rt, Cout, B, Cout, L, 1, 1.0f, s));
   TANGO_TRY(launch_pack(dt, w, wt, Cout, k, Cin, (int64_t)Cin * k, 1, k, (int64_t)k * Cin, 0, s));
-  GemmParams p;
-  p.A = xt; p.lda = Cin; p.W = wt; p.Kp = (int64_t)k * Cin; p.bias = bias; p.M = B * L; p.N = Cout; p.K = k * Cin; p.Cin = Cin;
-  p.mode = GATHER_1D; p.rows_pb = L; p.Lin = L; p.taps = k; p.tap_step = dilation; p.in_off = -dilation * (k - 1) / 2;
-  p.Lout = L; p.out = ot; p.ldo = Cout; p.R = rt; p.ldr = Cout;
+  GemmParams p = conv1d_problem(B, Cin, L, Cout, k, dilation);
+  p.A = xt; p.W = wt; p.bias = bias; p.out = ot; p.R = rt; p.ldr = Cout;
   p.a_act = a_act; p.a_slope = a_slope; p.e_act = e_act; p.e_slope = e_slope;
   TANGO_TRY(run_gemm(dt, p, sc, s));
   TANGO_TRY(launch_nhwc_to_nchw_f32(dt, ot, Cout, out, B, Cout, L, s));
@@ -469,23 +546,150 @@ int tango_op_conv_transpose1d(int dt, const float* x, const float* w, const floa
   if (!xt || !ot) TANGO_FAIL("op_convt1d: alloc");
   TANGO_TRY(launch_nchw_to_nhwc(dt, x, xt, Cin, B, Cin, L, 1, 1.0f, s));
   for (int r = 0; r < u; ++r) {
-    const int T = (k - r + u - 1) / u;
-    if (T <= 0) continue;
+    GemmParams p;
+    if (!convt_phase_problem(B, Cin, L, Cout, k, u, pd, r, p)) continue;
+    const int T = p.taps;
     void* wt = sc.get((size_t)Cout * T * Cin * esz);
     if (!wt) TANGO_FAIL("op_convt1d: alloc");
     TANGO_TRY(launch_pack(dt, w + r, wt, Cout, T, Cin, k, u, (int64_t)Cout * k, (int64_t)T * Cin, 0, s));
-    const int qmin = (pd > r) ? (pd - r + u - 1) / u : 0;
-    const int qmax = (Lo - 1 + pd - r) / u;
-    const int Q = qmax - qmin + 1;
-    if (Q <= 0) continue;
-    GemmParams p;
-    p.A = xt; p.lda = Cin; p.W = wt; p.Kp = (int64_t)T * Cin; p.bias = bias; p.M = B * Q; p.N = Cout; p.K = T * Cin; p.Cin = Cin;
-    p.mode = GATHER_1D; p.rows_pb = Q; p.Lin = L; p.taps = T; p.tap_step = -1; p.in_off = qmin;
-    p.Lout = Lo; p.out_mul = u; p.out_off = u * qmin + r - pd; p.out = ot; p.ldo = Cout;
+    p.A = xt; p.W = wt; p.bias = bias; p.out = ot;
     p.a_act = a_act; p.a_slope = a_slope;
     TANGO_TRY(run_gemm(dt, p, sc, s));
   }
   TANGO_TRY(launch_nhwc_to_nchw_f32(dt, ot, Cout, out, B, Cout, Lo, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_conv2d_ex(int dt, const float* x, const float* w, const float* bias, const float* residual, float* out, int B, int Cin, int H, int W,
+                       int Cout, int stride, int pad, int e_act, float e_slope, int out_f32, void* stream) {
+  if ((stride != 1 && stride != 2) || (pad != 0 && pad != 1)) TANGO_FAIL("op_conv2d_ex: stride must be 1 or 2, pad 0 or 1");
+  return op_conv2d_impl(dt, x, w, bias, nullptr, out, B, Cin, H, W, Cout, stride, 0, 0, stream, pad, residual, e_act, e_slope, out_f32);
+}
+
+const char* tango_debug_conv2d_route(int dt, int B, int Cin, int H, int W, int Cout, int stride, int ups, int pad, int residual, int e_act,
+                                     int out_f32, int* splitk) {
+  GemmParams p;
+  if ((Cin * dtype_size(dt)) % 64 != 0) {
+    p = conv2d_im2col_problem(B, Cin, H, W, Cout);
+  } else {
+    p = conv2d_problem(B, Cin, H, W, Cout, stride, ups, pad);
+  }
+  p.A = kRouteDummy; p.W = kRouteDummy; p.bias = (const float*)kRouteDummy; p.out = kRouteDummy; p.out_f32 = out_f32; p.e_act = e_act;
+  if (residual) { p.R = kRouteDummy; p.ldr = Cout; }
+  const bool phase = p.mode == GATHER_2D && ups == 1 && stride == 1 && gemm_pick_splitk(dt, p) <= 1 && gemm_route(dt, p) == ROUTE_CONV_WIDE &&
+                     conv_ups_phase_ok(dt, p);
+  return route_answer(dt, p, splitk, phase ? "+phase" : "");
+}
+
+const char* tango_debug_conv1d_route(int dt, int B, int Cin, int L, int Cout, int taps, int tap_step, int in_off, int rows_pb, int out_mul,
+                                     int out_off, int a_act, int residual, int e_act, int* splitk) {
+  // Lout only places the output rows: no predicate looks at it
+  GemmParams p = gather1d_problem(B, Cin, L, Cout, taps, tap_step, in_off, rows_pb, rows_pb * out_mul + out_off, out_mul, out_off);
+  p.A = kRouteDummy; p.W = kRouteDummy; p.bias = (const float*)kRouteDummy; p.out = kRouteDummy; p.a_act = a_act; p.e_act = e_act;
+  if (residual) { p.R = kRouteDummy; p.ldr = Cout; }
+  return route_answer(dt, p, splitk);
+}
+
+int tango_debug_conv_transpose1d_phase(int B, int Cin, int L, int Cout, int k, int u, int pd, int r, int* geom6) {
+  GemmParams p;
+  if (!convt_phase_problem(B, Cin, L, Cout, k, u, pd, r, p)) return 0;
+  geom6[0] = p.taps; geom6[1] = p.tap_step; geom6[2] = p.in_off; geom6[3] = p.rows_pb; geom6[4] = p.out_mul; geom6[5] = p.out_off;
+  return 1;
+}
+
+int tango_op_gemm_batched(int dt, const float* a, const float* w, const float* bias, float* out, int batch, int M, int N, int K, int lda,
+                          int ldw, int w_col_off, int a_shared, float alpha, int bias_rows, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype_size(dt);
+  if (batch <= 0 || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K) TANGO_FAIL("op_gemm_batched: bad sizes");
+  if (!w && (a_shared || N != M || ldw != lda || w_col_off < 0 || w_col_off + K > lda)) TANGO_FAIL("op_gemm_batched: W inside A needs per-batch A, N == M, ldw == lda and the columns in range");
+  if (w && w_col_off) TANGO_FAIL("op_gemm_batched: w_col_off is for W inside A");
+  Scratch sc;
+  const int na = a_shared ? 1 : batch;
+  void* at = sc.get((size_t)na * M * lda * esz);
+  void* wt = w ? sc.get((size_t)batch * N * ldw * esz) : nullptr;
+  void* ot = sc.get((size_t)batch * M * N * esz);
+  if (!at || !ot || (w && !wt)) TANGO_FAIL("op_gemm_batched: alloc");
+  TANGO_TRY(launch_cast_rows(dt, a, at, lda, na * M, lda, s));
+  if (w) TANGO_TRY(launch_cast_rows(dt, w, wt, ldw, batch * N, ldw, s));
+  GemmParams p;
+  p.A = at; p.lda = lda; p.W = w ? (const void*)wt : (const void*)((const char*)at + (size_t)w_col_off * esz); p.Kp = ldw;
+  p.bias = bias; p.bias_rows = bias_rows;
+  p.M = M; p.N = N; p.K = K; p.Cin = K; p.mode = GATHER_1D; p.rows_pb = M; p.Lin = M; p.Lout = M; p.taps = 1;
+  p.out = ot; p.ldo = N; p.alpha = alpha;
+  p.batch = batch; p.sA = a_shared ? 0 : (int64_t)M * lda; p.sW = (int64_t)N * ldw; p.sO = (int64_t)M * N;
+  TANGO_TRY(run_gemm(dt, p, sc, s));
+  TANGO_TRY(to_f32(dt, ot, N, out, (int64_t)batch * M, N, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_softmax_rows(int dt, const float* x, float* out, int rows, int cols, float scale, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Scratch sc;
+  void* xt = sc.get((size_t)rows * cols * dtype_size(dt));
+  if (!xt) TANGO_FAIL("op_softmax_rows: alloc");
+  TANGO_TRY(launch_cast_rows(dt, x, xt, cols, rows, cols, s));
+  TANGO_TRY(launch_softmax_rows(dt, xt, cols, rows, cols, scale, s));
+  TANGO_TRY(to_f32(dt, xt, cols, out, rows, cols, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_conv1d_i16(int dt, const float* x, const float* w, const float* bias, int16_t* out, int B, int Cin, int L, int Cout, int k,
+                        int dilation, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype_size(dt);
+  Scratch sc;
+  void* xt = sc.get((size_t)B * L * Cin * esz);
+  void* wt = sc.get((size_t)Cout * k * Cin * esz);
+  if (!xt || !wt) TANGO_FAIL("op_conv1d_i16: alloc");
+  TANGO_TRY(launch_nchw_to_nhwc(dt, x, xt, Cin, B, Cin, L, 1, 1.0f, s));
+  TANGO_TRY(launch_pack(dt, w, wt, Cout, k, Cin, (int64_t)Cin * k, 1, k, (int64_t)k * Cin, 0, s));
+  GemmParams p = conv1d_problem(B, Cin, L, Cout, k, dilation);
+  p.A = xt; p.W = wt; p.bias = bias; p.out = out;
+  p.e_act = ACT_TANH; p.epi = EPI_I16; p.out_scale = 32768.0f;
+  TANGO_TRY(run_gemm(dt, p, sc, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_avg3_act(int dt, const float* a, const float* b, const float* c, float* out, int64_t n, float scale, int act, float slope,
+                      void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n <= 0 || n > 0x7fffffff) TANGO_FAIL("op_avg3_act: n out of range");
+  const size_t esz = dtype_size(dt);
+  Scratch sc;
+  void* at = sc.get((size_t)n * esz); void* bt = sc.get((size_t)n * esz); void* ct = sc.get((size_t)n * esz); void* yt = sc.get((size_t)n * esz);
+  if (!at || !bt || !ct || !yt) TANGO_FAIL("op_avg3_act: alloc");
+  TANGO_TRY(launch_cast_rows(dt, a, at, n, 1, (int)n, s));
+  TANGO_TRY(launch_cast_rows(dt, b, bt, n, 1, (int)n, s));
+  TANGO_TRY(launch_cast_rows(dt, c, ct, n, 1, (int)n, s));
+  const int rc = launch_avg3_act(dt, at, bt, ct, yt, n, scale, act, slope, s);
+  if (rc == 0) TANGO_TRY(to_f32(dt, yt, n, out, 1, (int)n, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return rc;
+}
+
+int tango_op_pointwise_small(int dt, const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW, int ld,
+                             float scale, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ld < Cout) TANGO_FAIL("op_pointwise_small: ld < Cout");
+  Scratch sc;
+  void* yt = sc.get((size_t)B * HW * ld * dtype_size(dt));
+  if (!yt) TANGO_FAIL("op_pointwise_small: alloc");
+  TANGO_TRY(launch_pointwise_small(dt, x, w, bias, yt, ld, B, Cin, Cout, HW, scale, s));
+  TANGO_TRY(to_f32(dt, yt, ld, out, (int64_t)B * HW, Cout, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_pointwise_out_nchw(const float* x, int ld, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
+                                void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ld < Cin) TANGO_FAIL("op_pointwise_out_nchw: ld < Cin");
+  TANGO_TRY(launch_pointwise_out_nchw(x, ld, w, bias, out, B, Cin, Cout, HW, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
 }
