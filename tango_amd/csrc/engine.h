@@ -42,6 +42,15 @@ struct Arena {
   void release(size_t m) { off = m; }
 };
 
+// a dense (no gather) problem out[M, N] = A[M, K] @ W[N, K]^T with row strides lda / Kp
+inline GemmParams dense_gemm(const void* A, int64_t lda, const void* W, int64_t Kp, int M, int N, int K) {
+  GemmParams p;
+  p.A = A; p.lda = lda; p.W = W; p.Kp = Kp;
+  p.M = M; p.N = N; p.K = K; p.Cin = K;
+  p.mode = GATHER_1D; p.rows_pb = M; p.Lin = M; p.Lout = M; p.taps = 1;
+  return p;
+}
+
 struct TView {
   void* p = nullptr;
   int64_t ld = 0;
@@ -120,12 +129,38 @@ struct PlanMeta {
   size_t bytes = 0;
   uint64_t stamp = 0;
 };
-
-struct UNetPlan {
+// the kinds of plan an engine caches: the first entry of a PlanKey, followed by the shape ints of the call
+enum PlanKind { PLAN_UNET, PLAN_VAE_DEC, PLAN_VAE_ENC, PLAN_VOC, PLAN_T5, PLAN_STFT };
+using PlanKey = std::array<int, 7>;
+struct Plan {
+  const PlanKind kind;
   PlanMeta meta;
+  char* slab = nullptr;
+  explicit Plan(PlanKind k) : kind(k) {}     // get_plan() passes the kind of the key
+  virtual ~Plan() = default;
+};
+
+// how a UNet plan runs its batch (the last entry of its PlanKey)
+enum class UNetMode {
+  Whole = 1,       // one program for the whole batch
+  TwoChains = 2,   // two half-batch chains (the plan is a parent with two children)
+  CfgShared = 3,   // one program with the CFG-shared prefix (build_unet)
+};
+
+// the captured graphs of one update kernel: one denoise step, and k_steps of them back to back (round 5)
+struct StepGraphs {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  hipGraph_t graph_k = nullptr;
+  hipGraphExec_t exec_k = nullptr;
+  int k_steps = 0;
+};
+
+struct UNetPlan : Plan {
+  using Plan::Plan;
+  UNetMode mode = UNetMode::Whole;
   int B2 = 0, L = 0;
   int Lc[3] = {0, 0, 0};    // condition lengths: [0] text (== L), [1] beat, [2] chord (Music UNet only)
-  char* slab = nullptr;
   Program pre, step;
   void* xin = nullptr;      // T  [B2*HW][8]
   float* eps = nullptr;     // f32 [B2*HW][out_ch]
@@ -137,44 +172,26 @@ struct UNetPlan {
   // T5("") = one valid token), so their text cross-attention output is the constant to_out(v_key) + b, independent of the query
   int n_short = 0;
   int* key0 = nullptr;      // i32 [B2]: index of that key per sample (entries >= n_short unused)
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  // k denoise steps per replay (round 5): the same step captured k_steps times back to back
-  hipGraph_t graph_k = nullptr;
-  hipGraphExec_t exec_k = nullptr;
-  int k_steps = 0;
-  // the same two graphs with the multistep update (TANGO_RULE_DPM_MULTISTEP): the update kernel is chosen at launch, so a graph
-  // captured for DDPM / DDIM cannot replay a multistep loop (and vice versa); everything else is shared
-  hipGraph_t graph_ms = nullptr;
-  hipGraphExec_t exec_ms = nullptr;
-  hipGraph_t graph_k_ms = nullptr;
-  hipGraphExec_t exec_k_ms = nullptr;
-  int k_steps_ms = 0;
-  // and the masked (inpainting) variants of both update kernels, [0] DDPM / DDIM, [1] multistep: the blend of the next loop index is
-  // fused into the update kernel, so an unmasked call never replays these (nor a masked call the four above)
-  hipGraph_t graph_mk[2] = {nullptr, nullptr};
-  hipGraphExec_t exec_mk[2] = {nullptr, nullptr};
-  hipGraph_t graph_k_mk[2] = {nullptr, nullptr};
-  hipGraphExec_t exec_k_mk[2] = {nullptr, nullptr};
-  int k_steps_mk[2] = {0, 0};
+  // [masked][multistep]: the update kernel is chosen at launch (launch_sched_step: DDPM and DDIM share one, the multistep rule has
+  // its own, and the masked (inpainting) variants fuse the blend of the next loop index into either), so a graph captured with one
+  // cannot replay a loop that needs another; everything else is shared
+  StepGraphs graphs[2][2];
   // Two independent chains (round 5; Engine::denoise): a "dual" plan owns only the UNet input / output buffers of the whole batch; its
   // two children run the first and the second half of the samples (no op of the UNet crosses samples) as two branches of the captured
   // graph, so that one branch's dispatch gaps and kernel tails are filled by the other's kernels.  A child takes xin / eps from its
-  // parent (ext_*), owns its slab and program, and is never in the plan map on its own (the parent's eviction frees all three slabs).
+  // parent (ext_*), owns its slab and program, and is never in the plan cache on its own (the parent's eviction frees all three slabs).
   std::unique_ptr<UNetPlan> child[2];
   void* ext_xin = nullptr;
   float* ext_eps = nullptr;
-  bool cfg_shared = false;     // mode 3: the part of the UNet in front of the first cross-attention runs on B2 / 2 samples (build_unet)
   unsigned* sync = nullptr;    // barrier words its cooperative kernels use (one set per chain: two chains may run such a kernel at once)
 };
 struct T5LayerW {          // T5Block of the encoder: self-attention + gated-GELU feed-forward (no biases anywhere)
   WNorm ln1, ln2;
   WMat qkv, o, wi, wo;     // qkv = fused [q; k; v] rows; wi = [wi_1 | wi_0] in the GLU interleave (value | gate)
 };
-struct T5Plan {
-  PlanMeta meta;
+struct T5Plan : Plan {
+  using Plan::Plan;
   int B = 0, L = 0;
-  char* slab = nullptr;
   Program prog;
   int64_t* ids = nullptr;   // [B*L]
   float* bias = nullptr;    // [B*L] additive key mask
@@ -182,10 +199,9 @@ struct T5Plan {
   float* pos_bias = nullptr;  // [heads][L][L]
   float* out = nullptr;     // [B*L][d_model] fp32
 };
-struct VaePlan {           // also used for the vocoder: plan-owned in/out staging buffers
-  PlanMeta meta;
+struct VaePlan : Plan {    // decoder, encoder and vocoder: plan-owned in/out staging buffers
+  using Plan::Plan;
   int B = 0;
-  char* slab = nullptr;
   Program prog;
   void* in = nullptr;
   void* out = nullptr;
@@ -193,10 +209,9 @@ struct VaePlan {           // also used for the vocoder: plan-owned in/out stagi
   int n_out = 0;            // vocoder: samples per item
 };
 
-struct StftPlan {          // wave -> log-mel front-end buffers for one (batch, n_samples)
-  PlanMeta meta;
+struct StftPlan : Plan {   // wave -> log-mel front-end buffers for one (batch, n_samples)
+  using Plan::Plan;
   int B = 0, N = 0, T = 0, Np = 0, Kp2 = 0, ldz = 0;
-  char* slab = nullptr;
   float *in = nullptr, *xpad = nullptr, *Z = nullptr, *mag = nullptr, *mel_lin = nullptr, *mel = nullptr, *logmag = nullptr, *energy = nullptr;
 };
 
@@ -225,7 +240,7 @@ class Engine {
   void set_plan_budget(size_t bytes) { plan_budget = bytes; }
   void drop_plans() { const size_t b = plan_budget; plan_budget = 0; (void)make_room(1); plan_budget = b; }   // frees every cached plan
   size_t plan_bytes_in_use() const { return plan_bytes; }
-  int plan_count() const;
+  int plan_count() const { return (int)plans.size(); }
 
   tango_config_t cfg;
   int dt = DT_F32;
@@ -301,7 +316,6 @@ class Engine {
 
   // wave -> log-mel front-end (frontend.hip)
   WMat stft_basis, stft_mel;
-  std::map<std::pair<int, int>, std::unique_ptr<StftPlan>> stft_plans;
   int get_stft_plan(int B, int N, StftPlan** out);
 
   // text encoder
@@ -309,7 +323,6 @@ class Engine {
   float* t5_rel_table = nullptr;    // [rel_buckets][heads] fp32
   std::vector<T5LayerW> t5_layers;
   WNorm t5_final_ln;
-  std::map<std::pair<int, int>, std::unique_ptr<T5Plan>> t5_plans;
   int get_t5_plan(int B, int L, T5Plan** out);
   int build_t5(T5Plan& P, Arena& A, bool record);
 
@@ -327,10 +340,6 @@ class Engine {
   float* d_temb = nullptr;       // [max_steps][temb]  silu(emb)
   std::vector<int64_t> temb_ts;  // cache key
   int max_steps = 1000;
-  std::map<std::array<int, 6>, std::unique_ptr<UNetPlan>> unet_plans;   // key: (B2, L_text, L_beat, L_chord, n_short, chains)
-  std::map<int, std::unique_ptr<VaePlan>> vae_plans;
-  std::map<int, std::unique_ptr<VaePlan>> vae_enc_plans;
-  std::map<std::pair<int, int>, std::unique_ptr<VaePlan>> voc_plans;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipStream_t cap_stream = nullptr;
   // second chain of a dual plan: its capture stream, its eager stream, fork / join events (capture and eager pairs), barrier words
@@ -351,21 +360,46 @@ class Engine {
   int hslot_next = 0;
   int stage_h2d(void* dst_dev, const void* src_host, size_t bytes, hipStream_t s);
 
-  // ---- plan caches: shared LRU byte budget ----
+  // ---- the plan cache: every kind of plan in one map, one LRU byte budget ----
+  // keys: UNet (B2, L_text, L_beat, L_chord, n_short, mode); VAE decoder / encoder (B); vocoder (B, frames); T5 (B, L); STFT (B, N)
+  std::map<PlanKey, std::unique_ptr<Plan>> plans;
   size_t plan_budget = (size_t)64 << 30, plan_bytes = 0;
   uint64_t plan_clock = 0;
   void touch(PlanMeta& m) { m.stamp = ++plan_clock; }
   int make_room(size_t need);             // frees least-recently-used plans until plan_bytes + need <= plan_budget (or nothing is left)
   bool evict_lru();
   int alloc_slab(char** slab, size_t bytes, PlanMeta& m, bool zero);   // on out-of-memory: evicts LRU plans and retries
-  void release_slab(char** slab, PlanMeta& m);
+  void free_plan(Plan& P);                // graphs and children of a UNet plan, the slab; gives the bytes back to the budget
+  // `build` lays the plan out in an arena and, when `record`, records its program.  It runs twice: against a null arena to measure,
+  // then on the slab allocated from that measure (+ 256 bytes of slack; zero-filled when `zero`).  A plan that fails is freed here.
+  int build_plan(Plan& P, bool zero, const std::function<int(Arena&, bool record)>& build);
+  // the cached plan of `key`, or a new one: `init` fills in the shape fields, `build` goes through build_plan(), `post` (optional)
+  // runs on the built plan.  The plan enters the cache only when all of that succeeded (it is freed otherwise), so a plan under
+  // construction is invisible to the evictions its own allocation may trigger.
+  template <class P>
+  int get_plan(const PlanKey& key, bool zero, P** out, const std::function<void(P&)>& init,
+               const std::function<int(P&, Arena&, bool record)>& build, const std::function<int(P&)>& post = nullptr) {
+    auto it = plans.find(key);
+    if (it != plans.end()) { touch(it->second->meta); *out = static_cast<P*>(it->second.get()); return 0; }
+    if (!finalized) TANGO_FAIL("engine: weights not finalized");
+    std::unique_ptr<P> p(new P((PlanKind)key[0]));
+    init(*p);
+    TANGO_TRY(build_plan(*p, zero, [&](Arena& A, bool record) { return build(*p, A, record); }));
+    if (post)
+      if (int rc = post(*p)) { free_plan(*p); return rc; }
+    *out = p.get();
+    plans[key] = std::move(p);
+    return 0;
+  }
 
   int ensure_temb(const int64_t* ts_host, int n, hipStream_t s);
-  int get_unet_plan(int B2, int L, int Lbeat, int Lchord, int n_short, UNetPlan** out, int chains = 1);
-  int make_unet_plan(UNetPlan& P);            // measure, allocate the slab, build the programs
-  void free_unet_plan(UNetPlan& P);           // graphs, slab(s), children; gives the bytes back to the budget
+  int get_unet_plan(int B2, int L, int Lbeat, int Lchord, int n_short, UNetPlan** out, UNetMode mode = UNetMode::Whole);
+  int build_unet_plan(UNetPlan& P, Arena& A, bool record);   // build_unet, or the parent and the two children of a two-chain plan
   bool cfg_shared_ok(int B2, int n_short) const;
-  int unet_chains_for(int B2) const;          // 1 or 2: how denoise() runs a batch of B2 UNet rows
+  // how a guidance / plain batch of B2 UNet rows runs; profile_unet() asks with two_chains_ok = false
+  UNetMode unet_mode_for(int B2, int n_short, bool cfg_on, bool two_chains_ok) const;
+  int run_step(const UNetPlan& P, int rule, bool masked, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
+  int capture_steps(const UNetPlan& P, int rule, bool masked, int n, hipGraph_t* g_out, hipGraphExec_t* x_out);
   int single_key_prefix(const uint8_t* mask_dev, const uint8_t* mask_host, int B2, int L, std::vector<int>& key0, hipStream_t s);
   int build_unet(UNetPlan& P, Arena& A, bool record);
   int get_vae_plan(int B, VaePlan** out);
@@ -375,6 +409,7 @@ class Engine {
   int get_voc_plan(int B, int frames, VaePlan** out);
   int build_voc(VaePlan& P, Arena& A, bool record, int frames);
   int bind_text(UNetPlan& P, const Cond (&c)[3], const std::vector<int>& key0, hipStream_t s);
+  int bind_conditions(UNetPlan& P, const Cond (&c)[3], const std::vector<int>& key0, hipStream_t s);   // bind_text per chain
 };
 
 }  // namespace tango

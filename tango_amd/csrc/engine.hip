@@ -95,19 +95,20 @@ struct Builder {
     snprintf(buf, sizeof buf, "%s M=%d N=%d K=%d%s%s", what, p.M, p.N, p.K, p.batch > 1 ? " batched" : "", sk > 1 ? " splitK" : "");
     push([p, d](hipStream_t s) { return launch_gemm(d, p, s); }, buf, 2.0 * p.M * (double)p.N * p.K * p.batch);
   }
-
-
-  // out[rows, N] = x[rows, K] @ W^T
-  void linear(const TView& x, int64_t rows, const WMat& w, const TView& out, const GOpt& o = GOpt()) {
-    GemmParams p;
-    p.A = x.p; p.lda = x.ld; p.W = w.W; p.Kp = w.Kp;
-    p.bias = o.use_bias ? w.b : nullptr;
-    p.M = (int)rows; p.N = w.N; p.K = w.K; p.Cin = w.K;
-    p.mode = GATHER_1D; p.rows_pb = (int)rows; p.Lin = (int)rows; p.Lout = (int)rows; p.taps = 1;
-    p.out = out.p; p.ldo = out.ld; p.out_f32 = o.out_f32;
+  // the part of a GOpt every GEMM-shaped op takes: output type, residual, activations, epilogue, per-step bias
+  void apply(GemmParams& p, const GOpt& o) const {
+    p.out_f32 = o.out_f32;
     if (o.residual) { p.R = o.residual->p; p.ldr = o.residual->ld; }
     p.a_act = o.a_act; p.a_slope = o.a_slope; p.e_act = o.e_act; p.e_slope = o.e_slope; p.epi = o.epi; p.glu_tanh = o.glu_tanh;
     p.bias2 = o.bias2; p.bias2_stride = o.bias2_stride; p.step_ptr = o.bias2 ? E.d_step : nullptr;
+  }
+
+  // out[rows, N] = x[rows, K] @ W^T
+  void linear(const TView& x, int64_t rows, const WMat& w, const TView& out, const GOpt& o = GOpt()) {
+    GemmParams p = dense_gemm(x.p, x.ld, w.W, w.Kp, (int)rows, w.N, w.K);
+    p.bias = o.use_bias ? w.b : nullptr;
+    p.out = out.p; p.ldo = out.ld;
+    apply(p, o);
     if (o.vt) { p.epi = EPI_VT; p.vt = o.vt; p.vt_n0 = o.vt_n0; p.vt_S = o.vt_S; p.vt_ld = o.vt_ld; p.vt_perm = o.vt_perm; }
     if (o.ln) {
       GemmParams q = p;
@@ -175,10 +176,8 @@ struct Builder {
     p.A = x.p; p.lda = x.ld; p.W = w.W; p.Kp = w.Kp; p.bias = o.use_bias ? w.b : nullptr;
     p.M = B * H * W; p.N = w.N; p.K = w.K; p.Cin = w.Cin;
     p.mode = GATHER_2D; p.H = H; p.Wd = W; p.Hin = Hin; p.Win = Win; p.stride = stride; p.ups = ups; p.pad = o.pad;
-    p.out = out.p; p.ldo = out.ld; p.out_f32 = o.out_f32;
-    if (o.residual) { p.R = o.residual->p; p.ldr = o.residual->ld; }
-    p.a_act = o.a_act; p.a_slope = o.a_slope; p.e_act = o.e_act; p.e_slope = o.e_slope; p.epi = o.epi;
-    p.bias2 = o.bias2; p.bias2_stride = o.bias2_stride; p.step_ptr = o.bias2 ? E.d_step : nullptr;
+    p.out = out.p; p.ldo = out.ld;
+    apply(p, o);
     if (ups && w.Wph && gemm_pick_splitk(dt, p) <= 1 && gemm_route(dt, p) == ROUTE_CONV_WIDE && conv_ups_phase_ok(dt, p)) {
       // four 2x2-tap phase convolutions on the source grid: label and flop count say what is executed (K = 4 Cin)
       p.Wph = w.Wph;
@@ -200,10 +199,7 @@ struct Builder {
     gp.B = B; gp.rows = rows; gp.C = gn.C; gp.groups = groups; gp.eps = gn.eps; gp.act = ACT_NONE;
     gp.sync = nullptr;
     if (w.K != gn.C || !gn_fold_ok(dt, gp, w.N)) return false;
-    GemmParams p;
-    p.A = x.p; p.lda = x.ld; p.Kp = w.Kp; p.bias = nullptr;
-    p.M = B * rows; p.N = w.N; p.K = w.K; p.Cin = w.K;
-    p.mode = GATHER_1D; p.rows_pb = p.M; p.Lin = p.M; p.Lout = p.M; p.taps = 1;
+    GemmParams p = dense_gemm(x.p, x.ld, nullptr, w.Kp, B * rows, w.N, w.K);   // W: the folded copy allocated below
     p.out = out.p; p.ldo = out.ld;
     p.wb_rows = rows; p.wb_stride = (int64_t)w.N * w.Kp;
     p.rowvec_rows = p.M; p.rowvec_per = rows; p.out_lo = out.p; p.ldo_lo = out.ld;
@@ -350,17 +346,14 @@ struct Builder {
     // V^T[b][c][s] = Wv[c,:] . hn[b,s,:] + bv[c]   (weights as the row operand, tokens as columns)
     TView vt = alloc((int64_t)B * C, HW);
     {
-      GemmParams p;
-      p.A = w.v.W; p.lda = w.v.Kp; p.W = hn.p; p.Kp = hn.ld; p.bias = w.v.b; p.bias_rows = 1;
-      p.M = C; p.N = HW; p.K = C; p.Cin = C; p.mode = GATHER_1D; p.rows_pb = C; p.Lin = C; p.Lout = C; p.taps = 1;
+      GemmParams p = dense_gemm(w.v.W, w.v.Kp, hn.p, hn.ld, C, HW, C);
+      p.bias = w.v.b; p.bias_rows = 1;
       p.out = vt.p; p.ldo = HW; p.batch = B; p.sA = 0; p.sW = (int64_t)HW * hn.ld; p.sO = (int64_t)C * HW;
       gemm(p);
     }
     TView sc = alloc((int64_t)B * HW, HW);
     {
-      GemmParams p;
-      p.A = qk.p; p.lda = qk.ld; p.W = (char*)qk.p + (size_t)C * esz; p.Kp = qk.ld;
-      p.M = HW; p.N = HW; p.K = C; p.Cin = C; p.mode = GATHER_1D; p.rows_pb = HW; p.Lin = HW; p.Lout = HW; p.taps = 1;
+      GemmParams p = dense_gemm(qk.p, qk.ld, (char*)qk.p + (size_t)C * esz, qk.ld, HW, HW, C);
       p.out = sc.p; p.ldo = HW; p.alpha = 1.0f / std::sqrt((float)C);
       p.batch = B; p.sA = (int64_t)HW * qk.ld; p.sW = (int64_t)HW * qk.ld; p.sO = (int64_t)HW * HW;
       gemm(p);
@@ -371,9 +364,7 @@ struct Builder {
     }
     TView ao = alloc(rows, C);
     {
-      GemmParams p;
-      p.A = sc.p; p.lda = HW; p.W = vt.p; p.Kp = HW;
-      p.M = HW; p.N = C; p.K = HW; p.Cin = HW; p.mode = GATHER_1D; p.rows_pb = HW; p.Lin = HW; p.Lout = HW; p.taps = 1;
+      GemmParams p = dense_gemm(sc.p, HW, vt.p, HW, HW, C, HW);
       p.out = ao.p; p.ldo = C; p.batch = B; p.sA = (int64_t)HW * HW; p.sW = (int64_t)C * HW; p.sO = (int64_t)HW * C;
       gemm(p);
     }
@@ -507,12 +498,7 @@ Engine::Engine(const tango_config_t& c) : cfg(c) {
 
 Engine::~Engine() {
   (void)hipDeviceSynchronize();     // replays of the graphs destroyed below may still be in flight (denoise does not wait for its stream)
-  for (auto& kv : unet_plans) free_unet_plan(*kv.second);
-  for (auto& kv : vae_plans) if (kv.second->slab) (void)hipFree(kv.second->slab);
-  for (auto& kv : vae_enc_plans) if (kv.second->slab) (void)hipFree(kv.second->slab);
-  for (auto& kv : voc_plans) if (kv.second->slab) (void)hipFree(kv.second->slab);
-  for (auto& kv : t5_plans) if (kv.second->slab) (void)hipFree(kv.second->slab);
-  for (auto& kv : stft_plans) if (kv.second->slab) (void)hipFree(kv.second->slab);
+  for (auto& kv : plans) free_plan(*kv.second);
   for (void* p : owned) (void)hipFree(p);
   if (d_ring) (void)hipFree(d_ring);
   for (auto& hs : hslots) {
@@ -538,19 +524,6 @@ void* Engine::dmalloc(size_t bytes) {
   return p;
 }
 
-// ---- plan caches: one byte budget, least recently used first ------------------------------------------------------------------
-namespace {
-template <typename Map> void lru_candidate(Map& m, uint64_t& best, int which, int& best_which) {
-  for (auto& kv : m)
-    if (kv.second->meta.stamp < best) { best = kv.second->meta.stamp; best_which = which; }
-}
-template <typename Map, typename Free> bool lru_erase(Map& m, uint64_t stamp, Free&& fr) {
-  for (auto it = m.begin(); it != m.end(); ++it)
-    if (it->second->meta.stamp == stamp) { fr(*it->second); m.erase(it); return true; }
-  return false;
-}
-}  // namespace
-
 int Engine::stage_h2d(void* dst_dev, const void* src_host, size_t bytes, hipStream_t s) {
   if (bytes == 0) return 0;
   if (bytes > kHostSlotBytes) {          // never on the hot path (tables are <= 32 KB): plain synchronous upload
@@ -572,72 +545,46 @@ int Engine::stage_h2d(void* dst_dev, const void* src_host, size_t bytes, hipStre
   return 0;
 }
 
-int Engine::plan_count() const {
-  return (int)(unet_plans.size() + vae_plans.size() + vae_enc_plans.size() + voc_plans.size() + t5_plans.size() + stft_plans.size());
-}
-
-// frees the least recently used plan of any cache; false when nothing is left to free
+// ---- the plan cache: one byte budget, least recently used first --------------------------------------------------------------
+// frees the least recently used plan of any kind; false when nothing is left to free
 bool Engine::evict_lru() {
-  uint64_t best = ~0ull;
-  int which = -1;
-  lru_candidate(unet_plans, best, 0, which);
-  lru_candidate(vae_plans, best, 1, which);
-  lru_candidate(vae_enc_plans, best, 2, which);
-  lru_candidate(voc_plans, best, 3, which);
-  lru_candidate(t5_plans, best, 4, which);
-  lru_candidate(stft_plans, best, 5, which);
-  if (which < 0) return false;
-  // a slab may still be read by work queued on a stream: hipFree synchronises the device before it releases memory
-  auto drop = [&](auto& P) {
-    plan_bytes -= P.meta.bytes < plan_bytes ? P.meta.bytes : plan_bytes;
-    if (P.slab) (void)hipFree(P.slab);
-  };
-  switch (which) {
-    case 0:
-      return lru_erase(unet_plans, best, [&](UNetPlan& P) {
-        //  a replay of this plan may still be in flight -- denoise() no longer waits for its stream, and destroying an
-        // executing graph is not safe on HIP: drain the device first (hipFree would do so anyway, but only AFTER the destroy)
-        (void)hipDeviceSynchronize();
-        free_unet_plan(P);
-      });
-    case 1: return lru_erase(vae_plans, best, [&](VaePlan& P) { drop(P); });
-    case 2: return lru_erase(vae_enc_plans, best, [&](VaePlan& P) { drop(P); });
-    case 3: return lru_erase(voc_plans, best, [&](VaePlan& P) { drop(P); });
-    case 4: return lru_erase(t5_plans, best, [&](T5Plan& P) { drop(P); });
-    default: return lru_erase(stft_plans, best, [&](StftPlan& P) { drop(P); });
-  }
+  auto lru = plans.end();
+  for (auto it = plans.begin(); it != plans.end(); ++it)
+    if (lru == plans.end() || it->second->meta.stamp < lru->second->meta.stamp) lru = it;
+  if (lru == plans.end()) return false;
+  free_plan(*lru->second);
+  plans.erase(lru);
+  return true;
 }
 
-void Engine::free_unet_plan(UNetPlan& P) {
-  if (P.exec) (void)hipGraphExecDestroy(P.exec);
-  if (P.graph) (void)hipGraphDestroy(P.graph);
-  if (P.exec_k) (void)hipGraphExecDestroy(P.exec_k);
-  if (P.graph_k) (void)hipGraphDestroy(P.graph_k);
-  P.exec = P.exec_k = nullptr; P.graph = P.graph_k = nullptr;
-  for (hipGraphExec_t x : {P.exec_ms, P.exec_k_ms}) if (x) (void)hipGraphExecDestroy(x);
-  for (hipGraph_t g : {P.graph_ms, P.graph_k_ms}) if (g) (void)hipGraphDestroy(g);
-  P.exec_ms = P.exec_k_ms = nullptr; P.graph_ms = P.graph_k_ms = nullptr;
-  for (int r = 0; r < 2; ++r) {
-    for (hipGraphExec_t x : {P.exec_mk[r], P.exec_k_mk[r]}) if (x) (void)hipGraphExecDestroy(x);
-    for (hipGraph_t g : {P.graph_mk[r], P.graph_k_mk[r]}) if (g) (void)hipGraphDestroy(g);
-    P.exec_mk[r] = P.exec_k_mk[r] = nullptr; P.graph_mk[r] = P.graph_k_mk[r] = nullptr; P.k_steps_mk[r] = 0;
+// the one way a plan goes: eviction, drop_plans(), ~Engine and a build that failed
+void Engine::free_plan(Plan& P) {
+  if (P.kind == PLAN_UNET) {
+    UNetPlan& U = static_cast<UNetPlan&>(P);
+    //  a replay of this plan may still be in flight -- denoise() no longer waits for its stream, and destroying an
+    // executing graph is not safe on HIP: drain the device first (hipFree would do so anyway, but only AFTER the destroy)
+    (void)hipDeviceSynchronize();
+    for (auto& row : U.graphs)
+      for (StepGraphs& g : row) {
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        if (g.graph) (void)hipGraphDestroy(g.graph);
+        if (g.exec_k) (void)hipGraphExecDestroy(g.exec_k);
+        if (g.graph_k) (void)hipGraphDestroy(g.graph_k);
+        g = StepGraphs();
+      }
+    for (auto& c : U.child) if (c) { free_plan(*c); c.reset(); }
   }
-  for (auto& c : P.child) if (c) { free_unet_plan(*c); c.reset(); }
-  release_slab(&P.slab, P.meta);
+  // a slab may still be read by work queued on a stream: hipFree synchronises the device before it releases memory
+  if (P.slab) (void)hipFree(P.slab);
+  P.slab = nullptr;
+  plan_bytes -= P.meta.bytes < plan_bytes ? P.meta.bytes : plan_bytes;
+  P.meta.bytes = 0;
 }
 
 int Engine::make_room(size_t need) {
   while (plan_bytes + need > plan_budget)
     if (!evict_lru()) break;                                // nothing left to free: let the allocation decide
   return 0;
-}
-
-// a plan whose program could not be built gives its slab (and its share of the budget) back
-void Engine::release_slab(char** slab, PlanMeta& m) {
-  if (*slab) (void)hipFree(*slab);
-  *slab = nullptr;
-  plan_bytes -= m.bytes < plan_bytes ? m.bytes : plan_bytes;
-  m.bytes = 0;
 }
 
 int Engine::alloc_slab(char** slab, size_t bytes, PlanMeta& m, bool zero) {
@@ -655,6 +602,16 @@ int Engine::alloc_slab(char** slab, size_t bytes, PlanMeta& m, bool zero) {
   m.bytes = bytes;
   plan_bytes += bytes;
   touch(m);
+  return 0;
+}
+
+int Engine::build_plan(Plan& P, bool zero, const std::function<int(Arena&, bool record)>& build) {
+  Arena measure;
+  TANGO_TRY(build(measure, false));
+  TANGO_TRY(alloc_slab(&P.slab, measure.peak + 256, P.meta, zero));
+  Arena real;
+  real.base = P.slab;
+  if (int rc = build(real, true)) { free_plan(P); return rc; }
   return 0;
 }
 
@@ -1291,7 +1248,7 @@ int Engine::build_unet(UNetPlan& P, Arena& A, bool record) {
   // CFG-shared prefix (round 5; Builder::transformer `shared`): the batch is [uncond; cond] with identical latents in both halves, so
   // conv_in, the first ResBlock and the first transformer up to its cross-attention are computed for B2 / 2 samples only.  conv_in's
   // output is also skip 0 -- the last up-block ResBlock reads it for all B2 samples -- so its second half is filled by a row copy.
-  const bool shared = P.cfg_shared;
+  const bool shared = P.mode == UNetMode::CfgShared;
   const int Bh = B2 / 2;
   TView h = skip_dst();                                    // conv_in output = skip 0
   b.conv3x3(xin, shared ? Bh : B2, HH(0), WW(0), HH(0), WW(0), 1, 0, conv_in, h);
@@ -1378,56 +1335,41 @@ int Engine::build_unet(UNetPlan& P, Arena& A, bool record) {
   return 0;
 }
 
-int Engine::make_unet_plan(UNetPlan& P) {
-  Arena m;
-  TANGO_TRY(build_unet(P, m, false));
-  TANGO_TRY(alloc_slab(&P.slab, m.peak + 256, P.meta, true));   // zero-filled: V^T pad columns (L not a multiple of 8) must stay zero
-  Arena a; a.base = P.slab;
-  P.pre.ops.clear(); P.step.ops.clear(); P.pre.labels.clear(); P.step.labels.clear(); P.pre.flops.clear(); P.step.flops.clear();
-  if (int rc = build_unet(P, a, true)) { release_slab(&P.slab, P.meta); return rc; }
+int Engine::build_unet_plan(UNetPlan& P, Arena& A, bool record) {
+  if (P.mode != UNetMode::TwoChains) return build_unet(P, A, record);
+  // the parent: input and output of the whole batch (what the scheduler kernel reads and writes), nothing else
+  const int HW = cfg.latent_h * cfg.latent_w, hb = P.B2 / 2;
+  const int cin_pad = 8 > cfg.unet_in_channels ? 8 : ((cfg.unet_in_channels + 7) / 8) * 8;
+  P.xin = A.alloc((size_t)P.B2 * HW * cin_pad * esz);
+  P.eps = (float*)A.alloc((size_t)P.B2 * HW * cfg.unet_out_channels * 4);
+  for (int k = 0; record && k < 2; ++k) {
+    std::unique_ptr<UNetPlan> C(new UNetPlan(PLAN_UNET));
+    C->B2 = hb; C->L = P.L;
+    for (int i = 0; i < 3; ++i) C->Lc[i] = P.Lc[i];
+    C->n_short = k == 0 ? (P.n_short < hb ? P.n_short : hb) : (P.n_short > hb ? P.n_short - hb : 0);
+    C->ext_xin = (char*)P.xin + (size_t)k * hb * HW * cin_pad * esz;
+    C->ext_eps = P.eps + (size_t)k * hb * HW * cfg.unet_out_channels;
+    C->sync = k == 0 ? d_sync : d_sync2;
+    UNetPlan& c = *C;
+    TANGO_TRY(build_plan(c, true, [&](Arena& a, bool rec) { return build_unet(c, a, rec); }));   // zero-filled, as in get_unet_plan
+    P.child[k] = std::move(C);
+  }
   return 0;
 }
 
-int Engine::get_unet_plan(int B2, int L, int Lbeat, int Lchord, int n_short, UNetPlan** out, int chains) {
+int Engine::get_unet_plan(int B2, int L, int Lbeat, int Lchord, int n_short, UNetPlan** out, UNetMode mode) {
   if (cfg.unet_music && (Lbeat <= 0 || Lchord <= 0)) TANGO_FAIL("engine: the Music UNet needs beat and chord conditions (beat_len, chord_len > 0)");
   if (!cfg.unet_music) { Lbeat = 0; Lchord = 0; }
   if (n_short < 0 || n_short > B2) TANGO_FAIL("engine: bad single-key prefix");
-  // `chains` doubles as the plan's mode: 1 one program for the whole batch, 2 two half-batch chains, 3 one program with the CFG-shared prefix
-  if (chains != 1 && ((chains != 2 && chains != 3) || B2 % 2 != 0)) TANGO_FAIL("engine: dual / CFG-shared plans need an even batch");
-  if (chains == 3 && !cfg_shared_ok(B2, n_short)) TANGO_FAIL("engine: the CFG-shared prefix needs a [single-key; text] batch and a plain UNet");
-  const std::array<int, 6> key = {B2, L, Lbeat, Lchord, n_short, chains};
-  auto it = unet_plans.find(key);
-  if (it != unet_plans.end()) { touch(it->second->meta); *out = it->second.get(); return 0; }
-  if (!finalized) TANGO_FAIL("engine: weights not finalized");
-  std::unique_ptr<UNetPlan> P(new UNetPlan());
-  P->B2 = B2; P->L = L; P->n_short = n_short;
-  P->Lc[0] = L; P->Lc[1] = Lbeat; P->Lc[2] = Lchord;
-  if (chains == 1 || chains == 3) {
-    P->cfg_shared = chains == 3;
-    TANGO_TRY(make_unet_plan(*P));
-  } else {
-    // the parent: input and output of the whole batch (what the scheduler kernel reads and writes), nothing else
-    const int HW = cfg.latent_h * cfg.latent_w, hb = B2 / 2;
-    const int cin_pad = 8 > cfg.unet_in_channels ? 8 : ((cfg.unet_in_channels + 7) / 8) * 8;
-    const size_t xin_bytes = ((size_t)B2 * HW * cin_pad * esz + 255) & ~(size_t)255, eps_bytes = (size_t)B2 * HW * cfg.unet_out_channels * 4;
-    TANGO_TRY(alloc_slab(&P->slab, xin_bytes + eps_bytes + 256, P->meta, true));
-    P->xin = P->slab;
-    P->eps = (float*)(P->slab + xin_bytes);
-    for (int k = 0; k < 2; ++k) {
-      std::unique_ptr<UNetPlan> C(new UNetPlan());
-      C->B2 = hb; C->L = L;
-      C->Lc[0] = L; C->Lc[1] = Lbeat; C->Lc[2] = Lchord;
-      C->n_short = k == 0 ? (n_short < hb ? n_short : hb) : (n_short > hb ? n_short - hb : 0);
-      C->ext_xin = (char*)P->xin + (size_t)k * hb * HW * cin_pad * esz;
-      C->ext_eps = P->eps + (size_t)k * hb * HW * cfg.unet_out_channels;
-      C->sync = k == 0 ? d_sync : d_sync2;
-      if (int rc = make_unet_plan(*C)) { free_unet_plan(*P); return rc; }
-      P->child[k] = std::move(C);
-    }
-  }
-  *out = P.get();
-  unet_plans[key] = std::move(P);
-  return 0;
+  if (mode != UNetMode::Whole && B2 % 2 != 0) TANGO_FAIL("engine: dual / CFG-shared plans need an even batch");
+  if (mode == UNetMode::CfgShared && !cfg_shared_ok(B2, n_short)) TANGO_FAIL("engine: the CFG-shared prefix needs a [single-key; text] batch and a plain UNet");
+  // zero-filled: V^T pad columns (L not a multiple of 8) must stay zero
+  return get_plan<UNetPlan>({PLAN_UNET, B2, L, Lbeat, Lchord, n_short, (int)mode}, true, out,
+                            [&](UNetPlan& P) {
+                              P.mode = mode; P.B2 = B2; P.L = L; P.n_short = n_short;
+                              P.Lc[0] = L; P.Lc[1] = Lbeat; P.Lc[2] = Lchord;
+                            },
+                            [this](UNetPlan& P, Arena& A, bool record) { return build_unet_plan(P, A, record); });
 }
 
 int Engine::bind_text(UNetPlan& P, const Cond (&c)[3], const std::vector<int>& key0, hipStream_t s) {
@@ -1444,6 +1386,27 @@ int Engine::bind_text(UNetPlan& P, const Cond (&c)[3], const std::vector<int>& k
     else TANGO_TRY(launch_fill_zero(P.biases[i], (size_t)n * 4, s));
   }
   return P.pre.run(s);
+}
+
+// bind_text for the plan's one program, or for each of its two chains: a chain binds its own half of the conditions (rows [0, B2/2)
+// and [B2/2, B2) of every [B2, L, d] tensor)
+int Engine::bind_conditions(UNetPlan& P, const Cond (&c)[3], const std::vector<int>& key0, hipStream_t s) {
+  if (P.mode != UNetMode::TwoChains) return bind_text(P, c, key0, s);
+  const int hb = P.B2 / 2;
+  for (int k = 0; k < 2; ++k) {
+    UNetPlan& Ck = *P.child[k];
+    Cond ck[3];
+    for (int i = 0; i < 3; ++i) {
+      ck[i] = c[i];
+      if (c[i].emb) ck[i].emb = c[i].emb + (size_t)k * hb * c[i].len * cfg.unet_cross_dim;
+      if (c[i].mask) ck[i].mask = c[i].mask + (size_t)k * hb * c[i].len;
+      ck[i].mask_host = nullptr;
+    }
+    std::vector<int> k0;
+    if (Ck.n_short > 0) k0.assign(key0.begin() + (size_t)k * hb, key0.begin() + (size_t)k * hb + Ck.n_short);
+    TANGO_TRY(bind_text(Ck, ck, k0, s));
+  }
+  return 0;
 }
 
 // How many leading samples keep exactly ONE text key (and which): the unconditional half of a CFG batch is T5("") = one valid token
@@ -1491,9 +1454,6 @@ int Engine::unet_forward(const float* sample, int64_t t, const Cond (&c)[3], flo
 // steps per captured graph when TANGO_GRAPH_STEPS is unset (measured, round 5: see DESIGN.md section 5)
 static int graph_steps_default(int B2) { (void)B2; return 1; }
 
-// One chain or two (round 5)?  Two: the first and the second half of the UNet batch (with guidance: the unconditional and the
-// conditional rows) run as two independent kernel sequences -- two branches of the captured graph -- whose dispatch gaps and kernel
-// tails fill each other.  TANGO_UNET_CHAINS = 1 / 2 forces; unset = the measured rule.
 // May a guidance batch of B2 UNet rows whose first n_short rows are single-key run with the CFG-shared prefix (build_unet)?  The rows
 // b and B2 / 2 + b must carry identical latents -- true inside denoise() with guidance, which fills both halves from one tensor --, the
 // first half must be the single-key (unconditional) half, and the first down block must be a plain cross-attention block.
@@ -1502,14 +1462,17 @@ bool Engine::cfg_shared_ok(int B2, int n_short) const {
          cfg.unet_cross_attn[0] != 0 && cfg.unet_layers_per_block >= 1;
 }
 
-int Engine::unet_chains_for(int B2) const {
-  if (B2 < 2 || B2 % 2 != 0) return 1;
-  const int t = tuning().unet_chains;
-  if (t == 1 || t == 2) return t;
-  return 1;
+// How a batch of B2 UNet rows runs, for denoise() and profile_unet() alike.  One chain or two (round 5)?  Two: the first and the
+// second half of the UNet batch (with guidance: the unconditional and the conditional rows) run as two independent kernel sequences
+// -- two branches of the captured graph -- whose dispatch gaps and kernel tails fill each other.  TANGO_UNET_CHAINS = 1 / 2 forces;
+// unset = the measured rule (one).  One chain takes the CFG-shared prefix where a guidance batch allows it.
+UNetMode Engine::unet_mode_for(int B2, int n_short, bool cfg_on, bool two_chains_ok) const {
+  if (two_chains_ok && B2 >= 2 && B2 % 2 == 0 && tuning().unet_chains == 2) return UNetMode::TwoChains;
+  return cfg_on && cfg_shared_ok(B2, n_short) ? UNetMode::CfgShared : UNetMode::Whole;
 }
 
-int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
+// the argument checks of denoise(): callers read these messages
+static int check_denoise_args(const tango_denoise_args_t& a) {
   if (a.num_steps <= 0) TANGO_FAIL("denoise: num_steps must be positive");
   if (a.rule != TANGO_RULE_DDPM && a.rule != TANGO_RULE_DDIM && a.rule != TANGO_RULE_DPM_MULTISTEP) TANGO_FAIL("denoise: unknown rule");
   const bool ms = a.rule == TANGO_RULE_DPM_MULTISTEP;
@@ -1525,20 +1488,59 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
       if (!(o == 1.0f || (o == 2.0f && i >= 1) || (o == 3.0f && i >= 2))) TANGO_FAIL("denoise: multistep table row with a bad order");
     }
   }
-  const bool mk = a.known_latents != nullptr;       // masked-latent inpainting
+  const bool mk = a.known_latents != nullptr;
   if (mk != (a.latent_mask != nullptr)) TANGO_FAIL("denoise: known_latents and latent_mask go together");
   if (mk && !a.blend_coef) TANGO_FAIL("denoise: a masked call needs blend_coef [num_steps][2]");
   if (!mk && (a.blend_coef || a.blend_noise)) TANGO_FAIL("denoise: blend_coef / blend_noise need known_latents and latent_mask");
+  return 0;
+}
+
+// one denoise step = UNet forward, fused CFG combine + scheduler update (writes the next UNet input), step counter++
+// (two chains: fork after the previous step's update, join before this step's)
+int Engine::run_step(const UNetPlan& P, int rule, bool masked, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join) {
+  if (P.mode != UNetMode::TwoChains) {
+    TANGO_TRY(P.step.run(st));
+  } else {
+    TANGO_HIP(hipEventRecord(fork, st));
+    TANGO_HIP(hipStreamWaitEvent(st2, fork, 0));
+    TANGO_TRY(P.child[0]->step.run(st));
+    TANGO_TRY(P.child[1]->step.run(st2));
+    TANGO_HIP(hipEventRecord(join, st2));
+    TANGO_HIP(hipStreamWaitEvent(st, join, 0));
+  }
+  TANGO_TRY(launch_sched_step(dt, d_sched, P.B2 * cfg.latent_h * cfg.latent_w, st, rule, masked));
+  return launch_step_inc(d_step, st);
+}
+
+// capture `n` steps; every per-step quantity is read through d_step / d_sched
+// (captured on an engine-owned stream: the caller's stream may be the legacy null stream,
+// which cannot be captured; the instantiated graph is then launched on the caller's stream)
+int Engine::capture_steps(const UNetPlan& P, int rule, bool masked, int n, hipGraph_t* g_out, hipGraphExec_t* x_out) {
+  if (!cap_stream) TANGO_HIP(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
+  TANGO_HIP(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeRelaxed));
+  int rc = 0;
+  for (int i = 0; i < n && rc == 0; ++i) rc = run_step(P, rule, masked, cap_stream, cap_stream2, ev_fork, ev_join);
+  hipGraph_t g = nullptr;
+  hipError_t e = hipStreamEndCapture(cap_stream, &g);
+  if (rc != 0) return rc;
+  if (e != hipSuccess) TANGO_FAIL(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+  *g_out = g;
+  TANGO_HIP(hipGraphInstantiate(x_out, g, nullptr, nullptr, 0));
+  return 0;
+}
+
+int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
+  TANGO_TRY(check_denoise_args(a));
+  const bool ms = a.rule == TANGO_RULE_DPM_MULTISTEP;
+  const int coef_w = ms ? 16 : 8;
+  const bool mk = a.known_latents != nullptr;       // masked-latent inpainting
   const bool cfg_on = a.guidance_scale > 1.0f;
   const int B = a.batch, B2 = cfg_on ? 2 * B : B;
   UNetPlan* P;
   std::vector<int> key0;
   const int ns = single_key_prefix(a.prompt_mask, a.prompt_mask_host, B2, a.text_len, key0, s);
-  int chains = unet_chains_for(B2);
-  if (chains == 1 && cfg_on && cfg_shared_ok(B2, ns)) chains = 3;      // one program, CFG-shared prefix (mode 3 of get_unet_plan)
-  TANGO_TRY(get_unet_plan(B2, a.text_len, a.beat_len, a.chord_len, ns, &P, chains));
-  UNetPlan* const CA = chains == 2 ? P->child[0].get() : nullptr;
-  UNetPlan* const CB = chains == 2 ? P->child[1].get() : nullptr;
+  const UNetMode mode = unet_mode_for(B2, ns, cfg_on, true);
+  TANGO_TRY(get_unet_plan(B2, a.text_len, a.beat_len, a.chord_len, ns, &P, mode));
   TANGO_TRY(ensure_temb(a.timesteps, a.num_steps, s));
   const int HW = cfg.latent_h * cfg.latent_w;
   const int C = cfg.unet_in_channels;
@@ -1569,25 +1571,7 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
     c[0].emb = a.prompt_embeds; c[0].mask = a.prompt_mask; c[0].len = a.text_len;
     c[1].emb = a.beat_embeds; c[1].mask = a.beat_mask; c[1].len = a.beat_len;
     c[2].emb = a.chord_embeds; c[2].mask = a.chord_mask; c[2].len = a.chord_len;
-    if (chains != 2) {
-      TANGO_TRY(bind_text(*P, c, key0, s));
-    } else {
-      // each chain binds its own half of the conditions (rows [0, B2/2) and [B2/2, B2) of every [B2, L, d] tensor)
-      const int hb = B2 / 2;
-      for (int k = 0; k < 2; ++k) {
-        UNetPlan& Ck = *P->child[k];
-        Cond ck[3];
-        for (int i = 0; i < 3; ++i) {
-          ck[i] = c[i];
-          if (c[i].emb) ck[i].emb = c[i].emb + (size_t)k * hb * c[i].len * cfg.unet_cross_dim;
-          if (c[i].mask) ck[i].mask = c[i].mask + (size_t)k * hb * c[i].len;
-          ck[i].mask_host = nullptr;
-        }
-        std::vector<int> k0;
-        if (Ck.n_short > 0) k0.assign(key0.begin() + (size_t)k * hb, key0.begin() + (size_t)k * hb + Ck.n_short);
-        TANGO_TRY(bind_text(Ck, ck, k0, s));
-      }
-    }
+    TANGO_TRY(bind_conditions(*P, c, key0, s));
   }
   TANGO_TRY(launch_fill_zero(P->xin, (size_t)B2 * HW * 8 * esz, s));
   TANGO_TRY(launch_nchw_to_nhwc(dt, a.latents, P->xin, 8, B, C, HW, cfg_on ? 2 : 1, 1.0f, s));
@@ -1595,75 +1579,39 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
   // later ones are fused into the captured update kernel
   if (mk) TANGO_TRY(launch_inpaint_blend0(dt, d_sched, B * HW, s));
 
-  if (chains == 2 && !ev_fork) {
+  if (mode == UNetMode::TwoChains && !ev_fork) {
     TANGO_HIP(hipStreamCreateWithFlags(&cap_stream2, hipStreamNonBlocking));
     TANGO_HIP(hipStreamCreateWithFlags(&aux_stream, hipStreamNonBlocking));
     for (hipEvent_t* e : {&ev_fork, &ev_join, &ev_fork_e, &ev_join_e}) TANGO_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
-  // one denoise step = UNet forward, fused CFG combine + scheduler update (writes the next UNet input), step counter++
-  // (two chains: fork after the previous step's update, join before this step's)
-  auto run_step = [&](hipStream_t st, hipStream_t st2, hipEvent_t ef, hipEvent_t ej) -> int {
-    if (chains != 2) {
-      TANGO_TRY(P->step.run(st));
-    } else {
-      TANGO_HIP(hipEventRecord(ef, st));
-      TANGO_HIP(hipStreamWaitEvent(st2, ef, 0));
-      TANGO_TRY(CA->step.run(st));
-      TANGO_TRY(CB->step.run(st2));
-      TANGO_HIP(hipEventRecord(ej, st2));
-      TANGO_HIP(hipStreamWaitEvent(st, ej, 0));
-    }
-    TANGO_TRY(launch_sched_step(dt, d_sched, B2 * HW, st, a.rule, mk));
-    return launch_step_inc(d_step, st);
-  };
-  // capture `n` steps once per plan; every per-step quantity is read through d_step / d_sched
-  // (captured on an engine-owned stream: the caller's stream may be the legacy null stream,
-  // which cannot be captured; the instantiated graph is then launched on the caller's stream)
-  auto capture = [&](int n, hipGraph_t* g_out, hipGraphExec_t* x_out) -> int {
-    if (!cap_stream) TANGO_HIP(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-    TANGO_HIP(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeRelaxed));
-    int rc = 0;
-    for (int i = 0; i < n && rc == 0; ++i) rc = run_step(cap_stream, cap_stream2, ev_fork, ev_join);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(cap_stream, &g);
-    if (rc != 0) return rc;
-    if (e != hipSuccess) TANGO_FAIL(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    *g_out = g;
-    TANGO_HIP(hipGraphInstantiate(x_out, g, nullptr, nullptr, 0));
-    return 0;
-  };
-  // the update kernel is fixed at capture: the multistep rule and masked calls replay graphs of their own
-  hipGraph_t& graph1 = mk ? P->graph_mk[ms] : ms ? P->graph_ms : P->graph;
-  hipGraphExec_t& exec1 = mk ? P->exec_mk[ms] : ms ? P->exec_ms : P->exec;
-  hipGraph_t& graphk = mk ? P->graph_k_mk[ms] : ms ? P->graph_k_ms : P->graph_k;
-  hipGraphExec_t& execk = mk ? P->exec_k_mk[ms] : ms ? P->exec_k_ms : P->exec_k;
-  int& ksteps = mk ? P->k_steps_mk[ms] : ms ? P->k_steps_ms : P->k_steps;
-  if (a.use_graph && !exec1) TANGO_TRY(capture(1, &graph1, &exec1));
+  // the update kernel is fixed at capture: each (masked, multistep) pair replays graphs of its own, captured once per plan
+  StepGraphs& G = P->graphs[mk][ms];
+  if (a.use_graph && !G.exec) TANGO_TRY(capture_steps(*P, a.rule, mk, 1, &G.graph, &G.exec));
   // k steps per replay (round 5; north_star: "the 100-200 denoise steps captured as a hipGraph"): the same kernel sequence captured k
   // times back to back -- every per-step quantity is read through the device-side step counter, so a k-step graph is just k copies.
   // What it removes is the host-side launch of every replay and the gap between two replays, which only shows at small batches
   // (B = 1: a 7-ms step); the remainder of num_steps / k runs on the one-step graph.
   int kk = tuning().graph_steps > 0 ? tuning().graph_steps : graph_steps_default(B2);
   if (kk > a.num_steps) kk = a.num_steps;
-  if (a.use_graph && kk > 1 && (!execk || ksteps != kk)) {
-    if (execk) { TANGO_HIP(hipStreamSynchronize(s)); (void)hipGraphExecDestroy(execk); (void)hipGraphDestroy(graphk); execk = nullptr; graphk = nullptr; }
-    TANGO_TRY(capture(kk, &graphk, &execk));
-    ksteps = kk;
+  if (a.use_graph && kk > 1 && (!G.exec_k || G.k_steps != kk)) {
+    if (G.exec_k) { TANGO_HIP(hipStreamSynchronize(s)); (void)hipGraphExecDestroy(G.exec_k); (void)hipGraphDestroy(G.graph_k); G.exec_k = nullptr; G.graph_k = nullptr; }
+    TANGO_TRY(capture_steps(*P, a.rule, mk, kk, &G.graph_k, &G.exec_k));
+    G.k_steps = kk;
   }
   TANGO_HIP(hipEventRecord(ev0, s));
   {
     int i = 0;
     if (a.use_graph && kk > 1)
-      for (; i + kk <= a.num_steps; i += kk) TANGO_HIP(hipGraphLaunch(execk, s));
+      for (; i + kk <= a.num_steps; i += kk) TANGO_HIP(hipGraphLaunch(G.exec_k, s));
     for (; i < a.num_steps; ++i) {
-      if (a.use_graph) TANGO_HIP(hipGraphLaunch(exec1, s));
-      else TANGO_TRY(run_step(s, aux_stream, ev_fork_e, ev_join_e));
+      if (a.use_graph) TANGO_HIP(hipGraphLaunch(G.exec, s));
+      else TANGO_TRY(run_step(*P, a.rule, mk, s, aux_stream, ev_fork_e, ev_join_e));
     }
   }
   TANGO_HIP(hipEventRecord(ev1, s));
   last_steps = a.num_steps;
   last_step_gflop = 0.0;
-  for (const UNetPlan* q : {chains != 2 ? (const UNetPlan*)P : (const UNetPlan*)CA, (const UNetPlan*)CB})
+  for (const UNetPlan* q : {(const UNetPlan*)P, (const UNetPlan*)P->child[0].get(), (const UNetPlan*)P->child[1].get()})
     if (q) for (double f : q->step.flops) last_step_gflop += f / 1e9;
   return 0;
 }
@@ -1693,7 +1641,7 @@ int Engine::profile_unet(int B2, int L, std::string& report, hipStream_t s) {
   // the product's CFG structure: the first half of the batch is the unconditional (single-key) half
   const int ns = (!tuning().no_single_key && B2 % 2 == 0) ? B2 / 2 : 0;
   // (and the plan denoise() would run for it: with the CFG-shared prefix where that applies)
-  TANGO_TRY(get_unet_plan(B2, L, cfg.unet_music ? 50 : 0, cfg.unet_music ? 20 : 0, ns, &P, cfg_shared_ok(B2, ns) ? 3 : 1));   // mustango/models.py:336,340: beat_len 50, chord_len 20
+  TANGO_TRY(get_unet_plan(B2, L, cfg.unet_music ? 50 : 0, cfg.unet_music ? 20 : 0, ns, &P, unet_mode_for(B2, ns, true, false)));   // mustango/models.py:336,340: beat_len 50, chord_len 20
   int64_t t = 500;
   TANGO_TRY(ensure_temb(&t, 1, s));
   TANGO_HIP(hipMemsetAsync(d_step, 0, 4, s));
@@ -1856,25 +1804,15 @@ int Engine::build_t5(T5Plan& P, Arena& A, bool record) {
 }
 
 int Engine::get_t5_plan(int B, int L, T5Plan** out) {
-  auto key = std::make_pair(B, L);
-  auto it = t5_plans.find(key);
-  if (it != t5_plans.end()) { touch(it->second->meta); *out = it->second.get(); return 0; }
-  if (!finalized) TANGO_FAIL("engine: weights not finalized");
-  std::unique_ptr<T5Plan> P(new T5Plan());
-  P->B = B; P->L = L;
-  Arena m;
-  TANGO_TRY(build_t5(*P, m, false));
-  TANGO_TRY(alloc_slab(&P->slab, m.peak + 256, P->meta, true));
-  Arena a; a.base = P->slab;
-  P->prog.ops.clear(); P->prog.labels.clear(); P->prog.flops.clear();
-  if (int rc = build_t5(*P, a, true)) { release_slab(&P->slab, P->meta); return rc; }
-  std::vector<int> bk((size_t)L * L);
-  for (int i = 0; i < L; ++i)
-    for (int j = 0; j < L; ++j) bk[(size_t)i * L + j] = t5_bucket(j - i, cfg.t5_rel_buckets, cfg.t5_rel_max_distance);
-  TANGO_HIP(hipMemcpy(P->bucket, bk.data(), bk.size() * 4, hipMemcpyHostToDevice));
-  *out = P.get();
-  t5_plans[key] = std::move(P);
-  return 0;
+  return get_plan<T5Plan>({PLAN_T5, B, L}, true, out, [&](T5Plan& P) { P.B = B; P.L = L; },
+                          [this](T5Plan& P, Arena& A, bool record) { return build_t5(P, A, record); },
+                          [&](T5Plan& P) {
+                            std::vector<int> bk((size_t)L * L);
+                            for (int i = 0; i < L; ++i)
+                              for (int j = 0; j < L; ++j) bk[(size_t)i * L + j] = t5_bucket(j - i, cfg.t5_rel_buckets, cfg.t5_rel_max_distance);
+                            TANGO_HIP(hipMemcpy(P.bucket, bk.data(), bk.size() * 4, hipMemcpyHostToDevice));
+                            return 0;
+                          });
 }
 
 int Engine::encode_text(const int64_t* ids, const uint8_t* mask, float* out, int B, int L, hipStream_t s) {
@@ -1950,20 +1888,8 @@ int Engine::build_vae(VaePlan& P, Arena& A, bool record) {
 }
 
 int Engine::get_vae_plan(int B, VaePlan** out) {
-  auto it = vae_plans.find(B);
-  if (it != vae_plans.end()) { touch(it->second->meta); *out = it->second.get(); return 0; }
-  if (!finalized) TANGO_FAIL("engine: weights not finalized");
-  std::unique_ptr<VaePlan> P(new VaePlan());
-  P->B = B;
-  Arena m;
-  TANGO_TRY(build_vae(*P, m, false));
-  TANGO_TRY(alloc_slab(&P->slab, m.peak + 256, P->meta, false));
-  Arena a; a.base = P->slab;
-  P->prog.ops.clear();
-  if (int rc = build_vae(*P, a, true)) { release_slab(&P->slab, P->meta); return rc; }
-  *out = P.get();
-  vae_plans[B] = std::move(P);
-  return 0;
+  return get_plan<VaePlan>({PLAN_VAE_DEC, B}, false, out, [&](VaePlan& P) { P.B = B; },
+                           [this](VaePlan& P, Arena& A, bool record) { return build_vae(P, A, record); });
 }
 
 int Engine::vae_decode(const float* lat, float* mel, int B, hipStream_t s) {
@@ -2042,20 +1968,8 @@ int Engine::build_vae_enc(VaePlan& P, Arena& A, bool record) {
 }
 
 int Engine::get_vae_enc_plan(int B, VaePlan** out) {
-  auto it = vae_enc_plans.find(B);
-  if (it != vae_enc_plans.end()) { touch(it->second->meta); *out = it->second.get(); return 0; }
-  if (!finalized) TANGO_FAIL("engine: weights not finalized");
-  std::unique_ptr<VaePlan> P(new VaePlan());
-  P->B = B;
-  Arena m;
-  TANGO_TRY(build_vae_enc(*P, m, false));
-  TANGO_TRY(alloc_slab(&P->slab, m.peak + 256, P->meta, false));
-  Arena a; a.base = P->slab;
-  P->prog.ops.clear();
-  if (int rc = build_vae_enc(*P, a, true)) { release_slab(&P->slab, P->meta); return rc; }
-  *out = P.get();
-  vae_enc_plans[B] = std::move(P);
-  return 0;
+  return get_plan<VaePlan>({PLAN_VAE_ENC, B}, false, out, [&](VaePlan& P) { P.B = B; },
+                           [this](VaePlan& P, Arena& A, bool record) { return build_vae_enc(P, A, record); });
 }
 
 int Engine::vae_encode(const float* mel, float* moments, int B, hipStream_t s) {
@@ -2091,16 +2005,19 @@ int Engine::build_voc(VaePlan& P, Arena& A, bool record, int frames) {
   P.out = A.alloc(P.out_bytes);
   const int d = dt;
 
-  auto conv1d = [&](const TView& x, int L, const WMat& w, int dil, const TView& out, const GOpt& o, bool i16 = false) {
+  // `rows` output rows per item gathered from x [B][Lin][Cin] through the taps of w, written to out [B][Lout][N]
+  auto gather1d = [&](const TView& x, int Lin, const WMat& w, int rows, const TView& out, int Lout) {
     GemmParams p;
     p.A = x.p; p.lda = x.ld; p.W = w.W; p.Kp = w.Kp; p.bias = w.b;
-    p.M = B * L; p.N = w.N; p.K = w.K; p.Cin = w.Cin;
-    p.mode = GATHER_1D; p.rows_pb = L; p.Lin = L; p.taps = w.taps; p.tap_step = dil; p.in_mul = 1;
-    p.in_off = -dil * (w.taps - 1) / 2;
-    p.Lout = L; p.out_mul = 1; p.out_off = 0;
-    p.out = out.p; p.ldo = out.ld;
-    if (o.residual) { p.R = o.residual->p; p.ldr = o.residual->ld; }
-    p.a_act = o.a_act; p.a_slope = o.a_slope; p.e_act = o.e_act; p.e_slope = o.e_slope;
+    p.M = B * rows; p.N = w.N; p.K = w.K; p.Cin = w.Cin;
+    p.mode = GATHER_1D; p.rows_pb = rows; p.Lin = Lin; p.taps = w.taps; p.in_mul = 1;
+    p.Lout = Lout; p.out = out.p; p.ldo = out.ld;
+    return p;
+  };
+  auto conv1d = [&](const TView& x, int L, const WMat& w, int dil, const TView& out, const GOpt& o, bool i16 = false) {
+    GemmParams p = gather1d(x, L, w, L, out, L);
+    p.tap_step = dil; p.in_off = -dil * (w.taps - 1) / 2;
+    b.apply(p, o);
     if (i16) { p.epi = EPI_I16; p.out_scale = 32768.0f; }
     b.gemm(p);
   };
@@ -2127,12 +2044,9 @@ int Engine::build_voc(VaePlan& P, Arena& A, bool record, int frames) {
       const int Q = qmax - qmin + 1;
       if (Q <= 0) continue;
       const WMat& w = ct.phase[r];
-      GemmParams p;
-      p.A = h.p; p.lda = h.ld; p.W = w.W; p.Kp = w.Kp; p.bias = w.b;
-      p.M = B * Q; p.N = w.N; p.K = w.K; p.Cin = w.Cin;
-      p.mode = GATHER_1D; p.rows_pb = Q; p.Lin = L; p.taps = w.taps; p.tap_step = -1; p.in_mul = 1; p.in_off = qmin;
-      p.Lout = Lo; p.out_mul = u; p.out_off = u * qmin + r - pd;
-      p.out = y.p; p.ldo = y.ld;
+      GemmParams p = gather1d(h, L, w, Q, y, Lo);
+      p.tap_step = -1; p.in_off = qmin;
+      p.out_mul = u; p.out_off = u * qmin + r - pd;
       b.gemm(p);
     }
     L = Lo; C = ct.cout;
@@ -2168,21 +2082,8 @@ int Engine::build_voc(VaePlan& P, Arena& A, bool record, int frames) {
 }
 
 int Engine::get_voc_plan(int B, int frames, VaePlan** out) {
-  auto key = std::make_pair(B, frames);
-  auto it = voc_plans.find(key);
-  if (it != voc_plans.end()) { touch(it->second->meta); *out = it->second.get(); return 0; }
-  if (!finalized) TANGO_FAIL("engine: weights not finalized");
-  std::unique_ptr<VaePlan> P(new VaePlan());
-  P->B = B;
-  Arena m;
-  TANGO_TRY(build_voc(*P, m, false, frames));
-  TANGO_TRY(alloc_slab(&P->slab, m.peak + 256, P->meta, false));
-  Arena a; a.base = P->slab;
-  P->prog.ops.clear();
-  if (int rc = build_voc(*P, a, true, frames)) { release_slab(&P->slab, P->meta); return rc; }
-  *out = P.get();
-  voc_plans[key] = std::move(P);
-  return 0;
+  return get_plan<VaePlan>({PLAN_VOC, B, frames}, false, out, [&](VaePlan& P) { P.B = B; },
+                           [&](VaePlan& P, Arena& A, bool record) { return build_voc(P, A, record, frames); });
 }
 
 int Engine::vocode(const float* mel, int16_t* wav, int B, int frames, int* n_samples, hipStream_t s) {

@@ -98,37 +98,27 @@ void Engine::build_stft_weights() {
 }
 
 int Engine::get_stft_plan(int B, int N, StftPlan** out) {
-  auto key = std::make_pair(B, N);
-  auto it = stft_plans.find(key);
-  if (it != stft_plans.end()) { touch(it->second->meta); *out = it->second.get(); return 0; }
-  if (!finalized) TANGO_FAIL("engine: weights not finalized");
   const int nfft = cfg.stft_filter_length, hop = cfg.stft_hop_length, cutoff = nfft / 2 + 1, nmel = cfg.stft_n_mel;
   const int P = nfft / 2;
-  if (N <= P) TANGO_FAIL("mel_spectrogram: reflect padding needs more than n_fft / 2 samples (F.pad raises the same way)");
-  std::unique_ptr<StftPlan> Pn(new StftPlan());
-  StftPlan& S = *Pn;
-  S.B = B; S.N = N; S.T = 1 + N / hop;
-  S.Np = (N + 2 * P + 3) / 4 * 4;
-  S.Kp2 = (cutoff + 15) / 16 * 16;
-  S.ldz = (2 * cutoff + 15) / 16 * 16;
-  Arena a;
-  auto carve = [&](Arena& A) {
-    S.in = (float*)A.alloc((size_t)B * N * 4);
-    S.xpad = (float*)A.alloc((size_t)B * S.Np * 4 + 64);
-    S.Z = (float*)A.alloc((size_t)B * S.T * S.ldz * 4);
-    S.mag = (float*)A.alloc((size_t)B * S.T * S.Kp2 * 4);
-    S.mel_lin = (float*)A.alloc((size_t)B * S.T * nmel * 4);
-    S.mel = (float*)A.alloc((size_t)B * nmel * S.T * 4);
-    S.logmag = (float*)A.alloc((size_t)B * cutoff * S.T * 4);
-    S.energy = (float*)A.alloc((size_t)B * S.T * 4);
-  };
-  carve(a);
-  TANGO_TRY(alloc_slab(&S.slab, a.peak + 256, S.meta, false));
-  Arena r; r.base = S.slab;
-  carve(r);
-  *out = Pn.get();
-  stft_plans[key] = std::move(Pn);
-  return 0;
+  return get_plan<StftPlan>({PLAN_STFT, B, N}, false, out,
+                            [&](StftPlan& S) {
+                              S.B = B; S.N = N; S.T = 1 + N / hop;
+                              S.Np = (N + 2 * P + 3) / 4 * 4;
+                              S.Kp2 = (cutoff + 15) / 16 * 16;
+                              S.ldz = (2 * cutoff + 15) / 16 * 16;
+                            },
+                            [&](StftPlan& S, Arena& A, bool) {     // buffers only: this plan records no program
+                              if (N <= P) TANGO_FAIL("mel_spectrogram: reflect padding needs more than n_fft / 2 samples (F.pad raises the same way)");
+                              S.in = (float*)A.alloc((size_t)B * N * 4);
+                              S.xpad = (float*)A.alloc((size_t)B * S.Np * 4 + 64);
+                              S.Z = (float*)A.alloc((size_t)B * S.T * S.ldz * 4);
+                              S.mag = (float*)A.alloc((size_t)B * S.T * S.Kp2 * 4);
+                              S.mel_lin = (float*)A.alloc((size_t)B * S.T * nmel * 4);
+                              S.mel = (float*)A.alloc((size_t)B * nmel * S.T * 4);
+                              S.logmag = (float*)A.alloc((size_t)B * cutoff * S.T * 4);
+                              S.energy = (float*)A.alloc((size_t)B * S.T * 4);
+                              return 0;
+                            });
 }
 
 int Engine::mel_spectrogram(const float* wav, float* mel, float* logmag, float* energy, int B, int N, int* n_frames, hipStream_t s) {
@@ -142,10 +132,7 @@ int Engine::mel_spectrogram(const float* wav, float* mel, float* logmag, float* 
   hipLaunchKernelGGL(reflect_pad_kernel, dim3((unsigned)((S.Np + 255) / 256), (unsigned)B), dim3(256), 0, s, S.in, S.xpad, N, nfft / 2, S.Np);
   TANGO_HIP(hipGetLastError());
   {  // frames x DFT basis: rows overlap (lda = hop < K = n_fft), one batch item per waveform
-    GemmParams p;
-    p.A = S.xpad; p.lda = hop; p.W = stft_basis.W; p.Kp = nfft;
-    p.M = S.T; p.N = 2 * cutoff; p.K = nfft; p.Cin = nfft;
-    p.mode = GATHER_1D; p.rows_pb = S.T; p.Lin = S.T; p.Lout = S.T; p.taps = 1;
+    GemmParams p = dense_gemm(S.xpad, hop, stft_basis.W, nfft, S.T, 2 * cutoff, nfft);
     p.out = S.Z; p.ldo = S.ldz;
     p.batch = B; p.sA = S.Np; p.sW = 0; p.sO = (int64_t)S.T * S.ldz;
     TANGO_TRY(launch_gemm(DT_F32, p, s));
@@ -153,10 +140,7 @@ int Engine::mel_spectrogram(const float* wav, float* mel, float* logmag, float* 
   hipLaunchKernelGGL(stft_mag_kernel, dim3((unsigned)(B * S.T)), dim3(256), 0, s, S.Z, (int64_t)S.ldz, S.mag, S.Kp2, S.energy, cutoff);
   TANGO_HIP(hipGetLastError());
   {
-    GemmParams p;
-    p.A = S.mag; p.lda = S.Kp2; p.W = stft_mel.W; p.Kp = S.Kp2;
-    p.M = B * S.T; p.N = nmel; p.K = S.Kp2; p.Cin = S.Kp2;
-    p.mode = GATHER_1D; p.rows_pb = p.M; p.Lin = p.M; p.Lout = p.M; p.taps = 1;
+    GemmParams p = dense_gemm(S.mag, S.Kp2, stft_mel.W, S.Kp2, B * S.T, nmel, S.Kp2);
     p.out = S.mel_lin; p.ldo = nmel;
     TANGO_TRY(launch_gemm(DT_F32, p, s));
   }

@@ -31,7 +31,7 @@ struct Tuning {
   bool gn_coop_all;         // TANGO_GN_COOP_ALL=1      tests: that kernel for every geometry it can hold, not only where it was measured faster
   bool gn_coop_force_fb;    // TANGO_GN_COOP_FORCE_FALLBACK=1 tests: every workgroup of that kernel takes the no-rendezvous fallback (bit-identical results required) (round 5)
   int graph_steps;          // TANGO_GRAPH_STEPS=k      denoise: k UNet steps per captured hipGraph (default 1 = one replay per step: measured, no inter-replay gap to remove) (round 5)
-  int unet_chains;          // TANGO_UNET_CHAINS=1|2    denoise: the UNet batch as one kernel sequence or as two independent halves in two branches of the captured graph (Engine::unet_chains_for; unset = the measured rule) (round 5)
+  int unet_chains;          // TANGO_UNET_CHAINS=1|2    denoise: the UNet batch as one kernel sequence or as two independent halves in two branches of the captured graph (Engine::unet_mode_for; unset = the measured rule) (round 5)
   bool no_cfg_shared;       // TANGO_NO_CFG_SHARED=1    A/B: the CFG-shared prefix of a guidance step (conv_in ... first self-attention once for both halves) off (round 5)
   bool stream_spec;         // TANGO_STREAM_SPEC=0|1     lin_stream_kernel: compile-time GEGLU + folded-LayerNorm epilogue for the level-0 projection (default on) (round 5)
   int attn_qb2_min_wgs;     // TANGO_ATTN_QB2_MIN_WGS=n attention with Sq <= 512: 32 query rows per wave once that still leaves n workgroups (default 512: level-2 self-attention at B=32 0.319 -> 0.247 ms, profiles/r4_c14_attn_qb2_ab_b32.txt); 0 = never (round 4)

@@ -398,3 +398,30 @@ def test_plan_cache_lru_budget():
     e.set_plan_budget(1)                           # a budget nothing fits into: the current call still gets its plan
     assert torch.equal(run(16), first[16])
     assert e.plan_stats()[1] == 1
+
+
+def test_plan_budget_is_shared_across_plan_kinds():
+    """One byte budget and one LRU order for every kind of plan: a new vocoder plan that does not fit evicts the least recently used
+    plan whatever its kind -- here the older vocoder plan, not the VAE plan that was touched after it -- and a plan rebuilt after
+    its eviction computes the same bits."""
+    e = Engine(vae=O.VAE_CONFIG, hifigan=O.HIFIGAN_CONFIG, dtype="fp16")
+    e.load_synthetic(1234)
+    g = torch.Generator().manual_seed(9)
+    lat = torch.randn(1, 8, 256, 16, generator=g).cuda()
+    mel128 = torch.randn(1, 1, 128, 64, generator=g).cuda()
+    mel64 = torch.randn(1, 1, 64, 64, generator=g).cuda()
+    dec = e.vae_decode(lat).cpu()                  # plan A
+    wav128 = e.vocode(mel128).cpu()                # plan B
+    assert torch.equal(e.vae_decode(lat).cpu(), dec)       # B is now the least recently used
+    used, n = e.plan_stats()
+    assert n == 2 and used > 0
+    e.set_plan_budget(used)
+    wav64 = e.vocode(mel64).cpu()                  # plan C, smaller than B: freeing B alone makes room
+    assert e.plan_stats()[1] == 2
+    e.set_plan_budget(64 << 30)                    # the default
+    assert torch.equal(e.vae_decode(lat).cpu(), dec)
+    assert e.plan_stats()[1] == 2                  # A survived
+    assert torch.equal(e.vocode(mel128).cpu(), wav128)
+    assert e.plan_stats()[1] == 3                  # B was the one dropped
+    assert torch.equal(e.vocode(mel64).cpu(), wav64)
+    assert e.plan_stats()[1] == 3

@@ -302,6 +302,24 @@ def test_state_isolation_unmasked_masked_unmasked(lib, rule):
     assert not torch.equal(a, mk)
 
 
+def test_every_step_graph_slot_of_one_plan_and_its_teardown(lib):
+    """One UNet plan holds a captured step graph per (masked, multistep) pair -- the two bits that fix the update kernel.  All four on
+    one engine, the k-step slot of plain DDPM re-captured when k changes (N = 5: a 2-step replay plus a remainder, and the multistep
+    table reaches order 3), then the plan is dropped with graphs in every slot and each combination computes the same bits again."""
+    e = Engine(unet=O.UNET_CONFIG_TINY, dtype="fp32")
+    e.load_synthetic(1234)
+    inputs = _inputs(N=5)
+    combos = [(rule, masked) for rule in ("ddpm", "dpmpp_2m") for masked in (False, True)]
+    first = {c: _engine_run(e, c[0], 5, inputs, masked=c[1], seed=5) for c in combos}
+    for k in (2, 3):
+        with tuning(lib, TANGO_GRAPH_STEPS=k):
+            assert torch.equal(_engine_run(e, "ddpm", 5, inputs, masked=False, seed=5), first[("ddpm", False)]), k
+    e.drop_plans()
+    assert e.plan_stats() == (0, 0)
+    for c in combos:
+        assert torch.equal(_engine_run(e, c[0], 5, inputs, masked=c[1], seed=5), first[c]), c
+
+
 # ---- 7. argument errors ------------------------------------------------------------------------------------------------------------
 def test_masked_argument_errors(lib):
     e = unet_engine("fp32")
