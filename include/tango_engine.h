@@ -212,7 +212,8 @@ int tango_engine_unet_forward_music(tango_engine_t* h, const float* sample, int6
 int tango_engine_vae_decode(tango_engine_t* h, const float* latents, float* mel, int batch, void* stream);
 /* AutoencoderKL.encode (autoencoder.py:52-58: Encoder.forward, modules.py:519-543, then quant_conv): mel [B, in_ch, 4H, 4W] fp32
  * NCHW (H, W = latent_h, latent_w for three levels) -> moments [B, 2*embed_dim, H, W] fp32 NCHW = [mean | logvar]; the posterior
- * (clamp, exp, sample: distributions.py:24-41) and scale_factor (autoencoder.py:126-135) are host-side code of the caller */
+ * (clamp, exp, sample: distributions.py:24-41) and scale_factor (autoencoder.py:126-135) are host-side code of the caller, or one
+ * launch of tango_op_latent_encode below */
 int tango_engine_vae_encode(tango_engine_t* h, const float* mel, float* moments, int batch, void* stream);
 /* mel [B,1,T,num_mels] fp32 -> int16 [B, samples]; returns samples per item via *n_samples (may be NULL) */
 int tango_engine_vocode(tango_engine_t* h, const float* mel, int16_t* wav, int batch, int mel_frames, int* n_samples, void* stream);
@@ -389,6 +390,32 @@ int tango_op_sched_masked(float* latents, const float* model_out_nchw, const flo
 /* the N(0,1) values the masked loop's device Philox generator uses as the blend noise n_step of loop index `step` (the step noise's
  * counter with bit 31 of the step word set): out fp32 [B, C, HW] */
 int tango_op_philox_normal_blend(float* out, int B, int C, int HW, int step, uint64_t seed, int sample_offset, void* stream);
+
+/* Fused latent encode of audio-to-audio editing (AudioLDM style_transfer, audioldm/pipeline.py:145-247): VAE moments -> the latents a
+ * truncated denoise loop starts from, in one launch, ASYNCHRONOUS on `stream` (no synchronise, no scratch).  For sample b:
+ *   lv = clamp(logvar, -30, 20); z = mean + exp(0.5 * lv) * eps     distributions.py:24-41 (posterior_mode 1: z = mean)
+ *   z  = scale * z                                                  autoencoder.py:126-135
+ *   if max over the sample of |z| > clip_trigger: z = clamp(z, -clip_range, clip_range)        pipeline.py:209-210 (1e2, 10)
+ *   xt = sa * z + sb * n                                            latent_diffusion/ddim.py:259-262 == the fork's add_noise
+ * each line in that multiply / add order without FMA contraction; exp is the only inexact operation.
+ * The clip condition is per sample: the reference takes the maximum over the whole tensor, but its only caller repeats one clip
+ * `batchsize` times, where the two agree -- and per sample the result does not depend on how a batch is split.
+ * moments: device fp32 [moments_batch, 2C, HW] = [mean | logvar]; moments_batch is B, or 1 (one clip fans out to B samples).
+ * xt_out: device fp32 [B, C, HW].  z0_out: the same shape or NULL: the clean scaled (clipped) latents, a masked edit's known_latents.
+ * eps, noise: device fp32 [B, C, HW], or NULL -> device Philox with the denoise loop's key (seed) and counter layout
+ *   (hw, c / 4, sample_offset + b, word) on two streams of their own, word = 0x40000000 | 0 (eps) and 0x40000000 | 1 (noise):
+ *   step noise has bits 31 and 30 of the word clear, blend noise has bit 31 set, so the four streams are disjoint while a loop has
+ *   fewer than 2^30 steps.  A Philox stream needs C % 4 == 0.  Any HW.
+ *   With noise NULL and sb == 0 (the posterior alone) no n is drawn: xt = sa * z, and C is not constrained by that stream.
+ * Errors: moments_batch not 1 or B, C % 4 != 0 with Philox, non-positive sizes. */
+int tango_op_latent_encode(const float* moments, int moments_batch, float* z0_out, float* xt_out, const float* eps, const float* noise,
+                           int B, int C, int HW, float scale, float clip_trigger, float clip_range, float sa, float sb,
+                           int posterior_mode, uint64_t seed, int sample_offset, void* stream);
+
+/* the N(0,1) values tango_op_latent_encode's device Philox generator draws for global samples [sample_offset, sample_offset + B):
+ * which = 0 the posterior's eps, 1 the forward noise n; out fp32 [B, C, HW].  Synchronises.
+ * Errors: out NULL, non-positive sizes, B * C * HW >= 2^31, which not 0 or 1. */
+int tango_op_philox_normal_encode(float* out, int B, int C, int HW, int which, uint64_t seed, int sample_offset, void* stream);
 
 #ifdef __cplusplus
 }

@@ -113,6 +113,7 @@ SYMBOLS = [
     "tango_op_conv_transpose1d", "tango_op_groupnorm", "tango_op_layernorm", "tango_op_attention", "tango_op_attention_ex", "tango_op_xattn_block",
     "tango_op_sched_step", "tango_op_sched_multistep", "tango_op_philox_normal",
     "tango_op_sched_masked", "tango_op_philox_normal_blend",
+    "tango_op_latent_encode", "tango_op_philox_normal_encode",
     "tango_op_conv2d_ex", "tango_op_gemm_batched", "tango_op_softmax_rows", "tango_op_conv1d_i16", "tango_op_avg3_act",
     "tango_op_pointwise_small", "tango_op_pointwise_out_nchw", "tango_debug_conv2d_route", "tango_debug_conv1d_route",
     "tango_debug_conv_transpose1d_phase",
@@ -184,6 +185,8 @@ def load():
     lib.tango_op_philox_normal.argtypes = [vp, ci, ci, ci, ci, C.c_uint64, ci, vp]
     lib.tango_op_philox_normal_blend.argtypes = [vp, ci, ci, ci, ci, C.c_uint64, ci, vp]
     lib.tango_op_sched_masked.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, C.c_uint64, ci, ci, ci, ci, ci, cf, ci, ci, vp]
+    lib.tango_op_latent_encode.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, ci, C.c_uint64, ci, vp]
+    lib.tango_op_philox_normal_encode.argtypes = [vp, ci, ci, ci, ci, C.c_uint64, ci, vp]
     lib.tango_op_conv2d_ex.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, vp]
     lib.tango_op_gemm_batched.argtypes = [ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, vp]
     lib.tango_op_softmax_rows.argtypes = [ci, vp, vp, ci, ci, cf, vp]

@@ -3,10 +3,16 @@
 `with_encoder=True`, `encode` / `encode_first_stage` / `get_first_stage_encoding` with the
 `DiagonalGaussianDistribution` posterior of distributions.py:24-41.  The mel front-end (STFT) is not part of this class.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
-from .engine import HIFIGAN_CONFIG, Engine
+from . import _lib
+from .engine import HIFIGAN_CONFIG, Engine, _stream_ptr
+
+#: AudioLDM style_transfer's guard against blown-up encodings (audioldm/pipeline.py:209-210): above the trigger, clamp to the range
+EDIT_CLIP_TRIGGER, EDIT_CLIP_RANGE = 1e2, 10.0
 
 
 class DiagonalGaussianDistribution:
@@ -79,6 +85,48 @@ class AutoencoderKL:
         else:
             raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
         return self.scale_factor * z
+
+    @torch.no_grad()
+    def encode_start_latents(self, moments, sa, sb, samples, posterior="sample", eps=None, noise=None, seed=0, sample_offset=0,
+                             want_clean=False):
+        """The start latents of an audio-to-audio edit in one fused launch (tango_op_latent_encode, include/tango_engine.h): from
+        the encoder's `moments` [K, 2C, H, W] (K = `samples`, or 1: one clip fans out to `samples` draws) the posterior sample
+        (`posterior="mode"`: its mean), times scale_factor, clamped to +-10 when a sample's largest magnitude exceeds 100
+        (pipeline.py:209-210), then the forward noising `sa * z + sb * n` with the scheduler's add_noise scalars at the encode
+        timestep (a row of blend_table(); sa = 1, sb = 0: no noising).  `eps` / `noise` [samples, C, H, W] inject the two draws;
+        by default both come from the device Philox generator under `seed` at global sample index `sample_offset` + row, so an
+        edit does not depend on how a batch is split.  Returns x_t [samples, C, H, W] fp32, or `(x_t, z)` with `want_clean`
+        (z: the clean scaled latents, the `known_latents` of a regional edit).  Asynchronous on the current stream."""
+        if posterior not in ("sample", "mode"):
+            raise ValueError("posterior must be 'sample' or 'mode', got %r" % (posterior,))
+        if not torch.is_tensor(moments) or moments.dim() != 4 or moments.shape[1] % 2:
+            raise ValueError("moments must be [K, 2C, H, W]")
+        B = int(samples)
+        if B < 1 or moments.shape[0] not in (1, B):
+            raise ValueError("moments hold %d clips: need 1 or samples = %d" % (moments.shape[0], B))
+        dev = self._device
+        mom = moments.detach().to(device=dev, dtype=torch.float32).contiguous()
+        Cc, H, Wd = mom.shape[1] // 2, mom.shape[2], mom.shape[3]
+        shape = (B, Cc, H, Wd)
+        given = []
+        for what, t in (("eps", eps), ("noise", noise)):
+            if t is not None:
+                if tuple(t.shape) != shape:
+                    raise ValueError("%s must be %s, got %s" % (what, shape, tuple(t.shape)))
+                t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+            given.append(t)
+        eps, noise = given
+        if (noise is None or (eps is None and posterior == "sample")) and Cc % 4:
+            raise ValueError("the device Philox generator draws four channels at a time: C = %d needs injected eps / noise" % Cc)
+        xt = torch.empty(shape, device=dev, dtype=torch.float32)
+        z0 = torch.empty(shape, device=dev, dtype=torch.float32) if want_clean else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        with torch.cuda.device(dev):
+            _lib.check(self.engine.lib.tango_op_latent_encode(
+                p(mom), mom.shape[0], p(z0), p(xt), p(eps), p(noise), B, Cc, H * Wd, float(self.scale_factor), EDIT_CLIP_TRIGGER,
+                EDIT_CLIP_RANGE, float(sa), float(sb), 1 if posterior == "mode" else 0, int(seed) & (2 ** 64 - 1), int(sample_offset),
+                _stream_ptr()), "latent_encode")
+        return (xt, z0) if want_clean else xt
 
     @torch.no_grad()
     def decode(self, z):

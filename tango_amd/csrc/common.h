@@ -415,6 +415,14 @@ int launch_step_inc(int* step_ptr, hipStream_t s);
 // test hook: the N(0,1) draws of sched_step at loop index `step` -> out fp32 [B][C][HW] (`blend`: the masked loop's blend noise)
 int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned long long seed, int sample_offset, hipStream_t s,
                          bool blend = false);
+// fused latent encode of audio-to-audio editing (elementwise.hip latent_encode_kernel): moments fp32 [moments_batch][2C][HW] ->
+// xt (and z0 when not null) fp32 [B][C][HW]; eps / noise injected [B][C][HW] or null -> Philox.  One workgroup per sample, any HW.
+int launch_latent_encode(const float* moments, int moments_batch, float* z0, float* xt, const float* eps, const float* noise, int B,
+                         int C, int HW, float scale, float clip_trigger, float clip_range, float sa, float sb, int posterior_mode,
+                         unsigned long long seed, int sample_offset, hipStream_t s);
+// test hook: the draws of the encode kernel's Philox streams (which: 0 eps, 1 n) -> out fp32 [B][C][HW]
+int launch_philox_normal_encode(float* out, int B, int C, int HW, int which, unsigned long long seed, int sample_offset,
+                                hipStream_t s);
 
 // latents fp32 NCHW [B,C,HW] -> T NHWC [rep*B, HW, ld] (replicated `rep` times along batch), zero-pads C..ld? no: writes C channels
 int launch_nchw_to_nhwc(int dtype, const float* src, void* dst, int64_t ld, int B, int C, int HW, int rep, float scale, hipStream_t s);

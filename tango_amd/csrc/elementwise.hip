@@ -156,6 +156,127 @@ int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned lo
 }
 
 // ------------------------------------------------------------------------------------------
+// Fused latent encode of audio-to-audio editing (AudioLDM style_transfer, audioldm/pipeline.py:145-247): VAE moments
+// [Bm][2C][HW] = [mean | logvar] -> the latents the truncated loop starts from, one launch.  Per element, each line in the
+// reference's unfused multiply / add order (FMA contraction off):
+//   lv = clamp(logvar, -30, 20); z = mean + exp(0.5 * lv) * eps    distributions.py:24-41 (posterior mode: z = mean)
+//   z  = scale * z                                                 autoencoder.py:126-135 get_first_stage_encoding
+//   if max over the sample |z| > clip_trigger: z = clamp(z, -clip_range, clip_range)          pipeline.py:209-210
+//   xt = sa * z + sb * n                                           latent_diffusion/ddim.py:259-262 == the fork's add_noise
+// The clip condition is PER SAMPLE.  The reference takes torch.max over the whole tensor, but its only caller repeats one clip
+// `batchsize` times (pipeline.py:203-206), where the two definitions agree; per sample, the result does not depend on what else is in
+// the batch or on how a batch is split.
+// One workgroup per sample, two passes over its C * HW values: pass 1 computes z and reduces max |z| (wave shuffle, then LDS),
+// pass 2 recomputes z -- the same instructions on the same inputs, hence the same bits -- clips and writes.  Recomputing costs
+// a second read of the moments (256 KB per sample at the engine's size, L2-resident) and keeps the kernel free of a size limit.
+// eps / n: injected [B][C][HW] or null -> philox_normal4 with bit 30 of the step word set (word 0 eps, word 1 n): disjoint from
+// the step noise (bits 31, 30 clear) and from the blend noise (bit 31 set) while a loop has fewer than 2^30 steps.
+// With sb == 0 and no injected n the second stream is not drawn at all (xt = sa * z + 0).
+// Bm == 1: every sample reads clip 0's moments (one clip fans out to B samples with different draws).
+// ------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ int encode_step_word(int which) { return (int)(0x40000000u | (unsigned)which); }
+
+struct LatentEncodeParams {
+  const float* moments; float* z0; float* xt; const float* eps; const float* noise;
+  int B, C, HW, moments_batch;
+  float scale, clip_trigger, clip_range, sa, sb;
+  int posterior_mode, sample_offset;
+  unsigned long long seed;
+};
+
+// scale * posterior value of channel c at hw of the sample whose moments start at mom; e = the eps draw (unused in mode)
+__device__ __forceinline__ float encode_z(const float* __restrict__ mom, int C, int HW, int c, int hw, float e, bool mode,
+                                          float scale) {
+#pragma clang fp contract(off)
+  const float mean = mom[(int64_t)c * HW + hw];
+  float z = mean;
+  if (!mode) {
+    const float lv = fminf(fmaxf(mom[(int64_t)(C + c) * HW + hw], -30.0f), 20.0f);
+    const float h = 0.5f * lv;
+    const float sd = expf(h);
+    const float t = sd * e;
+    z = mean + t;
+  }
+  return scale * z;
+}
+
+constexpr int kEncodeThreads = 1024;
+__global__ __launch_bounds__(kEncodeThreads) void latent_encode_kernel(const LatentEncodeParams p) {
+#pragma clang fp contract(off)
+  __shared__ float red[kEncodeThreads / 64];
+  const int b = blockIdx.x;
+  const int C = p.C, HW = p.HW;
+  const bool mode = p.posterior_mode != 0;
+  const float* mom = p.moments + (p.moments_batch == 1 ? (int64_t)0 : (int64_t)b * 2 * C * HW);
+  const int64_t base = (int64_t)b * C * HW;
+  const int items = ((C + 3) >> 2) * HW;          // one item = 4 channels of one position (one Philox call per stream)
+  const bool eps_philox = !mode && !p.eps;
+  const bool n_philox = !p.noise && p.sb != 0.f;   // sb == 0 (the posterior alone, e.g. before an inversion): no draw, n = 0
+  float amax = 0.f;
+  for (int i = threadIdx.x; i < items; i += kEncodeThreads) {
+    const int c4 = i / HW, hw = i - c4 * HW;
+    float e[4] = {0.f, 0.f, 0.f, 0.f};
+    if (eps_philox) philox_normal4(hw, c4, p.sample_offset + b, encode_step_word(0), p.seed, e);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = 4 * c4 + k;
+      if (c < C) {
+        const float ev = (!mode && p.eps) ? p.eps[base + (int64_t)c * HW + hw] : e[k];
+        amax = fmaxf(amax, fabsf(encode_z(mom, C, HW, c, hw, ev, mode, p.scale)));
+      }
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
+  __syncthreads();
+  float smax = red[0];
+  for (int w = 1; w < kEncodeThreads / 64; ++w) smax = fmaxf(smax, red[w]);
+  const bool clip = smax > p.clip_trigger;
+  for (int i = threadIdx.x; i < items; i += kEncodeThreads) {
+    const int c4 = i / HW, hw = i - c4 * HW;
+    float e[4] = {0.f, 0.f, 0.f, 0.f}, n[4] = {0.f, 0.f, 0.f, 0.f};
+    if (eps_philox) philox_normal4(hw, c4, p.sample_offset + b, encode_step_word(0), p.seed, e);
+    if (n_philox) philox_normal4(hw, c4, p.sample_offset + b, encode_step_word(1), p.seed, n);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = 4 * c4 + k;
+      if (c < C) {
+        const int64_t o = base + (int64_t)c * HW + hw;
+        const float ev = (!mode && p.eps) ? p.eps[o] : e[k];
+        float z = encode_z(mom, C, HW, c, hw, ev, mode, p.scale);
+        if (clip) z = fminf(fmaxf(z, -p.clip_range), p.clip_range);
+        const float nv = p.noise ? p.noise[o] : n[k];
+        const float t0 = p.sa * z; const float t1 = p.sb * nv;
+        p.xt[o] = t0 + t1;
+        if (p.z0) p.z0[o] = z;
+      }
+    }
+  }
+}
+
+int launch_latent_encode(const float* moments, int moments_batch, float* z0, float* xt, const float* eps, const float* noise, int B,
+                         int C, int HW, float scale, float clip_trigger, float clip_range, float sa, float sb, int posterior_mode,
+                         unsigned long long seed, int sample_offset, hipStream_t s) {
+  LatentEncodeParams p;
+  p.moments = moments; p.z0 = z0; p.xt = xt; p.eps = eps; p.noise = noise;
+  p.B = B; p.C = C; p.HW = HW; p.moments_batch = moments_batch;
+  p.scale = scale; p.clip_trigger = clip_trigger; p.clip_range = clip_range; p.sa = sa; p.sb = sb;
+  p.posterior_mode = posterior_mode; p.sample_offset = sample_offset; p.seed = seed;
+  hipLaunchKernelGGL(latent_encode_kernel, dim3((unsigned)B), dim3(kEncodeThreads), 0, s, p);
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+// test hook: the draws of latent_encode_kernel's two Philox streams (which: 0 eps, 1 n), in philox_normal_kernel's layout
+int launch_philox_normal_encode(float* out, int B, int C, int HW, int which, unsigned long long seed, int sample_offset,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)((B * HW + 255) / 256)), dim3(256), 0, s, out, B, C, HW,
+                     encode_step_word(which), seed, sample_offset);
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // Fused CFG combine + multistep DPM-Solver / DPM-Solver++ update (rule 2; fork
 // mustango/diffusers/src/diffusers/schedulers/scheduling_dpmsolver_multistep.py:220-495).  One thread per (sample, position),
 // 8 channels.  Every scalar comes from the host table row (tango_amd/scheduler.py DPMSolverMultistepScheduler.coef_table,

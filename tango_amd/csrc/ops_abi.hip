@@ -938,4 +938,31 @@ int tango_op_sched_masked(float* latents, const float* model_out_nchw, const flo
   return 0;
 }
 
+int tango_op_latent_encode(const float* moments, int moments_batch, float* z0_out, float* xt_out, const float* eps, const float* noise,
+                           int B, int C, int HW, float scale, float clip_trigger, float clip_range, float sa, float sb,
+                           int posterior_mode, uint64_t seed, int sample_offset, void* stream) {
+  if (B <= 0 || C <= 0 || HW <= 0 || sample_offset < 0) TANGO_FAIL("op_latent_encode: bad sizes");
+  if ((int64_t)B * 2 * C * HW >= ((int64_t)1 << 31)) TANGO_FAIL("op_latent_encode: B * 2C * HW must stay below 2^31");
+  if (!moments || !xt_out) TANGO_FAIL("op_latent_encode: moments and xt_out are required");
+  if (moments_batch != 1 && moments_batch != B) TANGO_FAIL("op_latent_encode: moments_batch must be 1 or B");
+  if (posterior_mode != 0 && posterior_mode != 1) TANGO_FAIL("op_latent_encode: posterior_mode must be 0 (sample) or 1 (mode)");
+  const bool philox = (posterior_mode == 0 && !eps) || (!noise && sb != 0.f);        // sb == 0: the kernel draws no n
+  if (philox && C % 4 != 0) TANGO_FAIL("op_latent_encode: the Philox streams draw four channels at a time: C must be a multiple of 4");
+  if (!(clip_range >= 0.f)) TANGO_FAIL("op_latent_encode: clip_range must be >= 0");
+  TANGO_TRY(launch_latent_encode(moments, moments_batch, z0_out, xt_out, eps, noise, B, C, HW, scale, clip_trigger, clip_range, sa, sb,
+                                 posterior_mode, seed, sample_offset, (hipStream_t)stream));
+  return 0;
+}
+
+int tango_op_philox_normal_encode(float* out, int B, int C, int HW, int which, uint64_t seed, int sample_offset, void* stream) {
+  if (which != 0 && which != 1) TANGO_FAIL("op_philox_normal_encode: which must be 0 (eps) or 1 (noise)");
+  if (!out) TANGO_FAIL("op_philox_normal_encode: out is required");
+  if (B <= 0 || C <= 0 || HW <= 0 || sample_offset < 0) TANGO_FAIL("op_philox_normal_encode: bad sizes");
+  if ((int64_t)B * C * HW >= ((int64_t)1 << 31)) TANGO_FAIL("op_philox_normal_encode: B * C * HW must stay below 2^31");
+  hipStream_t s = (hipStream_t)stream;
+  TANGO_TRY(launch_philox_normal_encode(out, B, C, HW, which, seed, sample_offset, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 }  // extern "C"

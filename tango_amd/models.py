@@ -15,7 +15,7 @@ import torch
 
 from .engine import Engine, normalize_unet_config
 from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler  # noqa: F401  (re-exported like `from models import DDPMScheduler`)
-from .scheduler import from_diffusers
+from .scheduler import DDIMInverseScheduler, from_diffusers
 
 _TEXT_BUCKETS = (16, 32, 64, 128, 256, 512)
 
@@ -216,17 +216,24 @@ class AudioDiffusion:
         return pe, pm, mask_host
 
     def _denoise(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
-                 sample_offset, mask_host=None, known_latents=None, latent_mask=None, blend_noise=None, **extra_conditions):
+                 sample_offset, mask_host=None, known_latents=None, latent_mask=None, blend_noise=None, start=0, count=None,
+                 **extra_conditions):
         """the shared body of the loop of models.py:224-249 / mustango/models.py:563-598: seed derivation, text bucketing, scheduler
         tables, one engine call (`extra_conditions`: the Music UNet's beat / chord streams; `known_latents` / `latent_mask` /
-        `blend_noise`: the masked loop of audioldm/ldm.py:724-818, Engine.denoise)"""
+        `blend_noise`: the masked loop of audioldm/ldm.py:724-818, Engine.denoise).  `start` > 0: the truncated loop of an edit over
+        `timesteps[start:]` with the scheduler's truncated tables; `count`: the first `count` steps of a DDIMInverseScheduler."""
         cfg_on = guidance_scale > 1.0
         B = prompt_embeds.shape[0] // 2 if cfg_on else prompt_embeds.shape[0]
         if not hasattr(inference_scheduler, "coef_table"):
             # a diffusers / fork scheduler object (the reference's loop takes any): the engine's class of the same name and config
             inference_scheduler = from_diffusers(inference_scheduler)
         inference_scheduler.set_timesteps(num_steps, device=self.device)
-        timesteps = inference_scheduler.timesteps
+        if count is not None:
+            timesteps, coef, window = inference_scheduler.timesteps[:count], inference_scheduler.coef_table(count=count), {}
+        elif start:
+            timesteps, coef, window = inference_scheduler.timesteps[start:], inference_scheduler.coef_table(start=start), dict(start=start)
+        else:
+            timesteps, coef, window = inference_scheduler.timesteps, inference_scheduler.coef_table(), {}
         if latents is None:
             latents = self.prepare_latents(B, inference_scheduler, self.unet.config.in_channels, torch.float32, self.device)
         latents = latents.to(self.device, torch.float32).contiguous().clone()
@@ -242,11 +249,11 @@ class AudioDiffusion:
         self._calls += 1
         masking = {}
         if known_latents is not None or latent_mask is not None:
-            masking = dict(known_latents=known_latents, latent_mask=latent_mask, blend_coef=inference_scheduler.blend_table(),
+            masking = dict(known_latents=known_latents, latent_mask=latent_mask, blend_coef=inference_scheduler.blend_table(**window),
                            blend_noise=blend_noise)
         elif blend_noise is not None:
             raise ValueError("blend_noise needs known_latents and latent_mask")
-        self.engine.denoise(latents, pe, pm, timesteps.cpu().numpy(), inference_scheduler.coef_table(), guidance_scale,
+        self.engine.denoise(latents, pe, pm, timesteps.cpu().numpy(), coef, guidance_scale,
                             prediction_type=c.prediction_type, rule=inference_scheduler.rule, clip_sample=c.clip_sample,
                             clip_sample_range=getattr(c, "clip_sample_range", 1.0), noise=noise, seed=seed,
                             sample_offset=sample_offset, use_graph=self.use_graph, prompt_mask_host=mask_host, **masking,
@@ -307,6 +314,69 @@ class AudioDiffusion:
                                             known_latents=known_latents.repeat_interleave(S, 0),
                                             latent_mask=latent_mask.repeat_interleave(S, 0), mask_host=host)
 
+    # ---- audio-to-audio editing (audioldm/pipeline.py:145-247 style_transfer; latent_diffusion/ddim.py:246-304) ------------------
+    @torch.no_grad()
+    def edit_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
+                             start_latents, strength, known_latents=None, latent_mask=None, noise=None, blend_noise=None, seed=None,
+                             sample_offset=0, mask_host=None):
+        """The last k = int(strength * num_steps) steps of the loop of inference_from_embeddings, from `start_latents` [B, 8, 256,
+        16]: an existing clip's latents noised (AutoencoderKL.encode_start_latents) or inverted (invert_from_embeddings) to the
+        level `inference_scheduler.edit_plan(num_steps, strength)` names.  The engine runs `timesteps[start:]` with the scheduler's
+        truncated tables; the multistep DPM-Solver restarts its order ramp at the first executed step.  `noise` / `blend_noise`
+        hold one entry per EXECUTED step ([k, B, 8, 256, 16]).  With `known_latents` / `latent_mask` it is a regional edit: the
+        region where the mask is 1 keeps the clip's audio (the masked loop of inpaint_from_embeddings), the rest is edited."""
+        if not hasattr(inference_scheduler, "coef_table"):
+            inference_scheduler = from_diffusers(inference_scheduler)
+        if start_latents is None:
+            raise ValueError("an edit starts from start_latents")
+        start, _ = inference_scheduler.edit_plan(num_steps, strength)
+        return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, start_latents, noise,
+                             seed, sample_offset, mask_host=mask_host, known_latents=known_latents, latent_mask=latent_mask,
+                             blend_noise=blend_noise, start=start)
+
+    @torch.no_grad()
+    def edit(self, prompt, start_latents, inference_scheduler, num_steps=20, guidance_scale=3, strength=0.5, num_samples_per_prompt=1,
+             known_latents=None, latent_mask=None, seed=None):
+        """edit_from_embeddings() for prompt strings, encoded like inference() / inpaint(): `start_latents` (and `known_latents`
+        / `latent_mask` when given) hold one row per prompt and sample, row k * S + j for sample j of prompt k."""
+        S = num_samples_per_prompt
+        if start_latents.shape[0] != len(prompt) * S:
+            raise ValueError("start_latents need one row per prompt and sample (%d), got %d" % (len(prompt) * S, start_latents.shape[0]))
+        host = None
+        if guidance_scale > 1.0:
+            pe, pm, host = self._encode_text_classifier_free(prompt, S)
+        else:
+            pe, pm = self.encode_text(prompt)
+            pe = pe.repeat_interleave(S, 0)
+            pm = pm.repeat_interleave(S, 0)
+        return self.edit_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, start_latents=start_latents,
+                                         strength=strength, known_latents=known_latents, latent_mask=latent_mask, seed=seed,
+                                         mask_host=host)
+
+    @torch.no_grad()
+    def invert_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, *, latents, count,
+                               guidance_scale=1.0, mask_host=None):
+        """DDIM inversion, the deterministic encoder of an edit: `count` steps of DDIMInverseScheduler (ascending timesteps, the
+        inverse coefficient table, no step noise) from clean `latents` through the same fused loop, under the text the clip is
+        described by (`guidance_scale` 1: no CFG, `prompt_embeds` hold the B conditional rows only).  `inference_scheduler`: a
+        DDIMInverseScheduler, or a sampler: the inverse scheduler is then built on its noise schedule and walks its timesteps
+        upward (DDIMInverseScheduler.from_scheduler), so that after `count` = k steps the latents sit exactly on the sampler's
+        `edit_plan(num_steps, k / num_steps)` encode timestep `timesteps[num_steps - k - 1]`, DDIM and DPM-Solver alike.  A bare
+        DDIMInverseScheduler keeps the fork's grid `arange(0, n) * ratio + steps_offset` and lands on its own `timesteps[k]`."""
+        inv = _inverse_scheduler(inference_scheduler)
+        if latents is None:
+            raise ValueError("inversion starts from the clip's clean latents")
+        return self._denoise(prompt_embeds, boolean_prompt_mask, inv, num_steps, guidance_scale, latents, None, 0, 0,
+                             mask_host=mask_host, count=int(count))
+
+
+def _inverse_scheduler(scheduler):
+    if not hasattr(scheduler, "coef_table"):
+        scheduler = from_diffusers(scheduler)
+    if isinstance(scheduler, DDIMInverseScheduler):
+        return scheduler
+    return DDIMInverseScheduler.from_scheduler(scheduler)
+
 
 class MusicAudioDiffusion(AudioDiffusion):
     """Inference side of Mustango's `MusicAudioDiffusion` (mustango/models.py:312-740) on the engine: the UNet is
@@ -346,6 +416,42 @@ class MusicAudioDiffusion(AudioDiffusion):
                                               latents, noise, seed, sample_offset, encoded_beats=encoded_beats, beat_mask=beat_mask,
                                               encoded_chords=encoded_chords, chord_mask=chord_mask, known_latents=known_latents,
                                               latent_mask=latent_mask, blend_noise=blend_noise)
+
+    @staticmethod
+    def _need_music(encoded_beats, encoded_chords):
+        if encoded_beats is None or encoded_chords is None:
+            raise ValueError("encoded_beats and encoded_chords are required (mustango/models.py:548-550)")
+
+    @torch.no_grad()
+    def edit_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
+                             start_latents, strength, known_latents=None, latent_mask=None, noise=None, blend_noise=None, seed=None,
+                             sample_offset=0, encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None):
+        """AudioDiffusion.edit_from_embeddings with the beat / chord streams of inference_from_embeddings"""
+        if not hasattr(inference_scheduler, "coef_table"):
+            inference_scheduler = from_diffusers(inference_scheduler)
+        if start_latents is None:
+            raise ValueError("an edit starts from start_latents")
+        start, _ = inference_scheduler.edit_plan(num_steps, strength)
+        self._need_music(encoded_beats, encoded_chords)
+        return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, start_latents, noise,
+                             seed, sample_offset, known_latents=known_latents, latent_mask=latent_mask, blend_noise=blend_noise,
+                             start=start,
+                             beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
+
+    @torch.no_grad()
+    def invert_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, *, latents, count,
+                               guidance_scale=1.0, encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None):
+        """AudioDiffusion.invert_from_embeddings with the beat / chord streams of inference_from_embeddings"""
+        if latents is None:
+            raise ValueError("inversion starts from the clip's clean latents")
+        self._need_music(encoded_beats, encoded_chords)
+        return self._denoise(prompt_embeds, boolean_prompt_mask, _inverse_scheduler(inference_scheduler), num_steps, guidance_scale,
+                             latents, None, 0, 0, count=int(count),
+                             beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
+
+    def edit(self, *a, **k):
+        raise NotImplementedError("strings / beat and chord annotations are encoded by the caller's Mustango front-end modules; "
+                                  "pass their outputs to edit_from_embeddings()")
 
     def inpaint(self, *a, **k):
         raise NotImplementedError("strings / beat and chord annotations are encoded by the caller's Mustango front-end modules; "

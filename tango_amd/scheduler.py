@@ -8,6 +8,7 @@ the integer timestep schedule (bit-exact requirement) and the per-step fp32 coef
 kernel consumes.  Tables are computed with torch fp32 CPU ops in the reference's own order
 (`linspace(sqrt(b0), sqrt(b1), T)**2`, `cumprod`) so the scalars are bit-identical to the reference's.
 """
+import copy
 from types import SimpleNamespace
 
 import numpy as np
@@ -42,14 +43,38 @@ class _AddNoise:
             sb = sb.unsqueeze(-1)
         return sa * original_samples + sb * noise
 
-    def blend_table(self) -> np.ndarray:
-        """[N, 2] fp32: add_noise's scalars sqrt(abar_t), sqrt(1 - abar_t) at every set timestep (the masked loop's blend,
-        include/tango_engine.h tango_denoise_args_t.blend_coef)"""
+    def blend_table(self, start=0) -> np.ndarray:
+        """[N - start, 2] fp32: add_noise's scalars sqrt(abar_t), sqrt(1 - abar_t) at the set timesteps from index `start` on (the
+        masked loop's blend, include/tango_engine.h tango_denoise_args_t.blend_coef; start > 0: a truncated loop, edit_plan())"""
         if self.num_inference_steps is None:
             raise ValueError("call set_timesteps() before blend_table()")
-        t = torch.as_tensor(self.timesteps).to(torch.int64)
+        start = self._check_start(start)
+        t = torch.as_tensor(self.timesteps).to(torch.int64)[start:]
         ac = self.alphas_cumprod.to(torch.float32)
         return torch.stack([ac[t] ** 0.5, (1 - ac[t]) ** 0.5], 1).numpy().astype(np.float32)
+
+    def _check_start(self, start):
+        n = len(self.timesteps)
+        if int(start) != start or not 0 <= start < n:
+            raise ValueError("start must be an index into the %d set timesteps, got %r" % (n, start))
+        return int(start)
+
+    def edit_plan(self, num_steps, strength):
+        """Audio-to-audio editing (AudioLDM style_transfer, audioldm/pipeline.py:211-239): of a schedule of `num_steps` steps only the
+        last k = int(strength * num_steps) run (pipeline.py:214 t_enc), from the clip's latents noised part of the way.  Sets the
+        timesteps and returns `(start, encode_timestep)`: the loop executes `timesteps[start:]` (with `coef_table(start=start)` /
+        `blend_table(start=start)`), start = num_steps - k, and the clip is noised to `encode_timestep = timesteps[start - 1]`.
+
+        That is the reference's convention, kept as it is: DDIMSampler.stochastic_encode noises to the ASCENDING index t_enc = k
+        (latent_diffusion/ddim.py:246-262) while DDIMSampler.decode runs the ascending entries [:t_enc], the first of them one
+        entry lower (ddim.py:280) -- the start latents carry one step more noise than the first executed timestep says.
+        k = 0 would run nothing; k = num_steps indexes one past the schedule in the reference; both raise ValueError."""
+        k = int(strength * num_steps)
+        if not 1 <= k <= num_steps - 1:
+            raise ValueError("strength %r of %d steps runs k = %d steps; an edit needs 1 <= k <= %d" % (strength, num_steps, k, num_steps - 1))
+        self.set_timesteps(num_steps)
+        start = num_steps - k
+        return start, int(self.timesteps[start - 1])
 
 
 class _SchedulerBase(_AddNoise):
@@ -124,10 +149,11 @@ class DDPMScheduler(_SchedulerBase):
             raise NotImplementedError("variance_type %s" % self.variance_type)
         return var
 
-    def coef_table(self) -> np.ndarray:
-        """[N, 8] fp32: sqrt(abar_t), sqrt(1-abar_t), coef_x0, coef_xt, sigma (0 at t == 0), 0, 0, 0"""
+    def coef_table(self, start=0) -> np.ndarray:
+        """[N - start, 8] fp32: sqrt(abar_t), sqrt(1-abar_t), coef_x0, coef_xt, sigma (0 at t == 0), 0, 0, 0 for the set timesteps
+        from index `start` on (a one-step rule: the truncated table is rows start: of the full one)"""
         rows = []
-        for t in self.timesteps.tolist():
+        for t in self.timesteps.tolist()[self._check_start(start):]:
             prev_t = self._prev(t)
             a_t = self.alphas_cumprod[t]
             a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.one
@@ -160,15 +186,16 @@ class DDIMScheduler(_SchedulerBase):
     def set_timesteps(self, num_inference_steps, device=None):
         self.timesteps = torch.from_numpy(self._base_timesteps(num_inference_steps)) + self.config.steps_offset
 
-    def coef_table(self, eta=None) -> np.ndarray:
+    def coef_table(self, eta=None, start=0) -> np.ndarray:
         """per-step coefficients of the fused update; `eta` overrides the constructor's value for this table (the fork passes eta to
-        every step() call, scheduling_ddim.py:238: here the loop is one engine call, so it is a per-table argument)"""
+        every step() call, scheduling_ddim.py:238: here the loop is one engine call, so it is a per-table argument); `start`: rows
+        start: only (a truncated loop, edit_plan())"""
         eta = self.eta if eta is None else float(eta)
         if eta < 0:
             raise ValueError("eta must be >= 0")
         rows = []
         T = self.config.num_train_timesteps
-        for t in self.timesteps.tolist():
+        for t in self.timesteps.tolist()[self._check_start(start):]:
             prev_t = t - T // self.num_inference_steps
             a_t = self.alphas_cumprod[t]
             a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
@@ -178,6 +205,102 @@ class DDIMScheduler(_SchedulerBase):
             direction = (1 - a_prev - std ** 2) ** 0.5                       # :340
             rows.append([float(a_t ** 0.5), float(b_t ** 0.5), 0.0, 0.0, float(std), float(a_prev ** 0.5), float(direction), 0.0])
         return np.asarray(rows, dtype=np.float32)
+
+
+class DDIMInverseScheduler(_SchedulerBase):
+    """DDIM inversion after the fork's scheduling_ddim_inverse.py:25-268: the deterministic encoder of an edit.  The timesteps
+    ASCEND (`arange(0, n) * ratio + steps_offset`, :186-208) and step() (:210-265) is the DDIM update with the NEXT abar where the
+    sampler has the previous one: prev = sqrt(abar_next) * x0 + sqrt(1 - abar_next) * eps.  That is the `rule != 0` branch of the
+    engine's fused step with sigma = 0, so inversion runs through Engine.denoise with `rule = "ddim"` and this class's table: no
+    kernel of its own.  Past the last training timestep abar_next is `final_alpha_cumprod`: 0 with `set_alpha_to_zero` (the step
+    then returns the predicted noise), else abar of the last training timestep (:157-162).
+
+    Built on a sampler (`from_scheduler`), the grid is the SAMPLER's own, walked upward: entry 0 is the clean level (the sampler's
+    `steps_offset`, 0 where it has none) and entry j >= 1 is `sampler.timesteps[N - 1 - j]`, so that k steps from clean latents
+    land exactly on `sampler.edit_plan(N, k / N)`'s encode timestep `timesteps[N - k - 1]`.  For a DDIMScheduler that is the
+    fork's grid above, entry for entry.  The multistep DPM-Solver's timesteps are linspace-spaced and end one spacing above the
+    clean level 0 (N = 20: 999 ... 100, 50, then 0), so its inverse grid is 0, 100, 150, ...: the first inverse step spans two
+    of the sampler's spacings, every later one spans one."""
+    rule = "ddim"
+    _sampler = None
+
+    def __init__(self, set_alpha_to_zero=True, steps_offset=0, **kw):
+        kw.pop("set_alpha_to_one", None)                  # a sampler's config (from_scheduler): not this class's switch
+        kw.pop("eta", None)
+        super().__init__(set_alpha_to_zero=set_alpha_to_zero, steps_offset=steps_offset, **kw)
+        self.final_alpha_cumprod = torch.tensor(0.0) if set_alpha_to_zero else self.alphas_cumprod[-1]
+        self.timesteps = torch.from_numpy(np.arange(0, self.config.num_train_timesteps).copy().astype(np.int64))
+
+    @classmethod
+    def from_scheduler(cls, scheduler, **override):
+        """the inverse scheduler on the noise schedule of a sampler (`scheduler.config`: betas, prediction type, steps_offset)"""
+        items = dict(vars(scheduler.config))
+        accepted = _init_params(cls)
+        cfg = {k: v for k, v in items.items() if k in accepted}
+        if cfg.get("beta_schedule") not in ("linear", "scaled_linear"):
+            raise NotImplementedError("DDIMInverseScheduler supports the linear and scaled_linear beta schedules")
+        cfg.update(override)
+        inv = cls(**cfg)
+        inv._sampler = copy.deepcopy(scheduler)           # its set_timesteps() is called here: the caller's object stays as it is
+        return inv
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        base = self._base_timesteps(num_inference_steps)[::-1].copy() + self.config.steps_offset
+        if self._sampler is not None:
+            self._sampler.set_timesteps(num_inference_steps)
+            ts = np.asarray(torch.as_tensor(self._sampler.timesteps).cpu().numpy()[::-1], dtype=np.int64).copy()
+            ts[0] = self.config.steps_offset
+            if len(ts) != num_inference_steps or np.any(np.diff(ts) <= 0):
+                raise ValueError("the sampler's %d timesteps do not ascend strictly from the clean level %d: %s"
+                                 % (num_inference_steps, self.config.steps_offset, ts.tolist()))
+            base = ts
+        self.timesteps = torch.from_numpy(base)
+        # the level each step moves to: the next entry; past the last one the fork's t + T // n (:236), i.e. final_alpha_cumprod
+        last = int(base[-1]) + self.config.num_train_timesteps // num_inference_steps
+        self._next_timestep = dict(zip(base.tolist(), base.tolist()[1:] + [last]))
+
+    def _next_alpha(self, t):
+        nxt = self._next_timestep[t]
+        return self.alphas_cumprod[nxt] if nxt < self.config.num_train_timesteps else self.final_alpha_cumprod
+
+    def coef_table(self, count=None) -> np.ndarray:
+        """[count, 8] fp32 rows sqrt(abar_t), sqrt(1 - abar_t), 0, 0, 0, sqrt(abar_next), sqrt(1 - abar_next), 0 of the first `count`
+        (default: all) inverse steps, each a 0-dim fp32 torch expression in the fork's order"""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps() before coef_table()")
+        n = len(self.timesteps)
+        count = n if count is None else int(count)
+        if not 1 <= count <= n:
+            raise ValueError("count must be in [1, %d], got %d" % (n, count))
+        rows = []
+        for t in self.timesteps.tolist()[:count]:
+            a_t, a_next = self.alphas_cumprod[t], self._next_alpha(t)
+            b_t = 1 - a_t
+            rows.append([float(a_t ** 0.5), float(b_t ** 0.5), 0.0, 0.0, 0.0, float(a_next ** 0.5), float((1 - a_next) ** 0.5), 0.0])
+        return np.asarray(rows, dtype=np.float32)
+
+    def step(self, model_output, timestep, sample, return_dict=True, **_):
+        """scheduling_ddim_inverse.py:210-265 in its expression order (torch; the engine's fused step computes the same bits)"""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        t = int(timestep)
+        a_t, a_next = self.alphas_cumprod[t], self._next_alpha(t)
+        b_t = 1 - a_t
+        p = self.config.prediction_type
+        if p == "epsilon":
+            x0 = (sample - b_t ** 0.5 * model_output) / a_t ** 0.5
+            eps = model_output
+        elif p == "sample":
+            x0 = model_output
+            eps = (sample - a_t ** 0.5 * x0) / b_t ** 0.5
+        else:
+            x0 = (a_t ** 0.5) * sample - (b_t ** 0.5) * model_output
+            eps = (a_t ** 0.5) * model_output + (b_t ** 0.5) * sample
+        if self.config.clip_sample:
+            x0 = x0.clamp(-self.config.clip_sample_range, self.config.clip_sample_range)
+        direction = (1 - a_next) ** 0.5 * eps
+        prev = a_next ** 0.5 * x0 + direction
+        return _StepOutput(prev) if return_dict else (prev, x0)
 
 
 def _glide_cosine_betas(num_train_timesteps, max_beta=0.999):
@@ -343,15 +466,20 @@ class DPMSolverMultistepScheduler(_AddNoise):
             raise ValueError("the schedule of %d steps repeats a timestep (%d distinct of %d training steps): a multistep solver "
                              "cannot step between equal timesteps" % (len(ts), len(set(ts)), self.config.num_train_timesteps))
 
-    def coef_table(self) -> np.ndarray:
-        """[N, 16] fp32 per-step scalars of the fused update (layout: class docstring)"""
+    def coef_table(self, start=0) -> np.ndarray:
+        """[N - start, 16] fp32 per-step scalars of the fused update (layout: class docstring).  `start` > 0 is the table of a loop
+        over `timesteps[start:]` (edit_plan()): NOT rows start: of the full table -- the loop has no history yet, so its first step
+        is order 1 and the order ramp restarts, which is what the fork does when a pipeline slices `scheduler.timesteps[t_start:]`
+        after a fresh set_timesteps (lower_order_nums == 0); `lower_order_final` still counts from the true end of the schedule.
+        step() replays the same loop when it is first called with `timesteps[start]`."""
         if self.num_inference_steps is None:
             raise ValueError("call set_timesteps() before coef_table()")
         self._check_distinct()
+        start = self._check_start(start)
         algo = 0.0 if self.config.algorithm_type == "dpmsolver++" else 1.0
         rows = []
-        for i in range(len(self.timesteps)):
-            order = self._step_order(i, min(i, self.config.solver_order))
+        for i in range(start, len(self.timesteps)):
+            order = self._step_order(i, min(i - start, self.config.solver_order))
             rows.append([float(v) for v in self._row(i, order)] + [float(order), algo, 0.0, 0.0, 0.0, 0.0])
         return np.asarray(rows, dtype=np.float32)
 
@@ -396,7 +524,7 @@ class DPMSolverMultistepScheduler(_AddNoise):
         return _StepOutput(x) if return_dict else (x,)
 
 
-_FROM_DIFFUSERS = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
+_FROM_DIFFUSERS = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler, "DDIMInverseScheduler": DDIMInverseScheduler,
                    "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}
 
 

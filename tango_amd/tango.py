@@ -11,7 +11,7 @@ import torch
 from .autoencoder import AutoencoderKL
 from .inpaint import TARGET_FRAMES, latent_mask, prepare_waveform
 from .models import AudioDiffusion
-from .scheduler import SD21_SCHEDULER_CONFIG, DDPMScheduler
+from .scheduler import SD21_SCHEDULER_CONFIG, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 from .stft import wav_to_fbank
 
 _CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")
@@ -155,13 +155,117 @@ class Tango:
             mel = self.vae.decode_first_stage(latents)
             return self.vae.decode_to_waveform(mel)
 
+    # ---- audio-to-audio editing (audioldm/pipeline.py:145-247 style_transfer) -----------------------------------------------------
+    def edit(self, prompt, audio, strength=0.5, steps=100, guidance=3, samples=1, mode="noise", source_prompt="", time_range=None,
+             freq_range=None, seed=None):
+        """Edit one 16 kHz clip `audio` (1-D; reading and resampling are the caller's) towards the text `prompt`: the clip's latents
+        are moved part of the way into the noise and the last k = int(strength * steps) of `steps` denoise steps run from there.
+        Returns np.int16 [samples, 163872].
+
+        mode="noise" is AudioLDM's style_transfer: a posterior sample of the encoded clip, noised to the encode level (one fused
+        launch; the draws are the device Philox generator's under `seed`, so an edit reproduces across batch splits).
+        mode="invert" is deterministic: the posterior mode, then k DDIM-inversion steps under `source_prompt` (the text that
+        describes the clip as it is; no CFG) up the sampler's own timesteps, which end exactly on the encode timestep of
+        mode="noise" (DDIMInverseScheduler.from_scheduler); `self.scheduler` must be a DDIMScheduler with eta = 0 or a
+        DPMSolverMultistepScheduler (a stochastic sampler would not retrace an inverted trajectory).
+        With `time_range` / `freq_range` (fractions of the clip, tango_amd.inpaint.latent_mask) only that region is edited;
+        the rest keeps the clip's audio through the masked loop.
+
+        Not reproduced from AudioLDM: the `samples[:, :, :-3, :]` crop of the decoded mel and the `duration` argument
+        (pipeline.py:172-175,241) -- they belong to its variable-length decoder; the engine's plans are one size (10.24 s)."""
+        with torch.no_grad():
+            self._check_edit(mode, steps, strength)
+            host = None
+            if guidance > 1.0:
+                pe, pm, host = self.model._encode_text_classifier_free([prompt], samples)
+            else:
+                pe, pm = self.model.encode_text([prompt])
+                pe, pm = pe.repeat_interleave(samples, 0), pm.repeat_interleave(samples, 0)
+            src = None
+            if mode == "invert":
+                se, sm = self.model.encode_text([source_prompt])
+                src = (se.repeat_interleave(samples, 0).float(), sm.repeat_interleave(samples, 0))
+            return self._edit(pe.float(), pm, audio, strength, steps, guidance, samples, mode, src, time_range, freq_range, seed,
+                              dict(mask_host=host))
+
+    def edit_from_embeddings(self, prompt_embeds, boolean_prompt_mask, audio, strength=0.5, steps=100, guidance=3, samples=1,
+                             mode="noise", source_embeds=None, source_mask=None, time_range=None, freq_range=None, seed=None, **kw):
+        """`edit` given the text-encoder outputs for the `samples` rows ([uncond; cond] when guidance > 1, like
+        generate_from_embeddings); mode="invert" takes the source prompt's `source_embeds` [samples, L, d] / `source_mask`
+        (conditional rows only).  `kw` goes to AudioDiffusion.edit_from_embeddings (noise, blend_noise, sample_offset)."""
+        with torch.no_grad():
+            self._check_edit(mode, steps, strength)
+            rows = prompt_embeds.shape[0] // 2 if guidance > 1.0 else prompt_embeds.shape[0]
+            if rows != samples:
+                raise ValueError("prompt_embeds hold %d rows, `samples` is %d" % (rows, samples))
+            src = None
+            if mode == "invert":
+                if source_embeds is None or source_embeds.shape[0] != samples:
+                    raise ValueError("mode='invert' needs source_embeds with %d rows" % samples)
+                src = (source_embeds, source_mask)
+            return self._edit(prompt_embeds, boolean_prompt_mask, audio, strength, steps, guidance, samples, mode, src, time_range,
+                              freq_range, seed, kw)
+
+    def _check_edit(self, mode, steps, strength):
+        """the argument checks of edit() that need no device"""
+        if mode not in ("noise", "invert"):
+            raise ValueError("mode must be 'noise' or 'invert', got %r" % (mode,))
+        k = int(strength * steps)
+        if not 1 <= k <= steps - 1:
+            raise ValueError("strength %r of %d steps runs k = %d steps; an edit needs 1 <= k <= %d" % (strength, steps, k, steps - 1))
+        if mode == "invert":
+            s = self.scheduler
+            ok = isinstance(s, DPMSolverMultistepScheduler) or (isinstance(s, DDIMScheduler) and s.eta == 0)
+            if not ok:
+                raise ValueError("mode='invert' needs a deterministic sampler: set Tango.scheduler to a DDIMScheduler (eta = 0) or a "
+                                 "DPMSolverMultistepScheduler, not %s" % type(s).__name__)
+
+    def _edit(self, pe, pm, audio, strength, steps, guidance, samples, mode, src, time_range, freq_range, seed, kw):
+        moments = self.encode_moments(audio)
+        if seed is None:
+            # like the loop's step noise: the Philox key comes from torch's global generator, so torch.manual_seed() fixes the edit
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        offset = kw.get("sample_offset", 0)
+        regional = time_range is not None or freq_range is not None
+        start, t_enc = self.scheduler.edit_plan(steps, strength)
+        if mode == "noise":
+            sa, sb = self.scheduler.blend_table(start=start - 1)[0]
+            out = self.vae.encode_start_latents(moments, float(sa), float(sb), samples, seed=seed, sample_offset=offset,
+                                                want_clean=regional)
+            x, known = out if regional else (out, None)
+        else:
+            # sa = 1, sb = 0: the scaled posterior mode itself, the same clip in every row (with sb = 0 the kernel draws no n)
+            z = self.vae.encode_start_latents(moments, 1.0, 0.0, samples, posterior="mode", seed=seed, sample_offset=offset)
+            known = z if regional else None
+            x = self.model.invert_from_embeddings(src[0], src[1], self.scheduler, steps, latents=z, count=steps - start)
+        masking = {}
+        if regional:
+            # latent_mask(): 1 keeps the known audio, 0 regenerates the named region -- the region of the edit
+            m = latent_mask(samples, time_range or (0.0, 0.0), freq_range or (1.0, 1.0), x.shape[2], x.shape[3])
+            masking = dict(known_latents=known, latent_mask=m)
+        latents = self.model.edit_from_embeddings(pe, pm, self.scheduler, steps, guidance, start_latents=x, strength=strength,
+                                                  seed=seed, **masking, **kw)
+        mel = self.vae.decode_first_stage(latents)
+        return self.vae.decode_to_waveform(mel)
+
+    def _need_encoder(self, what):
+        if self.stft is None or not getattr(self.vae, "with_encoder", False):
+            raise RuntimeError("%s needs the mel front-end and the VAE encoder: build Tango(..., with_encoder=True) from a "
+                               "snapshot with stft_config.json / pytorch_model_stft.bin, or pass stft= and an AutoencoderKL(with_encoder=True) "
+                               "to from_components" % what)
+
+    def encode_moments(self, audio):
+        """one 1-D 16 kHz clip -> the posterior's moments [1, 16, 256, 16] = [mean | logvar]: prepare_waveform -> wav_to_fbank ->
+        the VAE encoder, before any draw (AutoencoderKL.encode_start_latents takes them)"""
+        self._need_encoder("editing")
+        wav = prepare_waveform(audio)[None].to(self.model.device)
+        fbank, _, _ = wav_to_fbank(wav, TARGET_FRAMES, fn_STFT=self.stft)
+        return self.vae.engine.vae_encode(fbank.unsqueeze(1))
+
     def encode_audio(self, audio):
         """one 1-D 16 kHz clip -> known latents [1, 8, 256, 16]: prepare_waveform -> wav_to_fbank -> encode_first_stage ->
         get_first_stage_encoding (one posterior sample from torch's global generator, ldm.py:180-181)"""
-        if self.stft is None or not getattr(self.vae, "with_encoder", False):
-            raise RuntimeError("inpainting needs the mel front-end and the VAE encoder: build Tango(..., with_encoder=True) from a "
-                               "snapshot with stft_config.json / pytorch_model_stft.bin, or pass stft= and an AutoencoderKL(with_encoder=True) "
-                               "to from_components")
+        self._need_encoder("inpainting")
         wav = prepare_waveform(audio)[None].to(self.model.device)
         fbank, _, _ = wav_to_fbank(wav, TARGET_FRAMES, fn_STFT=self.stft)
         return self.vae.get_first_stage_encoding(self.vae.encode_first_stage(fbank.unsqueeze(1)))
