@@ -177,6 +177,9 @@ typedef struct tango_denoise_args {
   const float* latent_mask;
   const float* blend_coef;
   const float* blend_noise;
+  /* latent height H of this call: latents, noise, known_latents, latent_mask and blend_noise are [.., H, latent_w].  0 = the
+   * configured tango_config_t.latent_h.  A multiple of 8 << (unet_levels - 1) (an error otherwise); the plan cache keys on it. */
+  int32_t latent_h;
 } tango_denoise_args_t;
 
 const char* tango_last_error(void);
@@ -207,6 +210,21 @@ int tango_engine_unet_forward_music(tango_engine_t* h, const float* sample, int6
                                     const uint8_t* prompt_mask, const float* beat_embeds, const uint8_t* beat_mask,
                                     const float* chord_embeds, const uint8_t* chord_mask, float* out, int batch2, int text_len,
                                     int beat_len, int chord_len, void* stream);
+
+/* The *_h entry points below take the latent height of the call (the reference's duration_to_latent_t_size, audioldm/pipeline.py:94-95:
+ * int(duration * 25.6)); 0 = tango_config_t.latent_h, which is what the entry points without the suffix pass.  The width is always
+ * tango_config_t.latent_w.  UNet heights are multiples of 8 << (unet_levels - 1), VAE heights multiples of 8: an error otherwise. */
+int tango_engine_unet_forward_h(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
+                                const uint8_t* prompt_mask, float* out, int batch2, int text_len, int latent_h, void* stream);
+int tango_engine_unet_forward_music_h(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
+                                      const uint8_t* prompt_mask, const float* beat_embeds, const uint8_t* beat_mask,
+                                      const float* chord_embeds, const uint8_t* chord_mask, float* out, int batch2, int text_len,
+                                      int beat_len, int chord_len, int latent_h, void* stream);
+/* latents [B,8,H,16] -> mel [B,1,4H,64]; mel [B,1,4H,64] -> moments [B,16,H,16] */
+int tango_engine_vae_decode_h(tango_engine_t* h, const float* latents, float* mel, int batch, int latent_h, void* stream);
+int tango_engine_vae_encode_h(tango_engine_t* h, const float* mel, float* moments, int batch, int latent_h, void* stream);
+int tango_engine_profile_unet_h(tango_engine_t* h, int batch2, int text_len, int latent_h, char* report, int report_cap, void* stream);
+int tango_engine_profile_vae_h(tango_engine_t* h, int batch, int latent_h, char* report, int report_cap, void* stream);
 
 /* latents [B,8,256,16] fp32 -> mel [B,1,1024,64] fp32 */
 int tango_engine_vae_decode(tango_engine_t* h, const float* latents, float* mel, int batch, void* stream);
@@ -247,6 +265,8 @@ int tango_engine_last_step_gflop(tango_engine_t* h, double* gflop);
  * freed first (hipFree: synchronises the device).  The reference has no counterpart: tango.py:51-64 just re-runs PyTorch eagerly. */
 int tango_engine_set_plan_budget(tango_engine_t* h, uint64_t bytes);
 int tango_engine_plan_stats(tango_engine_t* h, uint64_t* bytes_in_use, int* plans);
+/* diagnostic: capacity in floats of the multistep history ring (3 * B * C * H * W of the largest TANGO_RULE_DPM_MULTISTEP call so far; 0 before) */
+int tango_engine_ring_elems(tango_engine_t* h, uint64_t* elems);
 /* frees every cached plan now (the next call of each shape rebuilds its plan); also what a measurement tool calls after
  * tango_tuning_reload() so that build-time routing decisions are taken again */
 int tango_engine_drop_plans(tango_engine_t* h);

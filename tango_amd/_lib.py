@@ -99,6 +99,7 @@ class DenoiseArgs(C.Structure):
         ("latent_mask", C.c_void_p),
         ("blend_coef", C.c_void_p),
         ("blend_noise", C.c_void_p),
+        ("latent_h", C.c_int32),
     ]
 
 
@@ -109,7 +110,9 @@ SYMBOLS = [
     "tango_engine_finalize_weights", "tango_engine_denoise", "tango_engine_unet_forward", "tango_engine_unet_forward_music",
     "tango_engine_vae_decode", "tango_engine_vae_encode", "tango_engine_vocode", "tango_engine_vocoder_samples", "tango_engine_encode_text",
     "tango_engine_mel_frames", "tango_engine_mel_spectrogram",
-    "tango_engine_last_denoise_ms", "tango_engine_last_step_gflop", "tango_engine_profile_unet", "tango_engine_profile_vae", "tango_engine_profile_vocoder", "tango_engine_set_plan_budget", "tango_engine_plan_stats", "tango_engine_drop_plans", "tango_op_conv2d", "tango_op_conv2d_ups", "tango_op_pack_ups_phase", "tango_op_linear", "tango_op_linear_ln", "tango_op_ff_fused", "tango_op_qkv_stat", "tango_op_linear_qkv", "tango_op_linear_qkv_perm", "tango_op_conv1d",
+    "tango_engine_last_denoise_ms", "tango_engine_last_step_gflop", "tango_engine_profile_unet", "tango_engine_profile_vae", "tango_engine_profile_vocoder",
+    "tango_engine_unet_forward_h", "tango_engine_unet_forward_music_h", "tango_engine_vae_decode_h", "tango_engine_vae_encode_h",
+    "tango_engine_profile_unet_h", "tango_engine_profile_vae_h", "tango_engine_set_plan_budget", "tango_engine_plan_stats", "tango_engine_ring_elems", "tango_engine_drop_plans", "tango_op_conv2d", "tango_op_conv2d_ups", "tango_op_pack_ups_phase", "tango_op_linear", "tango_op_linear_ln", "tango_op_ff_fused", "tango_op_qkv_stat", "tango_op_linear_qkv", "tango_op_linear_qkv_perm", "tango_op_conv1d",
     "tango_op_conv_transpose1d", "tango_op_groupnorm", "tango_op_layernorm", "tango_op_attention", "tango_op_attention_ex", "tango_op_xattn_block",
     "tango_op_sched_step", "tango_op_sched_multistep", "tango_op_philox_normal",
     "tango_op_sched_masked", "tango_op_philox_normal_blend",
@@ -149,6 +152,12 @@ def load():
     lib.tango_engine_unet_forward_music.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.tango_engine_vae_decode.argtypes = [vp, vp, vp, ci, vp]
     lib.tango_engine_vae_encode.argtypes = [vp, vp, vp, ci, vp]
+    lib.tango_engine_unet_forward_h.argtypes = [vp, vp, i64, vp, vp, vp, ci, ci, ci, vp]
+    lib.tango_engine_unet_forward_music_h.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+    lib.tango_engine_vae_decode_h.argtypes = [vp, vp, vp, ci, ci, vp]
+    lib.tango_engine_vae_encode_h.argtypes = [vp, vp, vp, ci, ci, vp]
+    lib.tango_engine_profile_unet_h.argtypes = [vp, ci, ci, ci, C.c_char_p, ci, vp]
+    lib.tango_engine_profile_vae_h.argtypes = [vp, ci, ci, C.c_char_p, ci, vp]
     lib.tango_engine_vocode.argtypes = [vp, vp, vp, ci, ci, C.POINTER(ci), vp]
     lib.tango_engine_vocoder_samples.argtypes = [vp, ci]
     lib.tango_engine_encode_text.argtypes = [vp, vp, vp, vp, ci, ci, vp]
@@ -163,6 +172,7 @@ def load():
     lib.tango_engine_drop_plans.argtypes = [vp]
     lib.tango_debug_linear_route.argtypes = [ci] * 8
     lib.tango_debug_linear_route.restype = C.c_char_p
+    lib.tango_engine_ring_elems.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.tango_engine_plan_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(ci)]
     lib.tango_op_conv2d.argtypes = [ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.tango_op_conv2d_ups.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from .engine import HIFIGAN_CONFIG, Engine, _stream_ptr
+from .inpaint import check_latent_h
 
 #: AudioLDM style_transfer's guard against blown-up encodings (audioldm/pipeline.py:209-210): above the trigger, clamp to the range
 EDIT_CLIP_TRIGGER, EDIT_CLIP_RANGE = 1e2, 10.0
@@ -69,8 +70,20 @@ class AutoencoderKL:
 
     @torch.no_grad()
     def encode(self, x):
-        """autoencoder.py:52-58: Encoder + quant_conv on the engine -> posterior (subband == 1: no frequency split)."""
-        return DiagonalGaussianDistribution(self.engine.vae_encode(x))
+        """autoencoder.py:52-58: Encoder + quant_conv on the engine -> posterior (subband == 1: no frequency split).  The mel's
+        frame count names the clip length: [B, 1, 4H, 64] for a latent height H of the duration grid."""
+        return DiagonalGaussianDistribution(self.engine.vae_encode(x, latent_h=self._mel_h(x)))
+
+    def _mel_h(self, x):
+        f = 1 << (len(self.vae_cfg["ch_mult"]) - 1)
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[2] % f:
+            raise ValueError("mel must be [B, 1, %d H, %d], got %s" % (f, 16 * f, tuple(getattr(x, "shape", ()))))
+        return check_latent_h(x.shape[2] // f)
+
+    def _latent_h(self, z):
+        if not torch.is_tensor(z) or z.dim() != 4:
+            raise ValueError("latents must be [B, %d, H, 16], got %s" % (self.embed_dim, tuple(getattr(z, "shape", ()))))
+        return check_latent_h(z.shape[2])
 
     def encode_first_stage(self, x):
         """autoencoder.py:112-113"""
@@ -131,16 +144,16 @@ class AutoencoderKL:
     @torch.no_grad()
     def decode(self, z):
         """autoencoder.py:60-64 (post_quant_conv + Decoder); note: no 1/scale_factor here."""
-        return self.engine.vae_decode(z * self.scale_factor)
+        return self.engine.vae_decode(z * self.scale_factor, latent_h=self._latent_h(z))
 
     @torch.no_grad()
     def decode_first_stage(self, z):
-        """autoencoder.py:116-124: z / scale_factor -> decode -> mel [B,1,1024,64]."""
-        return self.engine.vae_decode(z)
+        """autoencoder.py:116-124: z / scale_factor -> decode -> mel [B,1,1024,64] ([B,1,4H,64] for latents of height H)."""
+        return self.engine.vae_decode(z, latent_h=self._latent_h(z))
 
     @torch.no_grad()
     def decode_to_waveform(self, dec) -> np.ndarray:
-        """autoencoder.py:66-69 -> vocoder_infer (hifigan/utilities.py:76-86): np.int16 [B, 163872].
+        """autoencoder.py:66-69 -> vocoder_infer (hifigan/utilities.py:76-86): np.int16 [B, 163872] (160 * frames + 32 samples for a mel of any frame count).
         The int16 cast (C truncation of wav*32768) happens on the device; only int16 crosses PCIe."""
         wav = self.engine.vocode(dec)
         return wav.cpu().numpy()

@@ -47,16 +47,21 @@ def write_wav(path: str, samples: np.ndarray, sample_rate: int = SAMPLE_RATE) ->
 
 
 def generate_and_save(generator, prompts: Sequence[str], num_steps: int = 200, guidance: float = 3, batch_size: int = 8,
-                      num_samples: int = 1, out_root: str = "outputs", tag: str = "", exp_id: Optional[str] = None) -> dict:
-    """Returns the summary record (also appended to <out_root>/summary.jsonl)."""
+                      num_samples: int = 1, out_root: str = "outputs", tag: str = "", exp_id: Optional[str] = None,
+                      duration: float = 10) -> dict:
+    """Returns the summary record (also appended to <out_root>/summary.jsonl).  `duration`: seconds of audio per prompt (2.5 .. 20
+    on the 2.5 s grid); any other value than the default 10 is handed to the generator's `generate_for_batch(..., duration=)`."""
     if num_samples < 1 or batch_size < 1:
         raise ValueError("num_samples and batch_size must be >= 1")
+    from .inpaint import duration_geometry
+    duration_geometry(duration)
+    length = {} if duration == 10 else {"duration": duration}
     exp_id = exp_id or str(int(time.time()))
     name = "{}_{}steps_{}_guidance_{}".format(exp_id, (tag + "_") if tag else "", num_steps, guidance)
     out_dir = os.path.join(out_root, name)
     t0 = time.perf_counter()
     outs = generator.generate_for_batch(list(prompts), steps=num_steps, guidance=guidance, samples=num_samples,
-                                        batch_size=batch_size) if prompts else []
+                                        batch_size=batch_size, **length) if prompts else []
     dt = time.perf_counter() - t0
     if len(outs) != len(prompts):
         raise RuntimeError("generator returned %d items for %d prompts" % (len(outs), len(prompts)))
@@ -111,6 +116,7 @@ def parse_args(argv: Optional[Iterable[str]] = None):
     ap.add_argument("--guidance", type=float, default=3)
     ap.add_argument("--batch_size", type=int, default=8)
     ap.add_argument("--num_samples", type=int, default=1)
+    ap.add_argument("--duration", type=float, default=10, help="seconds of audio per prompt: 2.5 .. 20 in steps of 2.5")
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--dtype", type=str, default="fp16", choices=["fp32", "fp16", "bf16"])
     ap.add_argument("--out_root", type=str, default="outputs")
@@ -131,7 +137,7 @@ def main(argv: Optional[Iterable[str]] = None) -> dict:
     tango.scheduler = make_scheduler(args.scheduler, tango.scheduler.config, args.solver_order)
     prompts = read_prompts(args.test_file, args.text_key, args.prefix)
     rec = generate_and_save(tango, prompts, args.num_steps, args.guidance, args.batch_size, args.num_samples, args.out_root,
-                            tag="_".join(p for p in args.model.strip("/").split("/")[-2:] if p))
+                            tag="_".join(p for p in args.model.strip("/").split("/")[-2:] if p), duration=args.duration)
     print(json.dumps(rec))
     return rec
 

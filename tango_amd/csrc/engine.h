@@ -131,7 +131,7 @@ struct PlanMeta {
 };
 // the kinds of plan an engine caches: the first entry of a PlanKey, followed by the shape ints of the call
 enum PlanKind { PLAN_UNET, PLAN_VAE_DEC, PLAN_VAE_ENC, PLAN_VOC, PLAN_T5, PLAN_STFT };
-using PlanKey = std::array<int, 7>;
+using PlanKey = std::array<int, 8>;
 struct Plan {
   const PlanKind kind;
   PlanMeta meta;
@@ -160,6 +160,7 @@ struct UNetPlan : Plan {
   using Plan::Plan;
   UNetMode mode = UNetMode::Whole;
   int B2 = 0, L = 0;
+  int H = 0;                // latent height of the call (the plan's images are H >> level rows of cfg.latent_w >> level pixels)
   int Lc[3] = {0, 0, 0};    // condition lengths: [0] text (== L), [1] beat, [2] chord (Music UNet only)
   Program pre, step;
   void* xin = nullptr;      // T  [B2*HW][8]
@@ -202,6 +203,7 @@ struct T5Plan : Plan {
 struct VaePlan : Plan {    // decoder, encoder and vocoder: plan-owned in/out staging buffers
   using Plan::Plan;
   int B = 0;
+  int H = 0;                // decoder / encoder: latent height of the call
   Program prog;
   void* in = nullptr;
   void* out = nullptr;
@@ -225,22 +227,24 @@ class Engine {
   int finalize_weights();
   int denoise(const tango_denoise_args_t& a, hipStream_t s);
   struct Cond { const float* emb = nullptr; const uint8_t* mask = nullptr; int len = 0; const uint8_t* mask_host = nullptr; };
-  int unet_forward(const float* sample, int64_t t, const Cond (&c)[3], float* out, int B2, hipStream_t s);
-  int vae_decode(const float* lat, float* mel, int B, hipStream_t s);
-  int vae_encode(const float* mel, float* moments, int B, hipStream_t s);
+  // latent_h: the latent height of the call, 0 = cfg.latent_h (the width is always cfg.latent_w)
+  int unet_forward(const float* sample, int64_t t, const Cond (&c)[3], float* out, int B2, int latent_h, hipStream_t s);
+  int vae_decode(const float* lat, float* mel, int B, int latent_h, hipStream_t s);
+  int vae_encode(const float* mel, float* moments, int B, int latent_h, hipStream_t s);
   int vocode(const float* mel, int16_t* wav, int B, int frames, int* n_samples, hipStream_t s);
   int vocoder_samples(int frames) const;
   int encode_text(const int64_t* ids, const uint8_t* mask, float* out, int B, int L, hipStream_t s);
   int mel_spectrogram(const float* wav, float* mel, float* logmag, float* energy, int B, int N, int* n_frames, hipStream_t s);
   int last_denoise_ms(float* total_ms, float* per_step_ms);
-  int profile_unet(int B2, int L, std::string& report, hipStream_t s);
-  int profile_vae(int B, std::string& report, hipStream_t s);                  // per-op timing of the mel-VAE decoder plan (round 6)
+  int profile_unet(int B2, int L, int latent_h, std::string& report, hipStream_t s);
+  int profile_vae(int B, int latent_h, std::string& report, hipStream_t s);                 // per-op timing of the mel-VAE decoder plan (round 6)
   int profile_vocoder(int B, int frames, std::string& report, hipStream_t s);  // ... of the HiFi-GAN plan
   // plan-cache budget (bytes of workspace slabs kept alive; default 64 GiB or TANGO_PLAN_BUDGET_MB) and its current use
   void set_plan_budget(size_t bytes) { plan_budget = bytes; }
   void drop_plans() { const size_t b = plan_budget; plan_budget = 0; (void)make_room(1); plan_budget = b; }   // frees every cached plan
   size_t plan_bytes_in_use() const { return plan_bytes; }
   int plan_count() const { return (int)plans.size(); }
+  size_t ring_capacity() const { return ring_elems; }     // floats the multistep history holds (diagnostic)
 
   tango_config_t cfg;
   int dt = DT_F32;
@@ -333,8 +337,8 @@ class Engine {
   int64_t* d_ts = nullptr;       // [max_steps]
   float* d_coef = nullptr;       // [max_steps][16] (DDPM / DDIM rows use the first 8 floats of a packed [N][8] table)
   float* d_bcoef = nullptr;      // [max_steps][2] add_noise scalars of the masked loop's blend (tango_denoise_args_t.blend_coef)
-  float* d_ring = nullptr;       // multistep history [3][ring_batch][C][HW] fp32 (hipMalloc'd, grown with the batch; not in `owned`)
-  int ring_batch = 0;
+  float* d_ring = nullptr;       // multistep history [3][B][C][HW] fp32 of the call (hipMalloc'd, grown on demand; not in `owned`)
+  size_t ring_elems = 0;         // its capacity in floats
   float* d_sin = nullptr;        // [max_steps][ch0]
   float* d_t1 = nullptr;         // [max_steps][temb]
   float* d_temb = nullptr;       // [max_steps][temb]  silu(emb)
@@ -361,7 +365,7 @@ class Engine {
   int stage_h2d(void* dst_dev, const void* src_host, size_t bytes, hipStream_t s);
 
   // ---- the plan cache: every kind of plan in one map, one LRU byte budget ----
-  // keys: UNet (B2, L_text, L_beat, L_chord, n_short, mode); VAE decoder / encoder (B); vocoder (B, frames); T5 (B, L); STFT (B, N)
+  // keys: UNet (B2, L_text, L_beat, L_chord, n_short, mode, H); VAE decoder / encoder (B, H); vocoder (B, frames); T5 (B, L); STFT (B, N)
   std::map<PlanKey, std::unique_ptr<Plan>> plans;
   size_t plan_budget = (size_t)64 << 30, plan_bytes = 0;
   uint64_t plan_clock = 0;
@@ -393,7 +397,9 @@ class Engine {
   }
 
   int ensure_temb(const int64_t* ts_host, int n, hipStream_t s);
-  int get_unet_plan(int B2, int L, int Lbeat, int Lchord, int n_short, UNetPlan** out, UNetMode mode = UNetMode::Whole);
+  static constexpr int kMaxLatentH = 4096;
+  int resolve_h(int latent_h, bool unet, int* H) const;
+  int get_unet_plan(int B2, int L, int Lbeat, int Lchord, int n_short, int H, UNetPlan** out, UNetMode mode = UNetMode::Whole);
   int build_unet_plan(UNetPlan& P, Arena& A, bool record);   // build_unet, or the parent and the two children of a two-chain plan
   bool cfg_shared_ok(int B2, int n_short) const;
   // how a guidance / plain batch of B2 UNet rows runs; profile_unet() asks with two_chains_ok = false
@@ -402,9 +408,9 @@ class Engine {
   int capture_steps(const UNetPlan& P, int rule, bool masked, int n, hipGraph_t* g_out, hipGraphExec_t* x_out);
   int single_key_prefix(const uint8_t* mask_dev, const uint8_t* mask_host, int B2, int L, std::vector<int>& key0, hipStream_t s);
   int build_unet(UNetPlan& P, Arena& A, bool record);
-  int get_vae_plan(int B, VaePlan** out);
+  int get_vae_plan(int B, int H, VaePlan** out);
   int build_vae(VaePlan& P, Arena& A, bool record);
-  int get_vae_enc_plan(int B, VaePlan** out);
+  int get_vae_enc_plan(int B, int H, VaePlan** out);
   int build_vae_enc(VaePlan& P, Arena& A, bool record);
   int get_voc_plan(int B, int frames, VaePlan** out);
   int build_voc(VaePlan& P, Arena& A, bool record, int frames);

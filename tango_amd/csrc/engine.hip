@@ -113,7 +113,9 @@ struct Builder {
     if (o.ln) {
       GemmParams q = p;
       q.W = w.Wln; q.bias = w.bln; q.ln_fold = 1; q.ln_eps = o.ln->eps; q.wsum = w.wsum;
-      if (w.Wln && gemm_ln_fold_ok(dt, q)) {
+      // (a folded LayerNorm is never split along K: the split-K policy does not ask the 256 x 320 GEMM, so with the big tiles forced
+      //  onto a small problem it would split what only the unsplit kernel can fold)
+      if (w.Wln && gemm_ln_fold_ok(dt, q) && gemm_pick_splitk(dt, q) <= 1) {
         const int rq = gemm_route(dt, q);
         gemm(q, rq == ROUTE_WIDE ? "linear+ln(wide)" : rq == ROUTE_DUO ? "linear+ln(duo)" : "linear+ln(stream)");
         return;
@@ -125,7 +127,7 @@ struct Builder {
         float* st = alloc_f32((size_t)rows * 2);
         GemmParams q2 = q;
         q2.row_stats = st;
-        if (gemm_wide_ok(dt, q2) && gemm_route(dt, q2) == ROUTE_WIDE) {
+        if (gemm_wide_ok(dt, q2) && gemm_route(dt, q2) == ROUTE_WIDE && gemm_pick_splitk(dt, q2) <= 1) {
           const int d = dt;
           const void* xp = x.p; const int64_t ldx = x.ld; const int r = (int)rows, c = o.ln->C; const float eps = o.ln->eps;
           push([=](hipStream_t s) { return launch_ln_stats(d, xp, ldx, st, r, c, eps, s); }, "ln_stats C=" + std::to_string(c));
@@ -1146,7 +1148,7 @@ int Engine::build_unet(UNetPlan& P, Arena& A, bool record) {
   const int* ch = cfg.unet_channels;
   const int B2 = P.B2, G = cfg.unet_groups;
   const int lpb = cfg.unet_layers_per_block;
-  auto HH = [&](int lvl) { return cfg.latent_h >> lvl; };
+  auto HH = [&](int lvl) { return P.H >> lvl; };
   auto WW = [&](int lvl) { return cfg.latent_w >> lvl; };
   auto rows_at = [&](int lvl) { return (int64_t)B2 * HH(lvl) * WW(lvl); };
   const int cin_pad = 8 > cfg.unet_in_channels ? 8 : ((cfg.unet_in_channels + 7) / 8) * 8;
@@ -1338,13 +1340,13 @@ int Engine::build_unet(UNetPlan& P, Arena& A, bool record) {
 int Engine::build_unet_plan(UNetPlan& P, Arena& A, bool record) {
   if (P.mode != UNetMode::TwoChains) return build_unet(P, A, record);
   // the parent: input and output of the whole batch (what the scheduler kernel reads and writes), nothing else
-  const int HW = cfg.latent_h * cfg.latent_w, hb = P.B2 / 2;
+  const int HW = P.H * cfg.latent_w, hb = P.B2 / 2;
   const int cin_pad = 8 > cfg.unet_in_channels ? 8 : ((cfg.unet_in_channels + 7) / 8) * 8;
   P.xin = A.alloc((size_t)P.B2 * HW * cin_pad * esz);
   P.eps = (float*)A.alloc((size_t)P.B2 * HW * cfg.unet_out_channels * 4);
   for (int k = 0; record && k < 2; ++k) {
     std::unique_ptr<UNetPlan> C(new UNetPlan(PLAN_UNET));
-    C->B2 = hb; C->L = P.L;
+    C->B2 = hb; C->L = P.L; C->H = P.H;
     for (int i = 0; i < 3; ++i) C->Lc[i] = P.Lc[i];
     C->n_short = k == 0 ? (P.n_short < hb ? P.n_short : hb) : (P.n_short > hb ? P.n_short - hb : 0);
     C->ext_xin = (char*)P.xin + (size_t)k * hb * HW * cin_pad * esz;
@@ -1357,16 +1359,27 @@ int Engine::build_unet_plan(UNetPlan& P, Arena& A, bool record) {
   return 0;
 }
 
-int Engine::get_unet_plan(int B2, int L, int Lbeat, int Lchord, int n_short, UNetPlan** out, UNetMode mode) {
+// the latent height of a call: 0 = the configured one.  Every UNet level halves it and the deepest level's kernels work on images of
+// at least 8 rows, so a UNet height is a multiple of 8 << (levels - 1); the VAE only ever doubles it.
+int Engine::resolve_h(int latent_h, bool unet, int* H) const {
+  const int h = latent_h ? latent_h : cfg.latent_h;
+  const int q = unet ? 8 << (cfg.unet_levels > 0 ? cfg.unet_levels - 1 : 0) : 8;
+  if (h <= 0 || h % q != 0 || h > kMaxLatentH)
+    TANGO_FAIL("engine: latent height " + std::to_string(h) + " must be a positive multiple of " + std::to_string(q) + ", at most " + std::to_string(kMaxLatentH));
+  *H = h;
+  return 0;
+}
+
+int Engine::get_unet_plan(int B2, int L, int Lbeat, int Lchord, int n_short, int H, UNetPlan** out, UNetMode mode) {
   if (cfg.unet_music && (Lbeat <= 0 || Lchord <= 0)) TANGO_FAIL("engine: the Music UNet needs beat and chord conditions (beat_len, chord_len > 0)");
   if (!cfg.unet_music) { Lbeat = 0; Lchord = 0; }
   if (n_short < 0 || n_short > B2) TANGO_FAIL("engine: bad single-key prefix");
   if (mode != UNetMode::Whole && B2 % 2 != 0) TANGO_FAIL("engine: dual / CFG-shared plans need an even batch");
   if (mode == UNetMode::CfgShared && !cfg_shared_ok(B2, n_short)) TANGO_FAIL("engine: the CFG-shared prefix needs a [single-key; text] batch and a plain UNet");
   // zero-filled: V^T pad columns (L not a multiple of 8) must stay zero
-  return get_plan<UNetPlan>({PLAN_UNET, B2, L, Lbeat, Lchord, n_short, (int)mode}, true, out,
+  return get_plan<UNetPlan>({PLAN_UNET, B2, L, Lbeat, Lchord, n_short, (int)mode, H}, true, out,
                             [&](UNetPlan& P) {
-                              P.mode = mode; P.B2 = B2; P.L = L; P.n_short = n_short;
+                              P.mode = mode; P.B2 = B2; P.L = L; P.n_short = n_short; P.H = H;
                               P.Lc[0] = L; P.Lc[1] = Lbeat; P.Lc[2] = Lchord;
                             },
                             [this](UNetPlan& P, Arena& A, bool record) { return build_unet_plan(P, A, record); });
@@ -1435,15 +1448,17 @@ int Engine::single_key_prefix(const uint8_t* mask_dev, const uint8_t* mask_host,
   return 0;
 }
 
-int Engine::unet_forward(const float* sample, int64_t t, const Cond (&c)[3], float* out, int B2, hipStream_t s) {
+int Engine::unet_forward(const float* sample, int64_t t, const Cond (&c)[3], float* out, int B2, int latent_h, hipStream_t s) {
   UNetPlan* P;
   std::vector<int> key0;
+  int H;
+  TANGO_TRY(resolve_h(latent_h, true, &H));
   const int ns = single_key_prefix(c[0].mask, c[0].mask_host, B2, c[0].len, key0, s);
-  TANGO_TRY(get_unet_plan(B2, c[0].len, c[1].len, c[2].len, ns, &P));
+  TANGO_TRY(get_unet_plan(B2, c[0].len, c[1].len, c[2].len, ns, H, &P));
   TANGO_TRY(ensure_temb(&t, 1, s));
   TANGO_HIP(hipMemsetAsync(d_step, 0, 4, s));
   TANGO_TRY(bind_text(*P, c, key0, s));
-  const int HW = cfg.latent_h * cfg.latent_w;
+  const int HW = H * cfg.latent_w;
   TANGO_TRY(launch_fill_zero(P->xin, (size_t)B2 * HW * 8 * esz, s));
   TANGO_TRY(launch_nchw_to_nhwc(dt, sample, P->xin, 8, B2, cfg.unet_in_channels, HW, 1, 1.0f, s));
   TANGO_TRY(P->step.run(s));
@@ -1508,7 +1523,7 @@ int Engine::run_step(const UNetPlan& P, int rule, bool masked, hipStream_t st, h
     TANGO_HIP(hipEventRecord(join, st2));
     TANGO_HIP(hipStreamWaitEvent(st, join, 0));
   }
-  TANGO_TRY(launch_sched_step(dt, d_sched, P.B2 * cfg.latent_h * cfg.latent_w, st, rule, masked));
+  TANGO_TRY(launch_sched_step(dt, d_sched, P.B2 * P.H * cfg.latent_w, st, rule, masked));
   return launch_step_inc(d_step, st);
 }
 
@@ -1538,17 +1553,20 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
   const int B = a.batch, B2 = cfg_on ? 2 * B : B;
   UNetPlan* P;
   std::vector<int> key0;
+  int H;
+  TANGO_TRY(resolve_h(a.latent_h, true, &H));
   const int ns = single_key_prefix(a.prompt_mask, a.prompt_mask_host, B2, a.text_len, key0, s);
   const UNetMode mode = unet_mode_for(B2, ns, cfg_on, true);
-  TANGO_TRY(get_unet_plan(B2, a.text_len, a.beat_len, a.chord_len, ns, &P, mode));
+  TANGO_TRY(get_unet_plan(B2, a.text_len, a.beat_len, a.chord_len, ns, H, &P, mode));
   TANGO_TRY(ensure_temb(a.timesteps, a.num_steps, s));
-  const int HW = cfg.latent_h * cfg.latent_w;
+  const int HW = H * cfg.latent_w;
   const int C = cfg.unet_in_channels;
-  if (ms && B > ring_batch) {
+  const size_t ring_need = (size_t)3 * B * C * HW;    // elements: a call with fewer, taller samples may need more than an earlier one
+  if (ms && ring_need > ring_elems) {
     // outside any capture; every earlier use of the old ring (replays in flight on any stream) completes before it is freed
-    if (d_ring) { TANGO_HIP(hipDeviceSynchronize()); (void)hipFree(d_ring); d_ring = nullptr; ring_batch = 0; }
-    if (hipMalloc(&d_ring, (size_t)3 * B * C * HW * 4) != hipSuccess) { d_ring = nullptr; TANGO_FAIL("denoise: hipMalloc of the multistep ring failed"); }
-    ring_batch = B;
+    if (d_ring) { TANGO_HIP(hipDeviceSynchronize()); (void)hipFree(d_ring); d_ring = nullptr; ring_elems = 0; }
+    if (hipMalloc(&d_ring, ring_need * 4) != hipSuccess) { d_ring = nullptr; TANGO_FAIL("denoise: hipMalloc of the multistep ring failed"); }
+    ring_elems = ring_need;
   }
   SchedParams sp;
   sp.lat = a.latents; sp.eps = P->eps; sp.xin = P->xin; sp.xin_ld = 8;
@@ -1636,12 +1654,14 @@ int Program::run_profiled(hipStream_t s, std::string& report) const {
   return 0;
 }
 
-int Engine::profile_unet(int B2, int L, std::string& report, hipStream_t s) {
+int Engine::profile_unet(int B2, int L, int latent_h, std::string& report, hipStream_t s) {
   UNetPlan* P;
+  int H;
+  TANGO_TRY(resolve_h(latent_h, true, &H));
   // the product's CFG structure: the first half of the batch is the unconditional (single-key) half
   const int ns = (!tuning().no_single_key && B2 % 2 == 0) ? B2 / 2 : 0;
   // (and the plan denoise() would run for it: with the CFG-shared prefix where that applies)
-  TANGO_TRY(get_unet_plan(B2, L, cfg.unet_music ? 50 : 0, cfg.unet_music ? 20 : 0, ns, &P, unet_mode_for(B2, ns, true, false)));   // mustango/models.py:336,340: beat_len 50, chord_len 20
+  TANGO_TRY(get_unet_plan(B2, L, cfg.unet_music ? 50 : 0, cfg.unet_music ? 20 : 0, ns, H, &P, unet_mode_for(B2, ns, true, false)));   // mustango/models.py:336,340: beat_len 50, chord_len 20
   int64_t t = 500;
   TANGO_TRY(ensure_temb(&t, 1, s));
   TANGO_HIP(hipMemsetAsync(d_step, 0, 4, s));
@@ -1652,10 +1672,12 @@ int Engine::profile_unet(int B2, int L, std::string& report, hipStream_t s) {
 
 // per-op tables of the two plans that follow the denoise loop in every pass (they had no per-op profile); inputs
 // are whatever the plan buffers hold -- only the times matter
-int Engine::profile_vae(int B, std::string& report, hipStream_t s) {
+int Engine::profile_vae(int B, int latent_h, std::string& report, hipStream_t s) {
   if (cfg.vae_levels <= 0) TANGO_FAIL("engine: VAE not configured");
   VaePlan* P;
-  TANGO_TRY(get_vae_plan(B, &P));
+  int H;
+  TANGO_TRY(resolve_h(latent_h, false, &H));
+  TANGO_TRY(get_vae_plan(B, H, &P));
   TANGO_TRY(P->prog.run(s));
   TANGO_HIP(hipStreamSynchronize(s));
   return P->prog.run_profiled(s, report);
@@ -1835,7 +1857,7 @@ int Engine::encode_text(const int64_t* ids, const uint8_t* mask, float* out, int
 int Engine::build_vae(VaePlan& P, Arena& A, bool record) {
   Builder b{*this, A, &P.prog, record, dt, esz};
   const int B = P.B, nl = cfg.vae_levels;
-  const int H0 = cfg.latent_h, W0 = cfg.latent_w, HW0 = H0 * W0;
+  const int H0 = P.H, W0 = cfg.latent_w, HW0 = H0 * W0;
   const int zc = cfg.vae_z_channels;
   P.in_bytes = (size_t)B * cfg.vae_embed_dim * HW0 * 4;
   P.in = A.alloc(P.in_bytes);
@@ -1887,16 +1909,18 @@ int Engine::build_vae(VaePlan& P, Arena& A, bool record) {
   return 0;
 }
 
-int Engine::get_vae_plan(int B, VaePlan** out) {
-  return get_plan<VaePlan>({PLAN_VAE_DEC, B}, false, out, [&](VaePlan& P) { P.B = B; },
+int Engine::get_vae_plan(int B, int H, VaePlan** out) {
+  return get_plan<VaePlan>({PLAN_VAE_DEC, B, H}, false, out, [&](VaePlan& P) { P.B = B; P.H = H; },
                            [this](VaePlan& P, Arena& A, bool record) { return build_vae(P, A, record); });
 }
 
-int Engine::vae_decode(const float* lat, float* mel, int B, hipStream_t s) {
+int Engine::vae_decode(const float* lat, float* mel, int B, int latent_h, hipStream_t s) {
   if (cfg.vae_levels <= 0) TANGO_FAIL("engine: VAE not configured");
   if (cfg.vae_out_ch != 1) TANGO_FAIL("engine: VAE out_ch must be 1 (NHWC == NCHW at the boundary)");
   VaePlan* P;
-  TANGO_TRY(get_vae_plan(B, &P));
+  int H;
+  TANGO_TRY(resolve_h(latent_h, false, &H));
+  TANGO_TRY(get_vae_plan(B, H, &P));
   TANGO_HIP(hipMemcpyAsync(P->in, lat, P->in_bytes, hipMemcpyDeviceToDevice, s));
   TANGO_TRY(P->prog.run(s));
   TANGO_HIP(hipMemcpyAsync(mel, P->out, P->out_bytes, hipMemcpyDeviceToDevice, s));
@@ -1912,8 +1936,8 @@ int Engine::build_vae_enc(VaePlan& P, Arena& A, bool record) {
   Builder b{*this, A, &P.prog, record, dt, esz};
   const int B = P.B, nl = cfg.vae_levels;
   const int cin = cfg.vae_in_channels > 0 ? cfg.vae_in_channels : 1;
-  int Hc = cfg.latent_h << (nl - 1), Wc = cfg.latent_w << (nl - 1);
-  const int HW0 = cfg.latent_h * cfg.latent_w;
+  int Hc = P.H << (nl - 1), Wc = cfg.latent_w << (nl - 1);
+  const int HW0 = P.H * cfg.latent_w;
   P.in_bytes = (size_t)B * cin * Hc * Wc * 4;
   P.in = A.alloc(P.in_bytes);
   P.out_bytes = (size_t)B * 2 * cfg.vae_embed_dim * HW0 * 4;
@@ -1967,15 +1991,17 @@ int Engine::build_vae_enc(VaePlan& P, Arena& A, bool record) {
   return 0;
 }
 
-int Engine::get_vae_enc_plan(int B, VaePlan** out) {
-  return get_plan<VaePlan>({PLAN_VAE_ENC, B}, false, out, [&](VaePlan& P) { P.B = B; },
+int Engine::get_vae_enc_plan(int B, int H, VaePlan** out) {
+  return get_plan<VaePlan>({PLAN_VAE_ENC, B, H}, false, out, [&](VaePlan& P) { P.B = B; P.H = H; },
                            [this](VaePlan& P, Arena& A, bool record) { return build_vae_enc(P, A, record); });
 }
 
-int Engine::vae_encode(const float* mel, float* moments, int B, hipStream_t s) {
+int Engine::vae_encode(const float* mel, float* moments, int B, int latent_h, hipStream_t s) {
   if (cfg.vae_levels <= 0 || !cfg.vae_encoder) TANGO_FAIL("engine: VAE encoder not configured (tango_config.vae_encoder)");
   VaePlan* P;
-  TANGO_TRY(get_vae_enc_plan(B, &P));
+  int H;
+  TANGO_TRY(resolve_h(latent_h, false, &H));
+  TANGO_TRY(get_vae_enc_plan(B, H, &P));
   TANGO_HIP(hipMemcpyAsync(P->in, mel, P->in_bytes, hipMemcpyDeviceToDevice, s));
   TANGO_TRY(P->prog.run(s));
   TANGO_HIP(hipMemcpyAsync(moments, P->out, P->out_bytes, hipMemcpyDeviceToDevice, s));
@@ -2120,6 +2146,11 @@ int tango_engine_drop_plans(tango_engine_t* h) {
   h->e->drop_plans();
   return 0;
 }
+int tango_engine_ring_elems(tango_engine_t* h, uint64_t* elems) {
+  if (!h || !elems) { tango::set_error("tango_engine_ring_elems: null argument"); return -1; }
+  *elems = (uint64_t)h->e->ring_capacity();
+  return 0;
+}
 int tango_engine_plan_stats(tango_engine_t* h, uint64_t* bytes_in_use, int* plans) {
   if (!h) { tango::set_error("tango_engine_plan_stats: null engine"); return -1; }
   if (bytes_in_use) *bytes_in_use = (uint64_t)h->e->plan_bytes_in_use();
@@ -2160,27 +2191,44 @@ int tango_engine_denoise(tango_engine_t* h, const tango_denoise_args_t* a, void*
   if (!a) { tango::set_error("denoise: null args"); return -1; }
   return h->e->denoise(*a, (hipStream_t)stream);
 }
-int tango_engine_unet_forward(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
-                              const uint8_t* prompt_mask, float* out, int batch2, int text_len, void* stream) {
+int tango_engine_unet_forward_h(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
+                                const uint8_t* prompt_mask, float* out, int batch2, int text_len, int latent_h, void* stream) {
   Engine::Cond c[3];
   c[0].emb = prompt_embeds; c[0].mask = prompt_mask; c[0].len = text_len;
-  return h->e->unet_forward(sample, timestep, c, out, batch2, (hipStream_t)stream);
+  return h->e->unet_forward(sample, timestep, c, out, batch2, latent_h, (hipStream_t)stream);
+}
+int tango_engine_unet_forward(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
+                              const uint8_t* prompt_mask, float* out, int batch2, int text_len, void* stream) {
+  return tango_engine_unet_forward_h(h, sample, timestep, prompt_embeds, prompt_mask, out, batch2, text_len, 0, stream);
 }
 int tango_engine_unet_forward_music(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
                                     const uint8_t* prompt_mask, const float* beat_embeds, const uint8_t* beat_mask,
                                     const float* chord_embeds, const uint8_t* chord_mask, float* out, int batch2, int text_len,
                                     int beat_len, int chord_len, void* stream) {
+  return tango_engine_unet_forward_music_h(h, sample, timestep, prompt_embeds, prompt_mask, beat_embeds, beat_mask, chord_embeds, chord_mask,
+                                           out, batch2, text_len, beat_len, chord_len, 0, stream);
+}
+int tango_engine_unet_forward_music_h(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
+                                      const uint8_t* prompt_mask, const float* beat_embeds, const uint8_t* beat_mask,
+                                      const float* chord_embeds, const uint8_t* chord_mask, float* out, int batch2, int text_len,
+                                      int beat_len, int chord_len, int latent_h, void* stream) {
   Engine::Cond c[3];
   c[0].emb = prompt_embeds; c[0].mask = prompt_mask; c[0].len = text_len;
   c[1].emb = beat_embeds; c[1].mask = beat_mask; c[1].len = beat_len;
   c[2].emb = chord_embeds; c[2].mask = chord_mask; c[2].len = chord_len;
-  return h->e->unet_forward(sample, timestep, c, out, batch2, (hipStream_t)stream);
+  return h->e->unet_forward(sample, timestep, c, out, batch2, latent_h, (hipStream_t)stream);
+}
+int tango_engine_vae_encode_h(tango_engine_t* h, const float* mel, float* moments, int batch, int latent_h, void* stream) {
+  return h->e->vae_encode(mel, moments, batch, latent_h, (hipStream_t)stream);
 }
 int tango_engine_vae_encode(tango_engine_t* h, const float* mel, float* moments, int batch, void* stream) {
-  return h->e->vae_encode(mel, moments, batch, (hipStream_t)stream);
+  return tango_engine_vae_encode_h(h, mel, moments, batch, 0, stream);
+}
+int tango_engine_vae_decode_h(tango_engine_t* h, const float* latents, float* mel, int batch, int latent_h, void* stream) {
+  return h->e->vae_decode(latents, mel, batch, latent_h, (hipStream_t)stream);
 }
 int tango_engine_vae_decode(tango_engine_t* h, const float* latents, float* mel, int batch, void* stream) {
-  return h->e->vae_decode(latents, mel, batch, (hipStream_t)stream);
+  return tango_engine_vae_decode_h(h, latents, mel, batch, 0, stream);
 }
 int tango_engine_vocode(tango_engine_t* h, const float* mel, int16_t* wav, int batch, int mel_frames, int* n_samples, void* stream) {
   return h->e->vocode(mel, wav, batch, mel_frames, n_samples, (hipStream_t)stream);
@@ -2192,8 +2240,11 @@ int tango_engine_encode_text(tango_engine_t* h, const int64_t* input_ids, const 
 }
 
 int tango_engine_profile_unet(tango_engine_t* h, int batch2, int text_len, char* report, int report_cap, void* stream) {
+  return tango_engine_profile_unet_h(h, batch2, text_len, 0, report, report_cap, stream);
+}
+int tango_engine_profile_unet_h(tango_engine_t* h, int batch2, int text_len, int latent_h, char* report, int report_cap, void* stream) {
   std::string r;
-  int rc = h->e->profile_unet(batch2, text_len, r, (hipStream_t)stream);
+  int rc = h->e->profile_unet(batch2, text_len, latent_h, r, (hipStream_t)stream);
   if (report && report_cap > 0) {
     const size_t n = std::min((size_t)report_cap - 1, r.size());
     memcpy(report, r.data(), n);
@@ -2202,9 +2253,12 @@ int tango_engine_profile_unet(tango_engine_t* h, int batch2, int text_len, char*
   return rc;
 }
 int tango_engine_profile_vae(tango_engine_t* h, int batch, char* report, int report_cap, void* stream) {
+  return tango_engine_profile_vae_h(h, batch, 0, report, report_cap, stream);
+}
+int tango_engine_profile_vae_h(tango_engine_t* h, int batch, int latent_h, char* report, int report_cap, void* stream) {
   if (!h || !report || report_cap <= 0) { tango::set_error("tango_engine_profile_vae: null argument"); return -1; }
   std::string r;
-  int rc = h->e->profile_vae(batch, r, (hipStream_t)stream);
+  int rc = h->e->profile_vae(batch, latent_h, r, (hipStream_t)stream);
   if (rc) return rc;
   snprintf(report, (size_t)report_cap, "%s", r.c_str());
   return 0;

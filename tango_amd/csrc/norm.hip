@@ -982,21 +982,22 @@ int launch_layernorm(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy
 }
 
 // ------------------------------------------------------------------------------------------
-// in-place row softmax(x * scale), one 256-thread block per row, row held in registers
+// in-place row softmax(x * scale), one 256-thread block per row, row held in registers: SM_NV 16-byte vectors per thread, or SM_NV_LONG for
+// the rows only the longest clips have (the VAE mid-block attention of a 20 s clip is 8192 columns: 2048 fp32 vectors)
 // ------------------------------------------------------------------------------------------
-static constexpr int SM_NV = 4;
+static constexpr int SM_NV = 4, SM_NV_LONG = 8;
 
-template <typename T>
+template <typename T, int NV>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(T* __restrict__ x, int64_t ld, int cols, float scale) {
   constexpr int EPV = 16 / (int)sizeof(T);
   __shared__ float red[8];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   T* xr = x + (int64_t)blockIdx.x * ld;
   const int VPR = cols / EPV;
-  float f[SM_NV][EPV];
+  float f[NV][EPV];
   float mx = -3.0e38f;
 #pragma unroll
-  for (int j = 0; j < SM_NV; ++j) {
+  for (int j = 0; j < NV; ++j) {
     const int v = tid + j * 256;
     if (v < VPR) {
       unpack16<T>(*(const u32x4*)(xr + v * EPV), f[j]);
@@ -1010,7 +1011,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(T* __restrict__ x, in
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float sum = 0.f;
 #pragma unroll
-  for (int j = 0; j < SM_NV; ++j) {
+  for (int j = 0; j < NV; ++j) {
     const int v = tid + j * 256;
     if (v < VPR) {
 #pragma unroll
@@ -1022,7 +1023,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(T* __restrict__ x, in
   __syncthreads();
   const float inv = 1.0f / (red[4] + red[5] + red[6] + red[7]);
 #pragma unroll
-  for (int j = 0; j < SM_NV; ++j) {
+  for (int j = 0; j < NV; ++j) {
     const int v = tid + j * 256;
     if (v < VPR) {
 #pragma unroll
@@ -1035,8 +1036,9 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(T* __restrict__ x, in
 template <typename T>
 static int sm_launch(void* x, int64_t ld, int rows, int cols, float scale, hipStream_t s) {
   constexpr int EPV = 16 / (int)sizeof(T);
-  if (cols % EPV != 0 || cols / EPV > 256 * SM_NV) TANGO_FAIL("softmax_rows: unsupported cols");
-  hipLaunchKernelGGL((softmax_rows_kernel<T>), dim3((unsigned)rows), dim3(256), 0, s, (T*)x, ld, cols, scale);
+  if (cols % EPV != 0 || cols / EPV > 256 * SM_NV_LONG) TANGO_FAIL("softmax_rows: unsupported cols");
+  if (cols / EPV <= 256 * SM_NV) hipLaunchKernelGGL((softmax_rows_kernel<T, SM_NV>), dim3((unsigned)rows), dim3(256), 0, s, (T*)x, ld, cols, scale);
+  else hipLaunchKernelGGL((softmax_rows_kernel<T, SM_NV_LONG>), dim3((unsigned)rows), dim3(256), 0, s, (T*)x, ld, cols, scale);
   TANGO_HIP(hipGetLastError());
   return 0;
 }

@@ -289,9 +289,11 @@ int tango_op_linear_ln(int dt, const float* x, const float* w, const float* bias
   TANGO_TRY(gemm_init());
   GemmParams px = p;
   px.row_stats = (float*)sc.get((size_t)M * 2 * 4);
-  if (gemm_ln_fold_ok(dt, p)) {
+  // (as Builder::linear: a folded LayerNorm is never split along K)
+  if (gemm_ln_fold_ok(dt, p) && gemm_pick_splitk(dt, p) <= 1) {
     TANGO_TRY(launch_gemm(dt, p, s));
-  } else if (geglu && !residual && px.row_stats && !tuning().no_ln_xstats && gemm_wide_ok(dt, px) && gemm_route(dt, px) == ROUTE_WIDE) {
+  } else if (geglu && !residual && px.row_stats && !tuning().no_ln_xstats && gemm_wide_ok(dt, px) && gemm_route(dt, px) == ROUTE_WIDE &&
+             gemm_pick_splitk(dt, px) <= 1) {
     // the engine's route for the GEGLU projections of levels 1-2: read-only statistics pass + folded weights (gemm_wide.hip XS)
     TANGO_TRY(launch_ln_stats(dt, xt, K, (float*)px.row_stats, M, K, eps, s));
     TANGO_TRY(launch_gemm(dt, px, s));
@@ -337,10 +339,10 @@ const char* tango_debug_linear_route(int dt, int M, int N, int K, int geglu, int
   if (!ln_fold) { out = name(p); return out.c_str(); }
   GemmParams q = p;
   q.ln_fold = 1; q.wsum = (const float*)dummy;
-  if (gemm_ln_fold_ok(dt, q)) { out = name(q); return out.c_str(); }
+  if (gemm_ln_fold_ok(dt, q) && gemm_pick_splitk(dt, q) <= 1) { out = name(q); return out.c_str(); }
   GemmParams q2 = q;
   q2.row_stats = (const float*)dummy;
-  if (geglu && !residual && !tuning().no_ln_xstats && gemm_wide_ok(dt, q2) && gemm_route(dt, q2) == ROUTE_WIDE) { out = name(q2); return out.c_str(); }
+  if (geglu && !residual && !tuning().no_ln_xstats && gemm_wide_ok(dt, q2) && gemm_route(dt, q2) == ROUTE_WIDE && gemm_pick_splitk(dt, q2) <= 1) { out = name(q2); return out.c_str(); }
   out = "layernorm+" + name(p);
   return out.c_str();
 }

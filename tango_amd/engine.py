@@ -8,6 +8,7 @@ import torch
 
 from . import _lib
 from . import weights as W
+from .inpaint import check_latent_h
 
 #: configs/diffusion_model_config.json of the reference (FLAN-T5-large Tango / Tango-full / Tango2)
 UNET_CONFIG_LARGE = dict(
@@ -211,11 +212,18 @@ class Engine:
     def _u8(self, m):
         return m.to(self.device).to(torch.uint8).contiguous() if m is not None else None
 
-    def _check_latents(self, what, x):
-        """the UNet plans are built for ONE latent size: [*, in_channels, latent_h, latent_w]"""
-        want = (self.unet_cfg["in_channels"], self._cfg.latent_h, self._cfg.latent_w)
+    def _height(self, latent_h):
+        """the latent height of a call: None = the engine's default (256, 10 s); else a height of the duration grid
+        (tango_amd.inpaint.duration_geometry: 64, 128, ..., 512).  The C engine keeps one plan per height."""
+        return self._cfg.latent_h if latent_h is None else check_latent_h(latent_h)
+
+    def _check_latents(self, what, x, latent_h=None):
+        """the C ABI sizes its reads from the plan of the call's height: [*, in_channels, H, latent_w] and nothing else.  Returns H."""
+        H = self._height(latent_h)
+        want = (self.unet_cfg["in_channels"], H, self._cfg.latent_w)
         if x.dim() != 4 or tuple(x.shape[1:]) != want:
             raise ValueError("%s must be [B, %d, %d, %d], got %s" % ((what,) + want + (tuple(x.shape),)))
+        return H
 
     def _check_cond(self, what, emb, mask, rows):
         """a condition stream [rows, L, cross_attention_dim] and its optional mask [rows, L]: the engine reads exactly that many
@@ -227,11 +235,12 @@ class Engine:
             raise ValueError("%s mask must be %s, got %s" % (what, tuple(emb.shape[:2]), tuple(mask.shape)))
 
     def unet_forward(self, sample, timestep, encoder_hidden_states, encoder_attention_mask=None, beat_features=None,
-                     chord_features=None, beat_attention_mask=None, chord_attention_mask=None):
-        """UNet2DConditionModel.forward; with beat / chord features, UNet2DConditionModelMusic.forward (Music configs only)"""
+                     chord_features=None, beat_attention_mask=None, chord_attention_mask=None, latent_h=None):
+        """UNet2DConditionModel.forward; with beat / chord features, UNet2DConditionModelMusic.forward (Music configs only).
+        `latent_h`: the height of `sample` when it is not the default 256 (see _height)"""
         x = self._f32(sample)
         enc = self._f32(encoder_hidden_states)
-        self._check_latents("sample", x)
+        H = self._check_latents("sample", x, latent_h)
         B2, L = x.shape[0], enc.shape[1] if enc.dim() == 3 else 0
         mask = self._u8(encoder_attention_mask)
         self._check_cond("encoder_hidden_states", enc, mask, B2)
@@ -247,19 +256,20 @@ class Engine:
                 bm, cm = self._u8(beat_attention_mask), self._u8(chord_attention_mask)
                 self._check_cond("beat_features", beat, bm, B2)
                 self._check_cond("chord_features", chord, cm, B2)
-                _lib.check(self.lib.tango_engine_unet_forward_music(
+                _lib.check(self.lib.tango_engine_unet_forward_music_h(
                     self._h, p(x), int(timestep), p(enc), p(mask), p(beat), p(bm), p(chord), p(cm), p(out), B2, L, beat.shape[1],
-                    chord.shape[1], _stream_ptr()), "unet_forward_music")
+                    chord.shape[1], H, _stream_ptr()), "unet_forward_music")
             else:
-                _lib.check(self.lib.tango_engine_unet_forward(self._h, p(x), int(timestep), p(enc), p(mask), p(out), B2, L,
-                                                              _stream_ptr()), "unet_forward")
+                _lib.check(self.lib.tango_engine_unet_forward_h(self._h, p(x), int(timestep), p(enc), p(mask), p(out), B2, L, H,
+                                                                _stream_ptr()), "unet_forward")
         return out
 
     def denoise(self, latents, prompt_embeds, prompt_mask, timesteps, coef, guidance_scale, prediction_type="v_prediction",
                 rule="ddpm", clip_sample=False, clip_sample_range=1.0, noise=None, seed=0, sample_offset=0, use_graph=True,
                 beat_embeds=None, beat_mask=None, chord_embeds=None, chord_mask=None, prompt_mask_host=None, known_latents=None,
-                latent_mask=None, blend_coef=None, blend_noise=None):
-        """In-place denoise of `latents` [B,8,256,16] (fp32 cuda).  `timesteps` int64 [N] and `coef`
+                latent_mask=None, blend_coef=None, blend_noise=None, latent_h=None):
+        """In-place denoise of `latents` [B,8,H,16] (fp32 cuda; H = 256, or `latent_h`: a height of the duration grid, which every
+        [.., 256, 16] below then follows).  `timesteps` int64 [N] and `coef`
         float32 [N,8] ([N,16] for rule "dpmsolver") are host tables from tango_amd.scheduler.  `prompt_mask_host`: the caller's CPU copy of a `prompt_mask`
         that already lives on the device (the tokenizer's attention mask): the engine then picks its plan from it instead of
         reading the device mask back, i.e. the call does not synchronise the host.
@@ -269,7 +279,7 @@ class Engine:
         `blend_noise` [N,B,8,256,16] (else the device Philox generator's blend stream, keyed by `seed`).  Before the UNet call of every
         loop index i, the latents become add_noise(known, n_i, t_i) * m + (1 - m) * latents; there is no blend after the last step."""
         assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
-        self._check_latents("latents", latents)
+        H = self._check_latents("latents", latents, latent_h)
         enc = self._f32(prompt_embeds)
         mask = prompt_mask.to(self.device).to(torch.uint8).contiguous() if prompt_mask is not None else None
         # a mask that is still on the host (tokenizer output) also travels as a host pointer: the engine then picks its plan without
@@ -322,6 +332,7 @@ class Engine:
         a.sample_offset = int(sample_offset)
         a.use_graph = 1 if use_graph else 0
         a.coef_width = width
+        a.latent_h = H
         keep = []
         if masked is not None:
             kl, lm, bc, bn = masked
@@ -375,11 +386,14 @@ class Engine:
                 raise ValueError("blend_noise must be [num_steps, %s], got %s" % (", ".join(map(str, shape)), tuple(bn.shape)))
         return self._f32(known_latents), self._f32(latent_mask), bc, bn
 
-    def profile_unet(self, batch2: int, text_len: int):
-        """per-op timing of one eager UNet step: list of (label, ms, gflop)"""
+    def profile_unet(self, batch2: int, text_len: int, latent_h: int = 0):
+        """per-op timing of one eager UNet step: list of (label, ms, gflop); `latent_h` 0 = the default height"""
         buf = C.create_string_buffer(1 << 20)
+        if latent_h:
+            check_latent_h(latent_h)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.tango_engine_profile_unet(self._h, batch2, text_len, buf, len(buf), _stream_ptr()), "profile_unet")
+            _lib.check(self.lib.tango_engine_profile_unet_h(self._h, batch2, text_len, int(latent_h), buf, len(buf), _stream_ptr()),
+                       "profile_unet")
         rows = []
         for line in buf.value.decode().splitlines():
             lab, ms, gf = line.rsplit("\t", 2)
@@ -396,9 +410,11 @@ class Engine:
             rows.append((lab, float(ms), float(gf)))
         return rows
 
-    def profile_vae(self, batch: int):
-        """per-op timing of the mel-VAE decoder plan for `batch` latents: list of (label, ms, gflop)"""
-        return self._profile(self.lib.tango_engine_profile_vae, "profile_vae", int(batch))
+    def profile_vae(self, batch: int, latent_h: int = 0):
+        """per-op timing of the mel-VAE decoder plan for `batch` latents of height `latent_h` (0 = the default): list of (label, ms, gflop)"""
+        if latent_h:
+            check_latent_h(latent_h)
+        return self._profile(self.lib.tango_engine_profile_vae_h, "profile_vae", int(batch), int(latent_h))
 
     def profile_vocoder(self, batch: int, frames: int = 1024):
         """per-op timing of the HiFi-GAN plan for `batch` mels of `frames` frames: list of (label, ms, gflop)"""
@@ -417,6 +433,12 @@ class Engine:
         b, n = C.c_uint64(), C.c_int()
         _lib.check(self.lib.tango_engine_plan_stats(self._h, C.byref(b), C.byref(n)), "plan_stats")
         return int(b.value), int(n.value)
+
+    def ring_elems(self):
+        """capacity in floats of the multistep DPM-Solver history ring: 3 * B * C * H * W of the largest such call so far"""
+        n = C.c_uint64()
+        _lib.check(self.lib.tango_engine_ring_elems(self._h, C.byref(n)), "ring_elems")
+        return int(n.value)
 
     def last_step_gflop(self):
         """GFLOP one launch of the last denoise call's step program executes (None before the first denoise call)"""
@@ -470,38 +492,42 @@ class Engine:
         assert nf.value == T
         return mel, lm, en
 
-    def vae_decode(self, latents):
+    def vae_decode(self, latents, latent_h=None):
+        """latents [B, embed_dim, H, 16] -> mel [B, 1, 4H, 64]; H = 256, or `latent_h` (a height of the duration grid)"""
         z = self._f32(latents)
         B = z.shape[0]
         nl = len(self.vae_cfg["ch_mult"])
-        want = (self.vae_cfg.get("embed_dim", 8), self._cfg.latent_h, self._cfg.latent_w)   # the plan's fixed input size
+        H = self._height(latent_h)
+        want = (self.vae_cfg.get("embed_dim", 8), H, self._cfg.latent_w)   # the input size of that height's plan
         if z.dim() != 4 or tuple(z.shape[1:]) != want:
             raise ValueError("vae_decode: latents must be [B, %d, %d, %d], got %s" % (want + (tuple(z.shape),)))
         mel = torch.empty((B, self.vae_cfg["out_ch"], z.shape[2] << (nl - 1), z.shape[3] << (nl - 1)),
                           device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.tango_engine_vae_decode(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(mel.data_ptr()), B,
-                                                        _stream_ptr()), "vae_decode")
+            _lib.check(self.lib.tango_engine_vae_decode_h(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(mel.data_ptr()), B, H,
+                                                          _stream_ptr()), "vae_decode")
         return mel
 
-    def vae_encode(self, mel):
-        """mel [B, 1, 4H, 4W] fp32 -> moments [B, 2*embed_dim, H, W] fp32 (= [mean | logvar]; autoencoder.py:52-58 up to quant_conv)"""
+    def vae_encode(self, mel, latent_h=None):
+        """mel [B, 1, 4H, 4W] fp32 -> moments [B, 2*embed_dim, H, W] fp32 (= [mean | logvar]; autoencoder.py:52-58 up to quant_conv);
+        H = 256, or `latent_h` (a height of the duration grid)"""
         if not self.vae_encoder:
             raise RuntimeError("Engine was created without vae_encoder=True")
         x = self._f32(mel)
         B = x.shape[0]
         nl = len(self.vae_cfg["ch_mult"])
-        # the engine's encoder plan is built for ONE spatial size, (latent_h, latent_w) << (levels - 1) = 1024 x 64 mel bins
-        # (the C ABI sees a bare pointer and copies exactly that many bytes): refuse anything else instead of reading past
-        # `mel` / writing past `moments` (ADVICE r2).  The reference Encoder accepts any H, W; Tango only ever feeds this one.
-        want = (self.vae_cfg.get("in_channels", 1), self._cfg.latent_h << (nl - 1), self._cfg.latent_w << (nl - 1))
+        # an encoder plan is built for ONE spatial size, (H, latent_w) << (levels - 1) mel bins (1024 x 64 at the default height; the
+        # C ABI sees a bare pointer and copies exactly that many bytes): refuse anything else instead of reading past `mel` /
+        # writing past `moments` (ADVICE r2).  The reference Encoder accepts any H, W.
+        H = self._height(latent_h)
+        want = (self.vae_cfg.get("in_channels", 1), H << (nl - 1), self._cfg.latent_w << (nl - 1))
         if x.dim() != 4 or tuple(x.shape[1:]) != want:
             raise ValueError("vae_encode: mel must be [B, %d, %d, %d], got %s" % (want + (tuple(x.shape),)))
         mom = torch.empty((B, 2 * self.vae_cfg.get("embed_dim", 8), x.shape[2] >> (nl - 1), x.shape[3] >> (nl - 1)),
                           device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.tango_engine_vae_encode(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(mom.data_ptr()), B,
-                                                        _stream_ptr()), "vae_encode")
+            _lib.check(self.lib.tango_engine_vae_encode_h(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(mom.data_ptr()), B, H,
+                                                          _stream_ptr()), "vae_encode")
         return mom
 
     def vocoder_samples(self, frames: int) -> int:

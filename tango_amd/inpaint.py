@@ -9,6 +9,60 @@ HOP = 160
 TARGET_FRAMES = 1024
 SEGMENT = TARGET_FRAMES * HOP
 
+#: the clip lengths the engine generates, edits and inpaints: multiples of 2.5 s (the grid of audioldm/pipeline.py:49-50) up to the
+#: 20 s the reference names as its ceiling (pipeline.py:168-170); 10 s is the default everywhere
+DURATION_STEP, MAX_DURATION, DEFAULT_DURATION = 2.5, 20.0, 10.0
+#: latent rows per grid step: int(2.5 * 25.6) (duration_to_latent_t_size, pipeline.py:94-95); the latent width is always 16
+LATENT_ROWS_PER_STEP, LATENT_W = 64, 16
+
+
+def vocoder_samples(frames, hifigan=None):
+    """samples HiFi-GAN makes of `frames` mel frames: every ConvTranspose1d maps L to (L - 1) u - 2 ((k - u) // 2) + k
+    (tango_engine_vocoder_samples; 160 * frames + 32 with the 16 kHz configuration)"""
+    if hifigan is None:
+        from .engine import HIFIGAN_CONFIG as hifigan
+    n = int(frames)
+    for u, k in zip(hifigan["upsample_rates"], hifigan["upsample_kernel_sizes"]):
+        n = (n - 1) * u - 2 * ((k - u) // 2) + k
+    return n
+
+
+def duration_geometry(duration):
+    """`duration` in seconds -> (latent height H = int(duration * 25.6), mel frames 4 H, waveform samples vocoder_samples(4 H)).
+    Only the grid 2.5, 5, ..., 20 s is supported; anything else is a ValueError naming the grid values on either side (nothing is
+    rounded silently)."""
+    try:
+        d = float(duration)
+    except (TypeError, ValueError):
+        raise ValueError("duration must be a number of seconds, got %r" % (duration,))
+    k = d / DURATION_STEP
+    nmax = int(MAX_DURATION / DURATION_STEP)
+    if not (1 <= k <= nmax and k == int(k)):          # (NaN compares false)
+        lo = (int(min(max(k, 1), nmax - 1)) if d == d else 1) * DURATION_STEP
+        raise ValueError("duration %r s is not on the %g s grid up to %g s: the neighbouring durations are %g and %g"
+                         % (duration, DURATION_STEP, MAX_DURATION, lo, lo + DURATION_STEP))
+    h = LATENT_ROWS_PER_STEP * int(k)
+    return h, 4 * h, vocoder_samples(4 * h)
+
+
+def check_latent_h(h):
+    """the latent heights of the duration grid (64, 128, ..., 512): a ValueError for any other"""
+    nmax = int(MAX_DURATION / DURATION_STEP)
+    if int(h) != h or h % LATENT_ROWS_PER_STEP or not 1 <= h // LATENT_ROWS_PER_STEP <= nmax:
+        lo = min(max(int(h) // LATENT_ROWS_PER_STEP, 1), nmax - 1) * LATENT_ROWS_PER_STEP
+        raise ValueError("latent height %r is not one of %d, %d, ..., %d (durations of 2.5 .. 20 s): the neighbouring heights are %d and %d"
+                         % (h, LATENT_ROWS_PER_STEP, 2 * LATENT_ROWS_PER_STEP, nmax * LATENT_ROWS_PER_STEP, lo, lo + LATENT_ROWS_PER_STEP))
+    return int(h)
+
+
+def clip_duration(n_samples):
+    """the smallest grid duration whose mel frames hold a 16 kHz clip of `n_samples` samples; 20 s for anything longer (the clip is
+    then cut).  Unlike the reference's round_up_duration (pipeline.py:49-50), which always adds one more 2.5 s block -- a 5 s clip
+    becomes 7.5 s --, a clip that fills a grid length exactly keeps it."""
+    block = 4 * LATENT_ROWS_PER_STEP * HOP
+    k = (max(int(n_samples), 1) + block - 1) // block
+    return min(k * DURATION_STEP, MAX_DURATION)
+
 
 def latent_mask(batch, time_range=(0.10, 0.15), freq_range=(1.0, 1.0), h=256, w=16):
     """[batch, 1, h, w] fp32 mask as ldm.py:773-777 builds it: ones, rows int(h * t0):int(h * t1) (time) and columns
@@ -20,13 +74,21 @@ def latent_mask(batch, time_range=(0.10, 0.15), freq_range=(1.0, 1.0), h=256, w=
     return m[:, None, ...]
 
 
-def prepare_waveform(audio, segment_length=SEGMENT):
+def prepare_waveform(audio, segment_length=SEGMENT, duration=DEFAULT_DURATION):
     """tools/torch_tools.py:9-54 after the resample: a 1-D 16 kHz clip -> fp32 [segment_length] = normalize_wav (remove the mean,
     divide by max |x| + 1e-8, halve), crop or zero-pad to `segment_length` samples, divide by max |x|, halve.  Reading the file and
-    resampling stay with the caller."""
+    resampling stay with the caller.  `duration` (seconds on the 2.5 s grid) other than the default sets `segment_length` to that
+    duration's mel frames times the hop; None takes clip_duration() of the clip: the clip is zero-padded up to the smallest grid
+    duration that holds it and cut at 20 s."""
     x = torch.as_tensor(np.asarray(audio) if not torch.is_tensor(audio) else audio).to(torch.float32).cpu()
     if x.dim() != 1:
         raise ValueError("prepare_waveform takes one 1-D clip, got shape %s" % (tuple(x.shape),))
+    if duration is None:
+        duration = clip_duration(len(x))
+    if duration != DEFAULT_DURATION:
+        if segment_length != SEGMENT:
+            raise ValueError("prepare_waveform takes a segment_length or a duration, not both")
+        segment_length = duration_geometry(duration)[1] * HOP
     x = x - torch.mean(x)                                       # normalize_wav
     x = x / (torch.max(torch.abs(x)) + 1e-8)
     x = x * 0.5

@@ -14,6 +14,7 @@ from typing import List, Optional
 import torch
 
 from .engine import Engine, normalize_unet_config
+from .inpaint import check_latent_h, duration_geometry
 from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler  # noqa: F401  (re-exported like `from models import DDPMScheduler`)
 from .scheduler import DDIMInverseScheduler, from_diffusers
 
@@ -189,9 +190,10 @@ class AudioDiffusion:
         return torch.cat([ne, pe]), (torch.cat([uam, am]) == 1).to(dev), host.cpu()
 
     # ---- latents -----------------------------------------------------------------------------
-    def prepare_latents(self, batch_size, inference_scheduler, num_channels_latents, dtype, device):
-        """models.py:259-264 (global torch generator on `device`, like the reference)."""
-        shape = (batch_size, num_channels_latents, 256, 16)
+    def prepare_latents(self, batch_size, inference_scheduler, num_channels_latents, dtype, device, latent_h=256):
+        """models.py:259-264 (global torch generator on `device`, like the reference).  `latent_h`: the latent height of the clip
+        length, tango_amd.inpaint.duration_geometry(duration)[0] (256 = 10 s)."""
+        shape = (batch_size, num_channels_latents, check_latent_h(latent_h), 16)
         latents = torch.randn(shape, device=device, dtype=dtype)
         return latents * inference_scheduler.init_noise_sigma
 
@@ -217,11 +219,13 @@ class AudioDiffusion:
 
     def _denoise(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
                  sample_offset, mask_host=None, known_latents=None, latent_mask=None, blend_noise=None, start=0, count=None,
-                 **extra_conditions):
+                 latent_h=256, **extra_conditions):
         """the shared body of the loop of models.py:224-249 / mustango/models.py:563-598: seed derivation, text bucketing, scheduler
         tables, one engine call (`extra_conditions`: the Music UNet's beat / chord streams; `known_latents` / `latent_mask` /
         `blend_noise`: the masked loop of audioldm/ldm.py:724-818, Engine.denoise).  `start` > 0: the truncated loop of an edit over
-        `timesteps[start:]` with the scheduler's truncated tables; `count`: the first `count` steps of a DDIMInverseScheduler."""
+        `timesteps[start:]` with the scheduler's truncated tables; `count`: the first `count` steps of a DDIMInverseScheduler.
+        The clip length is the height of `latents` (a height of the duration grid); `latent_h` sizes the latents drawn here when
+        none are given."""
         cfg_on = guidance_scale > 1.0
         B = prompt_embeds.shape[0] // 2 if cfg_on else prompt_embeds.shape[0]
         if not hasattr(inference_scheduler, "coef_table"):
@@ -235,8 +239,13 @@ class AudioDiffusion:
         else:
             timesteps, coef, window = inference_scheduler.timesteps, inference_scheduler.coef_table(), {}
         if latents is None:
-            latents = self.prepare_latents(B, inference_scheduler, self.unet.config.in_channels, torch.float32, self.device)
+            if known_latents is not None and torch.is_tensor(known_latents) and known_latents.dim() == 4:
+                latent_h = known_latents.shape[2]             # a masked loop runs at the known clip's length
+            latents = self.prepare_latents(B, inference_scheduler, self.unet.config.in_channels, torch.float32, self.device,
+                                           latent_h=latent_h)
         latents = latents.to(self.device, torch.float32).contiguous().clone()
+        if latents.dim() != 4:
+            raise ValueError("latents must be [B, C, H, W], got %s" % (tuple(latents.shape),))
         if boolean_prompt_mask is None:
             boolean_prompt_mask = torch.ones(prompt_embeds.shape[:2], dtype=torch.bool, device=prompt_embeds.device)
         # (the mask is NOT moved here: a host mask reaches the engine as a host pointer too, which spares the call its only host sync)
@@ -256,22 +265,24 @@ class AudioDiffusion:
         self.engine.denoise(latents, pe, pm, timesteps.cpu().numpy(), coef, guidance_scale,
                             prediction_type=c.prediction_type, rule=inference_scheduler.rule, clip_sample=c.clip_sample,
                             clip_sample_range=getattr(c, "clip_sample_range", 1.0), noise=noise, seed=seed,
-                            sample_offset=sample_offset, use_graph=self.use_graph, prompt_mask_host=mask_host, **masking,
-                            **extra_conditions)
+                            sample_offset=sample_offset, use_graph=self.use_graph, prompt_mask_host=mask_host,
+                            latent_h=check_latent_h(latents.shape[2]), **masking, **extra_conditions)
         return latents
 
     @torch.no_grad()
     def inference_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20,
-                                  guidance_scale=3, latents=None, noise=None, seed=None, sample_offset=0, mask_host=None):
+                                  guidance_scale=3, latents=None, noise=None, seed=None, sample_offset=0, mask_host=None, duration=10):
         """Loop of models.py:224-249 given the encoder outputs ([uncond; cond] when guidance > 1).  `mask_host`: optional CPU copy of
-        a device-resident `boolean_prompt_mask` (see Engine.denoise)."""
+        a device-resident `boolean_prompt_mask` (see Engine.denoise).  `duration` (seconds, 2.5 .. 20 on the 2.5 s grid) sizes the
+        initial latents when `latents` is None; given latents carry their own height."""
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
-                             sample_offset, mask_host=mask_host)
+                             sample_offset, mask_host=mask_host, latent_h=duration_geometry(duration)[0])
 
     @torch.no_grad()
     def inference(self, prompt, inference_scheduler, num_steps=20, guidance_scale=3, num_samples_per_prompt=1,
-                  disable_progress=True):
-        """models.py:210-257 (same signature, same return: latents [B*S, 8, 256, 16])."""
+                  disable_progress=True, duration=10):
+        """models.py:210-257 (same signature, same return: latents [B*S, 8, 256, 16]); `duration` seconds of audio instead of 10:
+        latents [B*S, 8, int(duration * 25.6), 16] (audioldm/pipeline.py:94-95,113-126)."""
         host = None
         if guidance_scale > 1.0:
             pe, pm, host = self._encode_text_classifier_free(prompt, num_samples_per_prompt)
@@ -279,7 +290,8 @@ class AudioDiffusion:
             pe, pm = self.encode_text(prompt)
             pe = pe.repeat_interleave(num_samples_per_prompt, 0)
             pm = pm.repeat_interleave(num_samples_per_prompt, 0)
-        return self.inference_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, mask_host=host)
+        return self.inference_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, mask_host=host,
+                                              duration=duration)
 
     # ---- masked-latent inpainting (audioldm/pipeline.py:249-301, ldm.py:724-818, ddim.py:207-233) ------------------------------
     @torch.no_grad()
@@ -398,13 +410,16 @@ class MusicAudioDiffusion(AudioDiffusion):
     @torch.no_grad()
     def inference_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3,
                                   latents=None, noise=None, seed=None, sample_offset=0, *, encoded_beats=None, beat_mask=None,
-                                  encoded_chords=None, chord_mask=None, known_latents=None, latent_mask=None, blend_noise=None):
+                                  encoded_chords=None, chord_mask=None, known_latents=None, latent_mask=None, blend_noise=None,
+                                  duration=10):
         """mustango/models.py:540-598 given the three encoder outputs ([uncond; cond] when guidance > 1); with `known_latents` /
-        `latent_mask` (/ `blend_noise`) the masked loop of AudioDiffusion.inpaint_from_embeddings."""
+        `latent_mask` (/ `blend_noise`) the masked loop of AudioDiffusion.inpaint_from_embeddings.  `duration` sizes the initial
+        latents when none are given, as in AudioDiffusion.inference_from_embeddings."""
         if encoded_beats is None or encoded_chords is None:
             raise ValueError("encoded_beats and encoded_chords are required (mustango/models.py:548-550)")
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
                              sample_offset, known_latents=known_latents, latent_mask=latent_mask, blend_noise=blend_noise,
+                             latent_h=duration_geometry(duration)[0],
                              beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
 
     @torch.no_grad()

@@ -9,7 +9,7 @@ import os
 import torch
 
 from .autoencoder import AutoencoderKL
-from .inpaint import TARGET_FRAMES, latent_mask, prepare_waveform
+from .inpaint import clip_duration, duration_geometry, latent_mask, prepare_waveform
 from .models import AudioDiffusion
 from .scheduler import SD21_SCHEDULER_CONFIG, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 from .stft import wav_to_fbank
@@ -69,21 +69,25 @@ class Tango:
         for i in range(0, len(lst), n):
             yield lst[i:i + n]
 
-    def generate(self, prompt, steps=100, guidance=3, samples=1, disable_progress=True):
-        """ Generate audio for a single prompt string. (tango.py:43-49) """
+    def generate(self, prompt, steps=100, guidance=3, samples=1, disable_progress=True, duration=10):
+        """ Generate audio for a single prompt string. (tango.py:43-49)  `duration`: seconds of audio, 2.5 .. 20 on the 2.5 s grid
+        (audioldm/pipeline.py:113-126 text_to_audio); a ValueError for anything else. """
         with torch.no_grad():
-            latents = self.model.inference([prompt], self.scheduler, steps, guidance, samples, disable_progress=disable_progress)
+            latents = self.model.inference([prompt], self.scheduler, steps, guidance, samples, disable_progress=disable_progress,
+                                           duration=duration)
             mel = self.vae.decode_first_stage(latents)
             wave = self.vae.decode_to_waveform(mel)
         return wave[0]
 
-    def generate_for_batch(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, disable_progress=True):
-        """ Generate audio for a list of prompt strings. (tango.py:51-64) """
+    def generate_for_batch(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, disable_progress=True, duration=10):
+        """ Generate audio for a list of prompt strings. (tango.py:51-64)  `duration`: as in generate(), one length for all. """
+        duration_geometry(duration)
         outputs = []
         for k in range(0, len(prompts), batch_size):
             batch = prompts[k: k + batch_size]
             with torch.no_grad():
-                latents = self.model.inference(batch, self.scheduler, steps, guidance, samples, disable_progress=disable_progress)
+                latents = self.model.inference(batch, self.scheduler, steps, guidance, samples, disable_progress=disable_progress,
+                                               duration=duration)
                 mel = self.vae.decode_first_stage(latents)
                 wave = self.vae.decode_to_waveform(mel)
                 outputs += [item for item in wave]
@@ -91,12 +95,14 @@ class Tango:
             return outputs
         return list(self.chunks(outputs, samples))
 
-    def generate_for_batch_dp(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, group=None):
+    def generate_for_batch_dp(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, group=None, duration=10):
         """Data-parallel `generate_for_batch` over the ranks of the default (or given) torch.distributed group: one
         process per GPU, each holding a full `Tango`.  Every rank makes this call; rank 0's `prompts` are used, the text
         encoder runs on rank 0 only, embeddings travel by one RCCL broadcast per pass of `batch_size * world` prompts,
-        int16 waveforms come back by one gather.  Returns the `generate_for_batch` result on rank 0, None elsewhere."""
+        int16 waveforms come back by one gather.  Returns the `generate_for_batch` result on rank 0, None elsewhere.
+        `duration`: as in generate(); every rank passes the same value."""
         from .parallel import generate_for_batch_dp
+        latent_h, frames, _ = duration_geometry(duration)
 
         def encode(batch, n_per_prompt, g):
             if g > 1.0:
@@ -112,40 +118,46 @@ class Tango:
             # number of ranks (parallel.py docstring)
             b = pe.shape[0] // 2 if guidance > 1.0 else pe.shape[0]
             ecfg = self.model.engine._cfg
-            lat = dp_initial_latents(seed, offset, b, self.model.unet.config.in_channels, ecfg.latent_h, ecfg.latent_w) * self.scheduler.init_noise_sigma
+            lat = dp_initial_latents(seed, offset, b, self.model.unet.config.in_channels, latent_h, ecfg.latent_w) * self.scheduler.init_noise_sigma
             latents = self.model.inference_from_embeddings(pe, pm, self.scheduler, steps, guidance, latents=lat, seed=seed,
                                                            sample_offset=offset)
             return self.vae.engine.vocode(self.vae.decode_first_stage(latents))      # int16 stays on the device
 
         with torch.no_grad():
-            return generate_for_batch_dp(prompts, encode, compute, self.vae.engine.vocoder_samples(1024), self.model.device,
+            return generate_for_batch_dp(prompts, encode, compute, self.vae.engine.vocoder_samples(frames), self.model.device,
                                          guidance=guidance, samples=samples, batch_size=batch_size, group=group)
 
-    def generate_from_embeddings(self, prompt_embeds, boolean_prompt_mask, steps=100, guidance=3, **kw):
-        """Same three calls given the text-encoder outputs (benchmarks / data-parallel workers)."""
+    def generate_from_embeddings(self, prompt_embeds, boolean_prompt_mask, steps=100, guidance=3, duration=10, **kw):
+        """Same three calls given the text-encoder outputs (benchmarks / data-parallel workers); `duration` as in generate()."""
         with torch.no_grad():
-            latents = self.model.inference_from_embeddings(prompt_embeds, boolean_prompt_mask, self.scheduler, steps, guidance, **kw)
+            latents = self.model.inference_from_embeddings(prompt_embeds, boolean_prompt_mask, self.scheduler, steps, guidance,
+                                                           duration=duration, **kw)
             mel = self.vae.decode_first_stage(latents)
             return self.vae.decode_to_waveform(mel)
 
     # ---- masked-latent inpainting (audioldm/pipeline.py:249-301 super_resolution_and_inpainting) ------------------------------
-    def inpaint(self, prompt, audio, time_range=(0.10, 0.15), freq_range=(1.0, 1.0), steps=100, guidance=3, samples=1):
+    def inpaint(self, prompt, audio, time_range=(0.10, 0.15), freq_range=(1.0, 1.0), steps=100, guidance=3, samples=1, duration=10):
         """Regenerate the time span `time_range` and the mel band `freq_range` (fractions of the clip, ldm.py:773-777) of one 16 kHz
         clip `audio` (1-D; reading and resampling are the caller's) under the text `prompt`; the rest keeps the clip's audio.
-        Returns np.int16 [samples, 163872]."""
+        Returns np.int16 [samples, 163872].
+
+        `duration`: seconds the clip is cut or zero-padded to (2.5 .. 20 on the 2.5 s grid; 10 -> 163872 samples, else
+        duration_geometry(duration)[2]).  None: the smallest grid duration that holds the clip (tango_amd.inpaint.clip_duration; a 3 s
+        clip runs as 5 s, a quarter of the latent rows of the default), 20 s for longer clips.  AudioLDM's round_up_duration
+        (pipeline.py:49-50) always adds one more 2.5 s block instead; that is not reproduced."""
         with torch.no_grad():
-            known = self.encode_audio(audio)
+            known = self.encode_audio(audio, duration)
             mask = latent_mask(1, time_range, freq_range, known.shape[2], known.shape[3])
             latents = self.model.inpaint([prompt], known, mask, self.scheduler, steps, guidance, samples)
             mel = self.vae.decode_first_stage(latents)
             return self.vae.decode_to_waveform(mel)
 
     def inpaint_from_embeddings(self, prompt_embeds, boolean_prompt_mask, audio, time_range=(0.10, 0.15), freq_range=(1.0, 1.0),
-                                steps=100, guidance=3, samples=1, **kw):
+                                steps=100, guidance=3, samples=1, duration=10, **kw):
         """`inpaint` given the text-encoder outputs for the `samples` rows ([uncond; cond] when guidance > 1, like
         generate_from_embeddings); `kw` goes to AudioDiffusion.inpaint_from_embeddings (latents, noise, blend_noise, seed, ...)."""
         with torch.no_grad():
-            known = self.encode_audio(audio)
+            known = self.encode_audio(audio, duration)
             rows = prompt_embeds.shape[0] // 2 if guidance > 1.0 else prompt_embeds.shape[0]
             if rows != samples:
                 raise ValueError("prompt_embeds hold %d rows, `samples` is %d" % (rows, samples))
@@ -157,7 +169,7 @@ class Tango:
 
     # ---- audio-to-audio editing (audioldm/pipeline.py:145-247 style_transfer) -----------------------------------------------------
     def edit(self, prompt, audio, strength=0.5, steps=100, guidance=3, samples=1, mode="noise", source_prompt="", time_range=None,
-             freq_range=None, seed=None):
+             freq_range=None, seed=None, duration=10):
         """Edit one 16 kHz clip `audio` (1-D; reading and resampling are the caller's) towards the text `prompt`: the clip's latents
         are moved part of the way into the noise and the last k = int(strength * steps) of `steps` denoise steps run from there.
         Returns np.int16 [samples, 163872].
@@ -171,8 +183,10 @@ class Tango:
         With `time_range` / `freq_range` (fractions of the clip, tango_amd.inpaint.latent_mask) only that region is edited;
         the rest keeps the clip's audio through the masked loop.
 
-        Not reproduced from AudioLDM: the `samples[:, :, :-3, :]` crop of the decoded mel and the `duration` argument
-        (pipeline.py:172-175,241) -- they belong to its variable-length decoder; the engine's plans are one size (10.24 s)."""
+        `duration`: seconds the clip is cut or zero-padded to, as in inpaint() (None: the smallest grid duration that holds the
+        clip, without round_up_duration's extra 2.5 s block); the result has duration_geometry(duration)[2] samples.
+
+        Not reproduced from AudioLDM: the `samples[:, :, :-3, :]` crop of the decoded mel (pipeline.py:241)."""
         with torch.no_grad():
             self._check_edit(mode, steps, strength)
             host = None
@@ -186,10 +200,11 @@ class Tango:
                 se, sm = self.model.encode_text([source_prompt])
                 src = (se.repeat_interleave(samples, 0).float(), sm.repeat_interleave(samples, 0))
             return self._edit(pe.float(), pm, audio, strength, steps, guidance, samples, mode, src, time_range, freq_range, seed,
-                              dict(mask_host=host))
+                              dict(mask_host=host), duration)
 
     def edit_from_embeddings(self, prompt_embeds, boolean_prompt_mask, audio, strength=0.5, steps=100, guidance=3, samples=1,
-                             mode="noise", source_embeds=None, source_mask=None, time_range=None, freq_range=None, seed=None, **kw):
+                             mode="noise", source_embeds=None, source_mask=None, time_range=None, freq_range=None, seed=None,
+                             duration=10, **kw):
         """`edit` given the text-encoder outputs for the `samples` rows ([uncond; cond] when guidance > 1, like
         generate_from_embeddings); mode="invert" takes the source prompt's `source_embeds` [samples, L, d] / `source_mask`
         (conditional rows only).  `kw` goes to AudioDiffusion.edit_from_embeddings (noise, blend_noise, sample_offset)."""
@@ -204,7 +219,7 @@ class Tango:
                     raise ValueError("mode='invert' needs source_embeds with %d rows" % samples)
                 src = (source_embeds, source_mask)
             return self._edit(prompt_embeds, boolean_prompt_mask, audio, strength, steps, guidance, samples, mode, src, time_range,
-                              freq_range, seed, kw)
+                              freq_range, seed, kw, duration)
 
     def _check_edit(self, mode, steps, strength):
         """the argument checks of edit() that need no device"""
@@ -220,8 +235,8 @@ class Tango:
                 raise ValueError("mode='invert' needs a deterministic sampler: set Tango.scheduler to a DDIMScheduler (eta = 0) or a "
                                  "DPMSolverMultistepScheduler, not %s" % type(s).__name__)
 
-    def _edit(self, pe, pm, audio, strength, steps, guidance, samples, mode, src, time_range, freq_range, seed, kw):
-        moments = self.encode_moments(audio)
+    def _edit(self, pe, pm, audio, strength, steps, guidance, samples, mode, src, time_range, freq_range, seed, kw, duration=10):
+        moments = self.encode_moments(audio, duration)
         if seed is None:
             # like the loop's step noise: the Philox key comes from torch's global generator, so torch.manual_seed() fixes the edit
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -254,20 +269,29 @@ class Tango:
                                "snapshot with stft_config.json / pytorch_model_stft.bin, or pass stft= and an AutoencoderKL(with_encoder=True) "
                                "to from_components" % what)
 
-    def encode_moments(self, audio):
-        """one 1-D 16 kHz clip -> the posterior's moments [1, 16, 256, 16] = [mean | logvar]: prepare_waveform -> wav_to_fbank ->
-        the VAE encoder, before any draw (AutoencoderKL.encode_start_latents takes them)"""
-        self._need_encoder("editing")
-        wav = prepare_waveform(audio)[None].to(self.model.device)
-        fbank, _, _ = wav_to_fbank(wav, TARGET_FRAMES, fn_STFT=self.stft)
-        return self.vae.engine.vae_encode(fbank.unsqueeze(1))
+    def _clip_fbank(self, audio, duration):
+        """prepare_waveform -> wav_to_fbank at `duration` seconds (None: clip_duration() of the clip): fbank [1, frames, 64]"""
+        if duration is None:
+            duration = clip_duration(len(audio))
+        frames = duration_geometry(duration)[1]
+        wav = prepare_waveform(audio, duration=duration)[None].to(self.model.device)
+        fbank, _, _ = wav_to_fbank(wav, frames, fn_STFT=self.stft)
+        return fbank
 
-    def encode_audio(self, audio):
+    def encode_moments(self, audio, duration=10):
+        """one 1-D 16 kHz clip -> the posterior's moments [1, 16, 256, 16] = [mean | logvar]: prepare_waveform -> wav_to_fbank ->
+        the VAE encoder, before any draw (AutoencoderKL.encode_start_latents takes them).  `duration` as in inpaint(): the moments
+        are [1, 16, int(duration * 25.6), 16]."""
+        self._need_encoder("editing")
+        fbank = self._clip_fbank(audio, duration)
+        return self.vae.engine.vae_encode(fbank.unsqueeze(1), latent_h=fbank.shape[1] // 4)
+
+    def encode_audio(self, audio, duration=10):
         """one 1-D 16 kHz clip -> known latents [1, 8, 256, 16]: prepare_waveform -> wav_to_fbank -> encode_first_stage ->
-        get_first_stage_encoding (one posterior sample from torch's global generator, ldm.py:180-181)"""
+        get_first_stage_encoding (one posterior sample from torch's global generator, ldm.py:180-181).  `duration` as in
+        inpaint(): the latents are [1, 8, int(duration * 25.6), 16]."""
         self._need_encoder("inpainting")
-        wav = prepare_waveform(audio)[None].to(self.model.device)
-        fbank, _, _ = wav_to_fbank(wav, TARGET_FRAMES, fn_STFT=self.stft)
+        fbank = self._clip_fbank(audio, duration)
         return self.vae.get_first_stage_encoding(self.vae.encode_first_stage(fbank.unsqueeze(1)))
 
 
