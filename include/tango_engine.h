@@ -285,6 +285,9 @@ void tango_tuning_reload(void);
  * LayerNorm statistics), or "layernorm+<route>" when no kernel folds the LayerNorm for that shape.  dtype 1 = fp16, 2 = bf16.
  * tests/test_routing.py pins the measured routing rules of the UNet's shapes with it.  No reference counterpart. */
 const char* tango_debug_linear_route(int dtype, int M, int N, int K, int geglu, int ln_fold, int residual, int vt);
+/* the GroupNorm kernel form tango_op_groupnorm runs for this shape under the current switches: "slab", "coop" (cooperative single launch), "group" (one
+   workgroup per (sample, group)), "two" (statistics + apply launches); "" = refused.  Asks the device for the cooperative kernel's occupancy. */
+const char* tango_debug_groupnorm_form(int dtype, int B, int C, int HW, int groups);
 
 /* ---- per-operator entry points (parity tests; fp32 reference-layout tensors on device) ---- */
 int tango_op_conv2d(int dtype, const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W,

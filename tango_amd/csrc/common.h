@@ -302,7 +302,7 @@ struct GroupNormParams {
   int B, rows, C, groups;
   float eps;
   int act;                        // ACT_NONE / ACT_SILU
-  float* partial;                 // workspace: [B][chunks][groups][2]
+  float* partial;                 // workspace: [B][chunks][groups][2] = sums of x - K and (x - K)^2, K = x[b][row 0][g * cg] (norm.hip gn_pivot)
   float* scale_shift;             // workspace: [B][C][2]
   unsigned* sync = nullptr;       // cross-workgroup barrier words (coop_sync_words() of them, zeroed once, owned by the engine): enables the
                                   // single-launch cooperative kernel when the whole grid is co-resident; null = always two launches
@@ -320,7 +320,9 @@ bool gn_fold_ok(int dtype, const GroupNormParams& p, int N);
 // statistics pass + finalisation: mr [B][groups][2] = mean, rstd (p.partial = workspace of groupnorm_ws_floats)
 bool gn_stats_mr_ok(int dtype, const GroupNormParams& p);
 int launch_gn_stats_mr(int dtype, const GroupNormParams& p, float* mr, hipStream_t s);
-int launch_groupnorm(int dtype, const GroupNormParams& p, hipStream_t s);
+int launch_groupnorm(int dtype, const GroupNormParams& p, hipStream_t s);   // y must not be x: every workgroup reads the groups' pivots in row 0 of x
+// the kernel form launch_groupnorm() picks for this problem under the current switches: "slab", "coop", "group" (one workgroup per (sample, group)), "two"
+const char* groupnorm_form(int dtype, const GroupNormParams& p);
 
 int launch_layernorm(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, const float* gamma,
                      const float* beta, int rows, int C, float eps, hipStream_t s);

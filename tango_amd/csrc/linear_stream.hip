@@ -43,6 +43,10 @@ template <> struct SMma<bf16> {
 // LayerNorm statistics of a row.  fp32 rows: sums of (x - shift) and (x - shift)^2 with shift = the row's first element, so
 // that the one-pass variance E[d^2] - E[d]^2 cancels only to the extent the row's mean differs from one of its own
 // elements (a few std), not to the extent |mean| >> std (fp32 rows with mean / std = 100 lost 3 digits without it).
+// The fp32 kernel centres the FRAGMENT itself (frag_centre, in place, when a k-step is first used) and multiplies the centred
+// values: rstd * (sum_k W' (x - shift) - (mean - shift) * wsum) is the same quantity, but "acc - mean * wsum" then cancels only
+// a few std's worth -- with the raw fragment it cancelled |mean| * |wsum| against itself at the rounding of two differently ordered
+// fp32 sums, times rstd (a constant row, rstd = eps^-1/2: 4e-4 of the output scale; tests/test_norm_conditioning_gpu.py).
 // 16-bit rows: v_dot2c_f32_{f16,bf16} on the packed pairs (products exact, fp32 accumulate), 8 VALU instructions per
 // 8-element fragment instead of 24; no shift - the storage rounding of x (2^-11 / 2^-8 of |mean|) already exceeds what
 // the cancellation loses in fp32 (tests/test_determinism_gpu.py::test_linear_ln_large_mean_and_outliers).
@@ -75,6 +79,13 @@ template <typename T> __device__ __forceinline__ void frag_stats(const u32x4& v,
     s = __builtin_amdgcn_fdot2_f32_bf16(p2, one, s, false); q = __builtin_amdgcn_fdot2_f32_bf16(p2, p2, q, false);
     s = __builtin_amdgcn_fdot2_f32_bf16(p3, one, s, false); q = __builtin_amdgcn_fdot2_f32_bf16(p3, p3, q, false);
   }
+}
+__device__ __forceinline__ void frag_centre(u32x4& v, float shift) {      // fp32 fragment -= shift
+  float e[4];
+  __builtin_memcpy(e, &v, 16);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) e[i] -= shift;
+  __builtin_memcpy(&v, e, 16);
 }
 template <typename T> __device__ __forceinline__ float frag_first(const u32x4& v) {
   T e0;
@@ -204,7 +215,12 @@ __global__ __launch_bounds__(512, 2) void lin_stream_kernel(const GemmParams p) 
 #pragma unroll
       for (int a = 0; a < H; ++a) wf[nb_][a] = *(const u32x4*)(wbase + (hn * H + a) * 16 * ROWB + koff_of(ksn));
       __builtin_amdgcn_sched_barrier(0);
-      if (LN && hh == 0) { frag_stats<T>(xf[slot][0], shift[0], ssum[0], ssq[0]); frag_stats<T>(xf[slot][1], shift[1], ssum[1], ssq[1]); }
+      if (LN && hh == 0) {
+        // first use of this k-step (the slot is refilled behind its last micro-step): fp32 fragments are centred in place, the
+        // statistics and the MFMAs below take the centred values
+        if constexpr (sizeof(T) == 4) { frag_centre(xf[slot][0], shift[0]); frag_centre(xf[slot][1], shift[1]); }
+        frag_stats<T>(xf[slot][0], 0.f, ssum[0], ssq[0]); frag_stats<T>(xf[slot][1], 0.f, ssum[1], ssq[1]);
+      }
 #pragma unroll
       for (int a = 0; a < H; ++a) {
         SMma<T>::run(acc[hh * H + a][0], wf[cb_][a], xf[slot][0]);
@@ -239,7 +255,7 @@ __global__ __launch_bounds__(512, 2) void lin_stream_kernel(const GemmParams p) 
         const float dmu = s / (float)p.K;
         float var = q / (float)p.K - dmu * dmu;
         var = var < 0.f ? 0.f : var;
-        mean[tm] = shift[tm] + dmu; rstd[tm] = rsqrtf(var + p.ln_eps);
+        mean[tm] = dmu; rstd[tm] = rsqrtf(var + p.ln_eps);      // (fp32: the mean of the CENTRED row, which is what the accumulators hold; 16-bit: no shift)
       }
     }
     // The epilogue must not contain dependent global-load chains: vmcnt is in-order, so every load -> use here also

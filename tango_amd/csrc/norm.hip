@@ -1,7 +1,15 @@
 // GroupNorm / LayerNorm / row-softmax kernels for channels-last activations (HBM-bound).
 // Reference ops replaced: native_group_norm (61/UNet step, 24/VAE), native_layer_norm (48), softmax
 // (VAE AttnBlock, audioldm/variational_autoencoder/modules.py:204-230).
-// Statistics are always fp32; 16-byte vector loads; wave64 shuffle reductions.
+// 16-byte vector loads; wave64 shuffle reductions.
+// Statistics: fp32 partial sums, double from the first cross-thread level on -- but never of x and x * x themselves.  A variance formed as
+// Q / n - mean^2 from such sums loses (mean / sigma)^2 2^-24 of its value in the fp32 partials, however exactly the last subtraction is done
+// (a group on an offset of 100 sigma -- ordinary in trained checkpoints -- comes out 1e-3 wrong).  Every GroupNorm form therefore sums
+// d = x - K and d * d about a PIVOT K of its (sample, group): the group's first element x[b][row 0][g cg], which every workgroup reads for
+// itself (gn_pivot), so the partial-sum layout stays two floats per (sample, chunk, group) and its consumers (gn_apply_kernel, gn_coop_kernel,
+// gn_fold_kernel, gn_finalize_kernel) finalise mean = K + S / n, var = Q / n - (S / n)^2 (gn_mean_rstd).  x - K is exact or nearly so (the
+// operands are a few sigma apart), S / n is of the order of sigma, and nothing cancels.  The apply steps are centred too, (x - mean) * (rstd gamma)
+// + beta: a constant group comes out as beta exactly.  LayerNorm (layernorm_kernel, ln_stats_kernel) is two-pass over registers.
 #include <map>
 #include <mutex>
 #include <utility>
@@ -34,6 +42,42 @@ template <typename T> __device__ __forceinline__ u32x4 pack16(const float* f) {
   return v;
 }
 
+// pivot of (sample, group): the group's first element in the sample's first row (x0 = the sample's row 0)
+template <typename T> __device__ __forceinline__ float gn_pivot(const T* __restrict__ x0, int g, int cg) { return to_f(x0[g * cg]); }
+
+// groups of the N consecutive channels c0 .. c0 + N - 1 (one division; a group may be shorter than N)
+template <int N> __device__ __forceinline__ void gn_groups_of(int c0, int cg, int* gi) {
+  int g = c0 / cg, rem = c0 - g * cg;
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    gi[e] = g;
+    if (++rem == cg) { rem = 0; ++g; }
+  }
+}
+// ... and their pivots.  Groups of at least N channels (every UNet / VAE width): the N channels touch at most two groups, whose pivots are two
+// independent loads with no branch between them; shorter groups: one load per channel.
+template <typename T, int N> __device__ __forceinline__ void gn_pivots_of(const T* __restrict__ x0, int c0, int cg, float* kk) {
+  int gi[N];
+  gn_groups_of<N>(c0, cg, gi);
+  if (cg >= N) {
+    const float k0 = gn_pivot(x0, gi[0], cg), k1 = gn_pivot(x0, gi[N - 1], cg);
+#pragma unroll
+    for (int e = 0; e < N; ++e) kk[e] = gi[e] == gi[0] ? k0 : k1;
+  } else {
+#pragma unroll
+    for (int e = 0; e < N; ++e) kk[e] = gn_pivot(x0, gi[e], cg);
+  }
+}
+
+// mean / rstd of a (sample, group) from the sums S of (x - K) and Q of (x - K)^2 over its n elements
+__device__ __forceinline__ void gn_mean_rstd(double K, double S, double Q, double n, float eps, float& mean, float& rstd) {
+  const double dm = S / n;
+  double var = Q / n - dm * dm;
+  if (var < 0.0) var = 0.0;
+  mean = (float)(K + dm);
+  rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
 struct GnGeom {
   int VPR, TPR, RPB, RC, chunks;
 };
@@ -59,7 +103,9 @@ template <typename T> static GnGeom gn_geom(int B, int rows, int C) {
   return g;
 }
 
-template <typename T>
+// NJ: 16-byte vectors per thread and row -- 1 when a row has at most 256 (every UNet width; VPR <= TPR), else GN_NV: the per-element pivots, scales and means
+// are registers, so the common case does not carry three of each
+template <typename T, int NJ>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, int64_t ldx, float* __restrict__ partial,
                                                        int rows, int C, int groups, int VPR, int TPR, int RPB, int RC) {
   constexpr int EPV = 16 / (int)sizeof(T);
@@ -67,14 +113,20 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
   const int tid = threadIdx.x;
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int rl = tid / TPR, tv = tid % TPR;
-  float s[GN_NV][EPV], ss[GN_NV][EPV];
+  const int cg = C / groups;
+  const T* const x0 = x + (int64_t)b * rows * ldx;
+  // sums of d = x - K and d * d, K the pivot of the element's group
+  float s[NJ][EPV], ss[NJ][EPV], kk[NJ][EPV];
 #pragma unroll
-  for (int j = 0; j < GN_NV; ++j)
+  for (int j = 0; j < NJ; ++j) {
+    const int v = tv + j * TPR;
 #pragma unroll
-    for (int e = 0; e < EPV; ++e) { s[j][e] = 0.f; ss[j][e] = 0.f; }
+    for (int e = 0; e < EPV; ++e) { s[j][e] = 0.f; ss[j][e] = 0.f; kk[j][e] = 0.f; }
+    if (rl < RPB && v < VPR) gn_pivots_of<T, EPV>(x0, v * EPV, cg, kk[j]);
+  }
   const int r0 = chunk * RC, r1 = min(rows, r0 + RC);
   if (rl < RPB) {
-    if (VPR <= TPR) {
+    if constexpr (NJ == 1) {
       // one 16-byte piece per thread and row (every UNet width): four rows per iteration with all four loads issued before the
       // first use -- the plain loop kept one load per thread in flight, ~30 KB per CU, short of what HBM latency x bandwidth
       // needs; the accumulation order per thread (row order) is unchanged, so the statistics are bit-identical
@@ -89,27 +141,27 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
             float f[EPV];
             unpack16<T>(v4[u], f);
 #pragma unroll
-            for (int e = 0; e < EPV; ++e) { s[0][e] += f[e]; ss[0][e] += f[e] * f[e]; }
+            for (int e = 0; e < EPV; ++e) { const float d = f[e] - kk[0][e]; s[0][e] += d; ss[0][e] += d * d; }
           }
         }
         for (; r < r1; r += RPB) {
           float f[EPV];
           unpack16<T>(*(const u32x4*)(x + ((int64_t)b * rows + r) * ldx + tv * EPV), f);
 #pragma unroll
-          for (int e = 0; e < EPV; ++e) { s[0][e] += f[e]; ss[0][e] += f[e] * f[e]; }
+          for (int e = 0; e < EPV; ++e) { const float d = f[e] - kk[0][e]; s[0][e] += d; ss[0][e] += d * d; }
         }
       }
     } else {
     for (int r = r0 + rl; r < r1; r += RPB) {
       const T* row = x + ((int64_t)b * rows + r) * ldx;
 #pragma unroll
-      for (int j = 0; j < GN_NV; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         const int v = tv + j * TPR;
         if (v < VPR) {
           float f[EPV];
           unpack16<T>(*(const u32x4*)(row + v * EPV), f);
 #pragma unroll
-          for (int e = 0; e < EPV; ++e) { s[j][e] += f[e]; ss[j][e] += f[e] * f[e]; }
+          for (int e = 0; e < EPV; ++e) { const float d = f[e] - kk[j][e]; s[j][e] += d; ss[j][e] += d * d; }
         }
       }
     }
@@ -119,7 +171,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
   for (int pass = 0; pass < RPB; ++pass) {
     if (rl == pass) {
 #pragma unroll
-      for (int j = 0; j < GN_NV; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         const int v = tv + j * TPR;
         if (v < VPR) {
 #pragma unroll
@@ -133,7 +185,6 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
     }
     __syncthreads();
   }
-  const int cg = C / groups;
   if (tid < groups) {
     float a = 0.f, q = 0.f;
     for (int c = tid * cg; c < (tid + 1) * cg; ++c) { a += sm[0][c]; q += sm[1][c]; }
@@ -145,7 +196,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
 // Normalise + affine (+ SiLU).  The former gn_finalize launch is folded in: every workgroup reduces the per-chunk partial
 // sums of ITS sample (chunks x groups pairs, double accumulation in a fixed order -- deterministic) and derives scale / shift
 // for its own channels; 61 launches per UNet step fewer.
-template <typename T>
+template <typename T, int NJ>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, int64_t ldx, T* __restrict__ y, int64_t ldy,
                                                        const float* __restrict__ partial, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, int chunks, int groups, float eps,
@@ -156,6 +207,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
   const int tid = threadIdx.x;
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int cg = C / groups;
+  const float piv = tid < groups ? gn_pivot(x + (int64_t)b * rows * ldx, tid, cg) : 0.f;     // (requested first: it is needed behind the reduction below)
   // Per-sample reduction of the chunk partials, spread over the whole workgroup: `lanes` threads per group each sum every
   // lanes-th chunk (double, fixed order), the group's first thread then adds the `lanes` sub-sums in fixed order.  (Round 2
   // had ONE thread per group walk all chunks: at B = 8 that is a chain of 128 loads at the head of every workgroup -- the
@@ -180,35 +232,28 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
     }
   }
   __syncthreads();
-  if (tid < groups) {
-    const double n = (double)rows * cg;
-    const double a = tot_s[0][tid], q = tot_s[1][tid];
-    const double mean = a / n;
-    double var = q / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    mean_s[tid] = (float)mean;
-    rstd_s[tid] = (float)(1.0 / sqrt(var + (double)eps));
-  }
+  if (tid < groups)
+    gn_mean_rstd((double)piv, tot_s[0][tid], tot_s[1][tid], (double)rows * cg, eps, mean_s[tid], rstd_s[tid]);
   __syncthreads();
   const int rl = tid / TPR, tv = tid % TPR;
   if (rl >= RPB) return;
-  float sc[GN_NV][EPV], sh[GN_NV][EPV];
+  float sc[NJ][EPV], sh[NJ][EPV], mu[NJ][EPV];
 #pragma unroll
-  for (int j = 0; j < GN_NV; ++j) {
+  for (int j = 0; j < NJ; ++j) {
     const int v = tv + j * TPR;
     if (v < VPR) {
+      int gi[EPV];
+      gn_groups_of<EPV>(v * EPV, cg, gi);
 #pragma unroll
       for (int e = 0; e < EPV; ++e) {
         const int c = v * EPV + e;
-        const int g = c / cg;
-        const float s1 = rstd_s[g] * gamma[c];
-        sc[j][e] = s1; sh[j][e] = beta[c] - mean_s[g] * s1;
+        sc[j][e] = rstd_s[gi[e]] * gamma[c]; sh[j][e] = beta[c]; mu[j][e] = mean_s[gi[e]];
       }
     }
   }
   const int r0 = chunk * RC, r1 = min(rows, r0 + RC);
   int rstart = r0 + rl;
-  if (VPR <= TPR && tv < VPR) {
+  if (NJ == 1 && tv < VPR) {
     // four rows per iteration, loads first (see gn_stats_kernel)
     for (; rstart + 3 * RPB < r1; rstart += 4 * RPB) {
       u32x4 v4[4];
@@ -220,7 +265,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
         unpack16<T>(v4[u], f);
 #pragma unroll
         for (int e = 0; e < EPV; ++e) {
-          float t = f[e] * sc[0][e] + sh[0][e];
+          float t = (f[e] - mu[0][e]) * sc[0][e] + sh[0][e];
           if (act == ACT_SILU) t = silu_f(t);
           f[e] = t;
         }
@@ -232,14 +277,14 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
     const T* row = x + ((int64_t)b * rows + r) * ldx;
     T* orow = y + ((int64_t)b * rows + r) * ldy;
 #pragma unroll
-    for (int j = 0; j < GN_NV; ++j) {
+    for (int j = 0; j < NJ; ++j) {
       const int v = tv + j * TPR;
       if (v < VPR) {
         float f[EPV];
         unpack16<T>(*(const u32x4*)(row + v * EPV), f);
 #pragma unroll
         for (int e = 0; e < EPV; ++e) {
-          float t = f[e] * sc[j][e] + sh[j][e];
+          float t = (f[e] - mu[j][e]) * sc[j][e] + sh[j][e];
           if (act == ACT_SILU) t = silu_f(t);
           f[e] = t;
         }
@@ -269,12 +314,13 @@ __global__ __launch_bounds__(1024) void gn_fused_small_kernel(const T* __restric
   const int cg = C / groups, hp = cg >> 1;  // pairs per row of this group
   const int n = rows * hp;
   const T* xb = x + (int64_t)b * rows * ldx + g * cg;
+  const float K = gn_pivot(xb, 0, cg);         // the group's first element: the sums below are of d = x - K and d * d
   float v[GNS_NP][2];
   float s = 0.f, q = 0.f;
 #pragma unroll
   for (int i = 0; i < GNS_NP; ++i) {
     const int e = tid + i * 1024;
-    v[i][0] = 0.f; v[i][1] = 0.f;
+    v[i][0] = K; v[i][1] = K;                  // (slots past the end: d = 0)
     if (e < n) {
       const int r = e / hp, c = (e - r * hp) * 2;
       const P pv = *(const P*)(xb + (int64_t)r * ldx + c);
@@ -284,18 +330,15 @@ __global__ __launch_bounds__(1024) void gn_fused_small_kernel(const T* __restric
     }
   }
 #pragma unroll
-  for (int i = 0; i < GNS_NP; ++i) { s += v[i][0] + v[i][1]; q += v[i][0] * v[i][0] + v[i][1] * v[i][1]; }
+  for (int i = 0; i < GNS_NP; ++i) { const float d0 = v[i][0] - K, d1 = v[i][1] - K; s += d0 + d1; q += d0 * d0 + d1 * d1; }
   s = wave_sum(s); q = wave_sum(q);
   if (lane == 0) { red[0][w] = s; red[1][w] = q; }
   __syncthreads();
   double S = 0.0, Q = 0.0;
 #pragma unroll
   for (int i = 0; i < 16; ++i) { S += (double)red[0][i]; Q += (double)red[1][i]; }
-  const double nn = (double)rows * cg;
-  const double mean = S / nn;
-  double var = Q / nn - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const float mu = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)eps));
+  float mu, rstd;
+  gn_mean_rstd((double)K, S, Q, (double)rows * cg, eps, mu, rstd);
   T* yb = y + (int64_t)b * rows * ldy + g * cg;
 #pragma unroll
   for (int i = 0; i < GNS_NP; ++i) {
@@ -306,7 +349,7 @@ __global__ __launch_bounds__(1024) void gn_fused_small_kernel(const T* __restric
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const float sc = rstd * gamma[g * cg + c + k];
-        float t = v[i][k] * sc + (beta[g * cg + c + k] - mu * sc);
+        float t = (v[i][k] - mu) * sc + beta[g * cg + c + k];
         if (act == ACT_SILU) t = silu_f(t);
         t2[k] = from_f<T>(t);
       }
@@ -321,7 +364,7 @@ __global__ __launch_bounds__(1024) void gn_fused_small_kernel(const T* __restric
 // Slab form (round 6): the GroupNorms of UNet levels 2-3 (<= 256 rows per sample; C = 1280 / 2560, i.e. groups of 40 / 80 channels = whole 16-byte
 // vectors).  One 320-thread workgroup owns G adjacent groups of one sample -- a rows x (G cg) slab, 320 contiguous bytes (20 vectors) per row: it is read
 // ONCE as 16-byte vectors into registers (thread = (row of a 16-row pass, vector): rows / 16 vectors per thread, every load in flight before the first
-// use; its group, gamma and beta are fixed), the per-group (sum, sum of squares) go through LDS in a fixed order to a double-precision mean / variance, and the slab is normalised (+ affine, SiLU) from the registers and written once.
+// use; its group, gamma and beta are fixed), the per-group sums of (x - K, (x - K)^2) about the group's pivot K go through LDS in a fixed order to a double-precision mean / variance, and the slab is normalised (+ affine, SiLU) from the registers and written once.
 // One launch, one read, one write: the two-launch path reads these tensors twice (they are 10-84 MB at B = 32: three passes through the memory side),
 // and the (sample, group)-per-workgroup kernel above fetches them as 4-byte pairs with 1024-thread workgroups (19 us per launch for a 10-MB tensor).
 // The choice depends on (rows, C, groups, dtype) only -- never on the batch -- so a sample's result does not depend on what it is batched with.
@@ -334,13 +377,15 @@ __global__ __launch_bounds__(GSL_TH, 3) void gn_slab_kernel(const T* __restrict_
   constexpr int EPV = 16 / (int)sizeof(T);
   __shared__ f32x2 part[GSL_TH];
   __shared__ f32x2 part2[GSL_MAXG][GSL_RPP];
-  __shared__ float mean_s[GSL_MAXG], rstd_s[GSL_MAXG];
+  __shared__ float mean_s[GSL_MAXG], rstd_s[GSL_MAXG], piv_s[GSL_MAXG];
   // thread -> (row of the pass r0, vector of the slab row vv): its group, gamma and beta are fixed; vector i is row r0 + 16 i
   const int tid = threadIdx.x, r0 = tid / GSL_VPS, vv = tid - r0 * GSL_VPS, grp = vv / VPG;
   const int b = blockIdx.y, cg = C / groups, c0 = blockIdx.x * G * cg + vv * EPV;
   const T* xp = x + ((int64_t)b * rows + r0) * ldx + c0;
   T* yp = y + ((int64_t)b * rows + r0) * ldy + c0;
   const int64_t xs = (int64_t)GSL_RPP * ldx, ys = (int64_t)GSL_RPP * ldy;
+  // pivot of this thread's group: the group's first element in the sample's first row, requested ahead of the slab; the sums are of d = x - K and d * d
+  const float K = gn_pivot(x + (int64_t)b * rows * ldx, blockIdx.x * G + grp, cg);
   u32x4 v[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) v[i] = *(const u32x4*)(xp + i * xs);         // rows == 16 NV (launcher): no tail
@@ -356,11 +401,12 @@ __global__ __launch_bounds__(GSL_TH, 3) void gn_slab_kernel(const T* __restrict_
     float f[EPV];
     unpack16<T>(v[i], f);
 #pragma unroll
-    for (int u = 0; u < EPV; ++u) { s += f[u]; q += f[u] * f[u]; }
+    for (int u = 0; u < EPV; ++u) { const float d = f[u] - K; s += d; q += d * d; }
     __builtin_amdgcn_sched_barrier(0);                   // one vector at a time (hipcc otherwise unpacks all NV vectors at once: 8 NV registers, spills at NV = 16)
   }
   // per-group sums in a fixed order: the VPG vectors of a (pass row, group), then the 16 pass rows (double)
   part[tid] = f32x2{s, q};
+  if (r0 == 0 && vv == grp * VPG) piv_s[grp] = K;
   __syncthreads();
   if (tid < G * GSL_RPP) {
     const int k = tid / GSL_RPP, rr = tid - k * GSL_RPP;
@@ -373,12 +419,7 @@ __global__ __launch_bounds__(GSL_TH, 3) void gn_slab_kernel(const T* __restrict_
     double S = 0.0, Q = 0.0;
 #pragma unroll
     for (int rr = 0; rr < GSL_RPP; ++rr) { S += (double)part2[tid][rr].x; Q += (double)part2[tid][rr].y; }
-    const double nn = (double)rows * cg;
-    const double mean = S / nn;
-    double var = Q / nn - mean * mean;
-    if (var < 0.0) var = 0.0;
-    mean_s[tid] = (float)mean;
-    rstd_s[tid] = (float)(1.0 / sqrt(var + (double)eps));
+    gn_mean_rstd((double)piv_s[tid], S, Q, (double)rows * cg, eps, mean_s[tid], rstd_s[tid]);
   }
   __syncthreads();
   // (the packed vectors are made opaque here: hipcc otherwise keeps the 8 NV CONVERTED values of the statistics loop alive across the barriers
@@ -386,16 +427,16 @@ __global__ __launch_bounds__(GSL_TH, 3) void gn_slab_kernel(const T* __restrict_
 #pragma unroll
   for (int i = 0; i < NV; ++i) asm volatile("" : "+v"(v[i]));
   const float mu = mean_s[grp], rstd = rstd_s[grp];
-  float sc[EPV], sh[EPV];
+  float sc[EPV];
 #pragma unroll
-  for (int u = 0; u < EPV; ++u) { sc[u] = rstd * ga[u]; sh[u] = be[u] - mu * sc[u]; }
+  for (int u = 0; u < EPV; ++u) sc[u] = rstd * ga[u];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     float f[EPV];
     unpack16<T>(v[i], f);
 #pragma unroll
     for (int u = 0; u < EPV; ++u) {
-      float t = f[u] * sc[u] + sh[u];
+      float t = (f[u] - mu) * sc[u] + be[u];
       if (act == ACT_SILU) t = silu_f(t);
       f[u] = t;
     }
@@ -426,7 +467,7 @@ template <typename T, int NV> static void gn_slab_go(const GroupNormParams& p, i
 // hipGraph at 4-5 us and the (sample, group)-per-workgroup kernel above at 16 us per call (64 workgroups, 4-byte strided loads);
 // the two-launch path reads x twice.  Here the grid of the STATISTICS pass keeps its rows in registers across a per-sample
 // rendezvous and normalises them in place of a second launch: one read, one write, one dispatch, 16-byte coalesced accesses.
-//   phase 1  every workgroup loads NV x RPB rows (all loads in flight), reduces per-group (sum, sum of squares) of its rows through
+//   phase 1  every workgroup loads NV x RPB rows (all loads in flight), reduces per-group sums of (x - K, (x - K)^2) of its rows (K: the group's pivot) through
 //            LDS and publishes them to partial[b][chunk][group] with agent-scope stores;
 //   barrier  per sample: arrival counter + generation word (agent-scope atomics; the last arriver resets the counter and bumps
 //            the generation, so the words are back at rest when the kernel ends and serve the next launch of any geometry);
@@ -476,22 +517,30 @@ __global__ __launch_bounds__(256, 4) void gn_coop_kernel(const T* __restrict__ x
   // phase-1 reduction of one chunk: per-thread sums over its NV rows (ascending), per-channel sums across the RPB row slots through
   // LDS (ascending), per-group sums over the group's channels (ascending); published with agent-scope stores.  `own`: rows come from
   // the registers loaded above; otherwise (fallback) they are re-read from x -- the SAME values in the SAME order, hence the same bits.
+  // pivots of this thread's channels' groups: the sums are of d = x - K and d * d
+  float kk[EPV];
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) kk[e] = 0.f;
+  if (active) gn_pivots_of<T, EPV>((const T*)xb, tv * EPV, cg, kk);
+  const float piv = tid < groups ? gn_pivot((const T*)xb, tid, cg) : 0.f;     // of the group this thread finalises in phase 2
   auto reduce_chunk = [&](int ch, bool own) {
     float s[EPV], ss[EPV];
 #pragma unroll
     for (int e = 0; e < EPV; ++e) { s[e] = 0.f; ss[e] = 0.f; }
 #pragma unroll
-    for (int u = 0; u < NV; ++u) {       // rows past the end contribute zeros
+    for (int u = 0; u < NV; ++u) {       // rows past the end contribute nothing
+      const int r = ch * RC + rl + u * RPB;
       u32x4 w = v[u];
       if (!own) {
-        const int r = ch * RC + rl + u * RPB;
         w = u32x4{0u, 0u, 0u, 0u};
         if (active && r < rows) w = *(const u32x4*)(xb + (((int64_t)r * ldx + tv * EPV) * (int64_t)sizeof(T)));
       }
       float f[EPV];
       unpack16<T>(w, f);
+      if (r < rows) {
 #pragma unroll
-      for (int e = 0; e < EPV; ++e) { s[e] += f[e]; ss[e] += f[e] * f[e]; }
+        for (int e = 0; e < EPV; ++e) { const float d = f[e] - kk[e]; s[e] += d; ss[e] += d * d; }
+      }
     }
     for (int pass = 0; pass < RPB; ++pass) {
       if (rl == pass) {
@@ -577,24 +626,17 @@ __global__ __launch_bounds__(256, 4) void gn_coop_kernel(const T* __restrict__ x
     }
   }
   __syncthreads();
-  if (tid < groups) {
-    const double n = (double)rows * cg;
-    const double a = tot_s[0][tid], q = tot_s[1][tid];
-    const double mean = a / n;
-    double var = q / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    mean_s[tid] = (float)mean;
-    rstd_s[tid] = (float)(1.0 / sqrt(var + (double)eps));
-  }
+  if (tid < groups)
+    gn_mean_rstd((double)piv, tot_s[0][tid], tot_s[1][tid], (double)rows * cg, eps, mean_s[tid], rstd_s[tid]);
   __syncthreads();
   if (!active) return;
-  float sc[EPV], sh[EPV];
+  float sc[EPV], sh[EPV], mu[EPV];
+  int gi[EPV];
+  gn_groups_of<EPV>(tv * EPV, cg, gi);
 #pragma unroll
   for (int e = 0; e < EPV; ++e) {
     const int c = tv * EPV + e;
-    const int g = c / cg;
-    const float s1 = rstd_s[g] * gamma[c];
-    sc[e] = s1; sh[e] = beta[c] - mean_s[g] * s1;
+    sc[e] = rstd_s[gi[e]] * gamma[c]; sh[e] = beta[c]; mu[e] = mean_s[gi[e]];
   }
 #pragma unroll
   for (int u = 0; u < NV; ++u) {
@@ -604,7 +646,7 @@ __global__ __launch_bounds__(256, 4) void gn_coop_kernel(const T* __restrict__ x
       unpack16<T>(v[u], f);
 #pragma unroll
       for (int e = 0; e < EPV; ++e) {
-        float t = f[e] * sc[e] + sh[e];
+        float t = (f[e] - mu[e]) * sc[e] + sh[e];
         if (act == ACT_SILU) t = silu_f(t);
         f[e] = t;
       }
@@ -630,20 +672,44 @@ static int coop_capacity(const void* kfn) {
   return cap;
 }
 
+// the cooperative kernel can take this problem: its geometry fits the kernel and the workspace, and the whole grid is co-resident
 template <typename T, int NV>
-static bool gn_coop_try(const GroupNormParams& p, hipStream_t s) {
+static bool gn_coop_ok(const GroupNormParams& p) {
   constexpr int EPV = 16 / (int)sizeof(T);
   const int VPR = p.C / EPV;
   if (VPR > 256 || p.groups > 256 || p.B > COOP_SYNC_SLOTS) return false;
   const int RPB = 256 / VPR, RC = RPB * NV;
   const int chunks = (p.rows + RC - 1) / RC;
   if (chunks > p.rows / 8 + 2 || chunks > 2048) return false;     // the workspace bound of groupnorm_ws_floats
+  const long cap = coop_capacity(reinterpret_cast<const void*>(gn_coop_kernel<T, NV>));
+  return (long)p.B * chunks <= cap * 3 / 4;                       // the whole grid must be co-resident, with room to spare
+}
+
+template <typename T, int NV>
+static void gn_coop_go(const GroupNormParams& p, hipStream_t s) {
+  constexpr int EPV = 16 / (int)sizeof(T);
+  const int VPR = p.C / EPV, RPB = 256 / VPR, RC = RPB * NV;
+  const int chunks = (p.rows + RC - 1) / RC;
   auto kfn = gn_coop_kernel<T, NV>;
-  const long cap = coop_capacity(reinterpret_cast<const void*>(kfn));
-  if ((long)p.B * chunks > cap * 3 / 4) return false;             // the whole grid must be co-resident, with room to spare
   hipLaunchKernelGGL(kfn, dim3((unsigned)chunks, (unsigned)p.B), dim3(256), 0, s, (const T*)p.x, p.ldx, (T*)p.y, p.ldy, p.gamma, p.beta,
                      p.partial, p.sync, p.rows, p.C, p.groups, p.eps, p.act, VPR, RPB, tuning().gn_coop_force_fb ? 1 : 0);
-  return true;
+}
+
+template <typename T> static void gn_stats_go(const GroupNormParams& p, const GnGeom& g, hipStream_t s) {
+  const dim3 grid((unsigned)g.chunks, (unsigned)p.B);
+  if (g.VPR <= g.TPR)
+    hipLaunchKernelGGL((gn_stats_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)p.x, p.ldx, p.partial, p.rows, p.C, p.groups, g.VPR, g.TPR, g.RPB, g.RC);
+  else
+    hipLaunchKernelGGL((gn_stats_kernel<T, GN_NV>), grid, dim3(256), 0, s, (const T*)p.x, p.ldx, p.partial, p.rows, p.C, p.groups, g.VPR, g.TPR, g.RPB, g.RC);
+}
+template <typename T> static void gn_apply_go(const GroupNormParams& p, const GnGeom& g, hipStream_t s) {
+  const dim3 grid((unsigned)g.chunks, (unsigned)p.B);
+  if (g.VPR <= g.TPR)
+    hipLaunchKernelGGL((gn_apply_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)p.x, p.ldx, (T*)p.y, p.ldy, p.partial, p.gamma, p.beta, g.chunks, p.groups, p.eps,
+                       p.rows, p.C, p.act, g.VPR, g.TPR, g.RPB, g.RC);
+  else
+    hipLaunchKernelGGL((gn_apply_kernel<T, GN_NV>), grid, dim3(256), 0, s, (const T*)p.x, p.ldx, (T*)p.y, p.ldy, p.partial, p.gamma, p.beta, g.chunks, p.groups, p.eps,
+                       p.rows, p.C, p.act, g.VPR, g.TPR, g.RPB, g.RC);
 }
 
 size_t groupnorm_ws_floats(int B, int rows, int C, int groups) {
@@ -653,48 +719,79 @@ size_t groupnorm_ws_floats(int B, int rows, int C, int groups) {
   return (size_t)B * chunks * groups * 2 + (size_t)B * C * 2;
 }
 
+enum GnForm { GN_FORM_SLAB, GN_FORM_COOP, GN_FORM_GROUP, GN_FORM_TWO };
+
+// Which GroupNorm form takes this problem (one decision, used by the launcher AND by groupnorm_form() for the tests).
+// Where the cooperative kernel wins (profiles/r4_c11_gn_coop_modes_ab_b1.txt, B = 1): against the (sample, group)-per-workgroup kernel
+// on tensors with >= 1024 rows per sample (C=320 rows=4096 x13 0.438 -> 0.227 ms, C=640 rows=1024 x11 0.198 -> 0.162, C=1280
+// rows=1024 0.034 -> 0.023); at 256 / 64 rows that kernel's 9-13 us beat the ~10-us rendezvous, and against the two-launch path
+// (tensors > 8 MB: B >= 8) the cooperative kernel loses 5-20 % everywhere.  TANGO_GN_COOP_ALL=1 (tests) lifts the size rule.
+// round 6: the slab form where the shape takes it (levels 2-3 of the UNet: rows <= 256, groups of whole 16-byte vectors) -- a function of the shape
+// only, never of the batch (TANGO_GN_SLAB=0: A/B)
 template <typename T>
-static int gn_launch(const GroupNormParams& p, hipStream_t s) {
+static GnForm gn_pick(const GroupNormParams& p) {
+  const int cg = p.C / p.groups;
+  if (tuning().gn_slab) {
+    int G = 0, VPG = 0, nv = 0;
+    if ((((uintptr_t)p.gamma | (uintptr_t)p.beta) & 15) == 0 && gn_slab_geom<T>(p.rows, p.C, p.groups, G, VPG, nv)) return GN_FORM_SLAB;
+  }
+  const bool coop_size = (size_t)p.B * p.rows * p.C * sizeof(T) <= ((size_t)8 << 20) && p.rows >= 1024;
+  // (16 rows per thread: 128 VGPRs + spills at 4 waves / SIMD -- same bytes resident, not built)
+  if (p.sync && !tuning().no_gn_coop && (coop_size || tuning().gn_coop_all) && gn_coop_ok<T, 8>(p)) return GN_FORM_COOP;
+  if ((cg & 1) == 0 && (int64_t)p.rows * (cg / 2) <= (int64_t)1024 * GNS_NP && (p.ldx & 1) == 0 && (p.ldy & 1) == 0 &&
+      (size_t)p.B * p.rows * p.C * sizeof(T) <= ((size_t)tuning().gn_small_mb << 20))
+    return GN_FORM_GROUP;
+  return GN_FORM_TWO;
+}
+
+template <typename T>
+static int gn_check(const GroupNormParams& p) {
   constexpr int EPV = 16 / (int)sizeof(T);
   if (p.C % EPV != 0 || p.C > GN_MAXC || p.C % p.groups != 0 || p.groups > 256) TANGO_FAIL("groupnorm: unsupported C/groups");
   if (p.C / EPV > 256 * GN_NV) TANGO_FAIL("groupnorm: C too large");
   if ((p.ldx * (int64_t)sizeof(T)) % 16 || (p.ldy * (int64_t)sizeof(T)) % 16) TANGO_FAIL("groupnorm: ld alignment");
-  const int cg = p.C / p.groups;
-  // Where the cooperative kernel wins (profiles/r4_c11_gn_coop_modes_ab_b1.txt, B = 1): against the (sample, group)-per-workgroup kernel
-  // below on tensors with >= 1024 rows per sample (C=320 rows=4096 x13 0.438 -> 0.227 ms, C=640 rows=1024 x11 0.198 -> 0.162, C=1280
-  // rows=1024 0.034 -> 0.023); at 256 / 64 rows that kernel's 9-13 us beat the ~10-us rendezvous, and against the two-launch path
-  // (tensors > 8 MB: B >= 8) the cooperative kernel loses 5-20 % everywhere.  TANGO_GN_COOP_ALL=1 (tests) lifts the size rule.
-  // round 6: the slab form where the shape takes it (levels 2-3 of the UNet: rows <= 256, groups of whole 16-byte vectors) -- a function of the shape
-  // only, never of the batch (TANGO_GN_SLAB=0: A/B)
-  if (tuning().gn_slab) {
-    int G = 0, VPG = 0, nv = 0;
-    if ((((uintptr_t)p.gamma | (uintptr_t)p.beta) & 15) == 0 && gn_slab_geom<T>(p.rows, p.C, p.groups, G, VPG, nv)) {
+  // every workgroup reads its groups' pivots in row 0 of x (gn_pivot) -- in the two-launch form while another workgroup already writes row 0 of y
+  if (p.x == p.y) TANGO_FAIL("groupnorm: in place (y == x) is not supported");
+  return 0;
+}
+
+template <typename T>
+static int gn_launch(const GroupNormParams& p, hipStream_t s) {
+  TANGO_TRY(gn_check<T>(p));
+  switch (gn_pick<T>(p)) {
+    case GN_FORM_SLAB: {
+      int G = 0, VPG = 0, nv = 0;
+      gn_slab_geom<T>(p.rows, p.C, p.groups, G, VPG, nv);
       if (nv == 4) gn_slab_go<T, 4>(p, G, VPG, s);
       else if (nv == 8) gn_slab_go<T, 8>(p, G, VPG, s);
       else gn_slab_go<T, 16>(p, G, VPG, s);
-      TANGO_HIP(hipGetLastError());
-      return 0;
+      break;
+    }
+    case GN_FORM_COOP: gn_coop_go<T, 8>(p, s); break;
+    case GN_FORM_GROUP:
+      hipLaunchKernelGGL((gn_fused_small_kernel<T>), dim3((unsigned)p.groups, (unsigned)p.B), dim3(1024), 0, s, (const T*)p.x, p.ldx,
+                         (T*)p.y, p.ldy, p.gamma, p.beta, p.rows, p.C, p.groups, p.eps, p.act);
+      break;
+    case GN_FORM_TWO: {
+      const GnGeom g = gn_geom<T>(p.B, p.rows, p.C);
+      gn_stats_go<T>(p, g, s);
+      gn_apply_go<T>(p, g, s);
+      break;
     }
   }
-  const bool coop_size = (size_t)p.B * p.rows * p.C * sizeof(T) <= ((size_t)8 << 20) && p.rows >= 1024;
-  if (p.sync && !tuning().no_gn_coop && (coop_size || tuning().gn_coop_all)) {
-    if (gn_coop_try<T, 8>(p, s)) { TANGO_HIP(hipGetLastError()); return 0; }      // (16 rows per thread: 128 VGPRs + spills at 4 waves / SIMD -- same bytes resident, not built)
-  }
-  if ((cg & 1) == 0 && (int64_t)p.rows * (cg / 2) <= (int64_t)1024 * GNS_NP && (p.ldx & 1) == 0 && (p.ldy & 1) == 0 &&
-      (size_t)p.B * p.rows * p.C * sizeof(T) <= ((size_t)tuning().gn_small_mb << 20)) {
-    hipLaunchKernelGGL((gn_fused_small_kernel<T>), dim3((unsigned)p.groups, (unsigned)p.B), dim3(1024), 0, s, (const T*)p.x, p.ldx,
-                       (T*)p.y, p.ldy, p.gamma, p.beta, p.rows, p.C, p.groups, p.eps, p.act);
-    TANGO_HIP(hipGetLastError());
-    return 0;
-  }
-  const GnGeom g = gn_geom<T>(p.B, p.rows, p.C);
-  dim3 grid((unsigned)g.chunks, (unsigned)p.B);
-  hipLaunchKernelGGL((gn_stats_kernel<T>), grid, dim3(256), 0, s, (const T*)p.x, p.ldx, p.partial, p.rows, p.C, p.groups,
-                     g.VPR, g.TPR, g.RPB, g.RC);
-  hipLaunchKernelGGL((gn_apply_kernel<T>), grid, dim3(256), 0, s, (const T*)p.x, p.ldx, (T*)p.y, p.ldy, p.partial, p.gamma, p.beta,
-                     g.chunks, p.groups, p.eps, p.rows, p.C, p.act, g.VPR, g.TPR, g.RPB, g.RC);
   TANGO_HIP(hipGetLastError());
   return 0;
+}
+
+// the form launch_groupnorm() runs for this problem under the current switches: "slab", "coop", "group", "two" ("" = it refuses the problem)
+const char* groupnorm_form(int dtype, const GroupNormParams& p) {
+  static const char* const names[] = {"slab", "coop", "group", "two"};
+  switch (dtype) {
+    case DT_F32: return gn_check<float>(p) ? "" : names[gn_pick<float>(p)];
+    case DT_F16: return gn_check<f16>(p) ? "" : names[gn_pick<f16>(p)];
+    case DT_BF16: return gn_check<bf16>(p) ? "" : names[gn_pick<bf16>(p)];
+  }
+  return "";
 }
 
 
@@ -707,7 +804,7 @@ static int gn_launch(const GroupNormParams& p, hipStream_t s) {
 // chunk partials exactly as gn_apply_kernel does (double, fixed order).
 // ------------------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(256) void gn_fold_kernel(const float* __restrict__ partial, const T* __restrict__ W, int64_t Kp,
+__global__ __launch_bounds__(256) void gn_fold_kernel(const T* __restrict__ x, int64_t ldx, const float* __restrict__ partial, const T* __restrict__ W, int64_t Kp,
                                                       const float* __restrict__ bias, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, T* __restrict__ Wf, float* __restrict__ bf,
                                                       int chunks, int groups, float eps, int rows, int C, int N) {
@@ -716,6 +813,7 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const float* __restrict__ 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.y;
   const int cg = C / groups;
+  const float piv = tid < groups ? gn_pivot(x + (int64_t)b * rows * ldx, tid, cg) : 0.f;     // (requested first: needed behind the reduction below)
   int lanes = 256 / groups;
   if (lanes > 8) lanes = 8;
   {
@@ -736,14 +834,8 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const float* __restrict__ 
     }
   }
   __syncthreads();
-  if (tid < groups) {
-    const double n = (double)rows * cg;
-    const double mean = tot_s[0][tid] / n;
-    double var = tot_s[1][tid] / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    mean_s[tid] = (float)mean;
-    rstd_s[tid] = (float)(1.0 / sqrt(var + (double)eps));
-  }
+  if (tid < groups)
+    gn_mean_rstd((double)piv, tot_s[0][tid], tot_s[1][tid], (double)rows * cg, eps, mean_s[tid], rstd_s[tid]);
   __syncthreads();
   const int n = blockIdx.x * 4 + wave;
   if (n >= N) return;
@@ -768,13 +860,15 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const float* __restrict__ 
 // normalises on its own way in (ff_fused.hip qkv_stat_kernel, norm mode 2: Transformer2DModel.norm -> proj_in without the normalised tensor).
 // Same arithmetic as gn_apply_kernel's per-workgroup finalisation (double, fixed order), done ONCE per sample instead of once per workgroup.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partial, float* __restrict__ mr, int chunks, int groups,
-                                                          float eps, int rows, int cg) {
+template <typename T>
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const T* __restrict__ x, int64_t ldx, const float* __restrict__ partial, float* __restrict__ mr,
+                                                          int chunks, int groups, float eps, int rows, int cg) {
   __shared__ double part_s[2][256];
   const int tid = threadIdx.x, b = blockIdx.x;
   int lanes = 256 / groups;
   if (lanes > 8) lanes = 8;
   const int g = tid / lanes, sub = tid - g * lanes;
+  const float piv = g < groups && sub == 0 ? gn_pivot(x + (int64_t)b * rows * ldx, g, cg) : 0.f;     // (requested first: needed behind the reduction below)
   if (g < groups) {
     double a = 0.0, q = 0.0;
     for (int ch = sub; ch < chunks; ch += lanes) {
@@ -787,20 +881,17 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
   if (g < groups && sub == 0) {
     double a = 0.0, q = 0.0;
     for (int k = 0; k < lanes; ++k) { a += part_s[0][tid + k]; q += part_s[1][tid + k]; }
-    const double n = (double)rows * cg;
-    const double mean = a / n;
-    double var = q / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    mr[((int64_t)b * groups + g) * 2] = (float)mean;
-    mr[((int64_t)b * groups + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    float mean, rstd;
+    gn_mean_rstd((double)piv, a, q, (double)rows * cg, eps, mean, rstd);
+    mr[((int64_t)b * groups + g) * 2] = mean;
+    mr[((int64_t)b * groups + g) * 2 + 1] = rstd;
   }
 }
 
 template <typename T> static int gn_stats_mr_t(const GroupNormParams& p, float* mr, hipStream_t s) {
   const GnGeom g = gn_geom<T>(p.B, p.rows, p.C);
-  hipLaunchKernelGGL((gn_stats_kernel<T>), dim3((unsigned)g.chunks, (unsigned)p.B), dim3(256), 0, s, (const T*)p.x, p.ldx, p.partial, p.rows,
-                     p.C, p.groups, g.VPR, g.TPR, g.RPB, g.RC);
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)p.B), dim3(256), 0, s, p.partial, mr, g.chunks, p.groups, p.eps, p.rows, p.C / p.groups);
+  gn_stats_go<T>(p, g, s);
+  hipLaunchKernelGGL((gn_finalize_kernel<T>), dim3((unsigned)p.B), dim3(256), 0, s, (const T*)p.x, p.ldx, p.partial, mr, g.chunks, p.groups, p.eps, p.rows, p.C / p.groups);
   TANGO_HIP(hipGetLastError());
   return 0;
 }
@@ -828,9 +919,8 @@ bool gn_fold_ok(int dtype, const GroupNormParams& p, int N) {
 template <typename T>
 static int gn_stats_fold_t(const GroupNormParams& p, const void* W, int64_t Kp, const float* bias, int N, void* Wf, float* bf, hipStream_t s) {
   const GnGeom g = gn_geom<T>(p.B, p.rows, p.C);
-  hipLaunchKernelGGL((gn_stats_kernel<T>), dim3((unsigned)g.chunks, (unsigned)p.B), dim3(256), 0, s, (const T*)p.x, p.ldx, p.partial, p.rows,
-                     p.C, p.groups, g.VPR, g.TPR, g.RPB, g.RC);
-  hipLaunchKernelGGL((gn_fold_kernel<T>), dim3((unsigned)((N + 3) / 4), (unsigned)p.B), dim3(256), 0, s, p.partial, (const T*)W, Kp, bias,
+  gn_stats_go<T>(p, g, s);
+  hipLaunchKernelGGL((gn_fold_kernel<T>), dim3((unsigned)((N + 3) / 4), (unsigned)p.B), dim3(256), 0, s, (const T*)p.x, p.ldx, p.partial, (const T*)W, Kp, bias,
                      p.gamma, p.beta, (T*)Wf, bf, g.chunks, p.groups, p.eps, p.rows, p.C, N);
   TANGO_HIP(hipGetLastError());
   return 0;

@@ -734,6 +734,16 @@ int tango_op_groupnorm(int dt, const float* x, const float* gamma, const float* 
   return 0;
 }
 
+const char* tango_debug_groupnorm_form(int dt, int B, int C, int HW, int groups) {
+  // the GroupNorm form tango_op_groupnorm(dt, ..., B, C, HW, groups, ...) runs under the current switches (same params: dense rows, barrier words present)
+  char* const dummy = (char*)(uintptr_t)0x10000;           // aligned, never dereferenced: the choice looks at alignment and shape only
+  GroupNormParams p;
+  p.x = dummy; p.ldx = C; p.y = dummy + 16; p.ldy = C; p.gamma = (const float*)dummy; p.beta = (const float*)dummy; p.B = B; p.rows = HW; p.C = C;
+  p.groups = groups; p.eps = 1e-5f; p.act = ACT_NONE; p.partial = (float*)dummy; p.scale_shift = (float*)dummy; p.sync = (unsigned*)dummy;
+  if (groups <= 0 || C <= 0) return "";
+  return groupnorm_form(dt, p);
+}
+
 int tango_op_layernorm(int dt, const float* x, const float* gamma, const float* beta, float* out, int rows, int C, float eps,
                        void* stream) {
   hipStream_t s = (hipStream_t)stream;
