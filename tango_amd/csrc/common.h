@@ -234,7 +234,7 @@ bool conv_halo_ok(int dtype, const GemmParams& p);
 int launch_conv_halo(int dtype, const GemmParams& p, const unsigned char* zero_page, hipStream_t s);
 bool gemm_wide_ok(int dtype, const GemmParams& p);   // 256 x 320 ping-pong LDS-DMA GEMM for the big 16-bit linears (gemm_wide.hip)
 int launch_gemm_wide(int dtype, const GemmParams& p, hipStream_t s);
-int gemm_wide_pers_cus();                            // workgroups the persistent 256 x 320 GEMM launches (the device's CU count)
+bool gemm_wide_persistent(int dtype, const GemmParams& p);   // launch_gemm_wide() runs this problem in the persistent form (TANGO_WIDE_PERS tiles per CU-workgroup)
 bool gemm_duo_ok(int dtype, const GemmParams& p);    // 256 x 160 LDS-DMA GEMM, two workgroups per CU, for the short-K 16-bit linears (gemm_duo.hip)
 int launch_gemm_duo(int dtype, const GemmParams& p, hipStream_t s);
 // a kernel with the LayerNorm folded into the weights takes this problem (else: LayerNorm kernel + plain GEMM)
@@ -261,6 +261,47 @@ int launch_linear_stream(int dtype, const GemmParams& p, hipStream_t s);
 inline bool gemm_ln_fold_ok(int dtype, const GemmParams& p) { return linear_stream_ok(dtype, p) || gemm_wide_ok(dtype, p) || gemm_duo_ok(dtype, p); }
 int launch_fold_ln(int dtype, const void* W, int64_t Kp, const float* gamma, const float* beta, const float* bias_in, void* Wo,
                    float* bias_out, float* wsum, int N, int K, hipStream_t s);
+
+// ---- the planner (gemm.hip): every decision about how a GEMM-shaped op runs, made in one place for the engine's plan builders, the
+// per-op wrappers and the route queries.  It looks at shapes, strides and pointer ALIGNMENT only (never at memory): buffers the chosen
+// form needs -- row statistics, the normalised copy, the split-K workspace -- are allocated by the caller afterwards. ----
+enum LinearForm : int {
+  LIN_PLAIN = 0,       // no LayerNorm in front
+  LIN_LN_FOLD,         // LayerNorm folded into the weights, row statistics inside the GEMM kernel
+  LIN_LN_XSTATS,       // launch_ln_stats into g.row_stats, then the folded weights on the 256 x 320 GEMM (XS)
+  LIN_LN_MATERIAL,     // launch_layernorm into a dense [M][K] copy (g.A / g.lda), then the plain GEMM
+};
+struct GemmPlan {
+  int form = LIN_PLAIN;
+  int splitk = 1;          // what gemm_apply_splitk() will set on the problem
+  int route = ROUTE_NONE;  // the kernel family of the (split) problem
+  bool pers = false;       // ROUTE_WIDE in its persistent form
+  bool phase = false;      // upsampler conv as four 2x2-tap phase convolutions (the caller sets GemmParams::Wph)
+  GemmParams g;            // the problem to launch: the weights of the form chosen; form-specific buffers still to be set by the caller
+};
+// the LayerNorm-folded copy of a linear's weights (launch_fold_ln); Wln null = there is none
+struct LnFold {
+  const void* Wln = nullptr;
+  const float* bln = nullptr;
+  const float* wsum = nullptr;
+  float eps = 1e-5f;
+};
+GemmPlan plan_gemm(int dtype, const GemmParams& p);   // split-K factor, route and persistent form of a problem as it stands
+// p: the plain problem (plain weights and bias); ln: a LayerNorm over K precedes it.  Owns the rules: a folded LayerNorm is never split
+// along K; the XS form is for GEGLU without residual (TANGO_NO_LN_XSTATS: never); else LayerNorm is materialised
+GemmPlan plan_linear(int dtype, const GemmParams& p, const LnFold* ln = nullptr);
+// p: a conv2d_problem(); allow_phase: the caller has (or can make) the phase weights
+GemmPlan plan_conv3x3(int dtype, const GemmParams& p, bool allow_phase);
+std::string plan_name(const GemmPlan& pl);   // what the route queries answer: "wide+xstats+pers", "layernorm+tile+splitk", "conv_wide+phase", ...
+// apply the split-K policy to a problem about to be launched: p.splitk and p.ws = alloc_ws(floats) when it splits; returns the factor
+template <typename AllocWs> int gemm_apply_splitk(int dtype, GemmParams& p, AllocWs&& alloc_ws) {
+  const int sk = gemm_pick_splitk(dtype, p);
+  if (sk > 1) {
+    p.splitk = sk;
+    p.ws = alloc_ws((size_t)sk * p.M * p.N);
+  }
+  return sk;
+}
 
 // ---- fused level-0 feed-forward (ff_fused.hip): out = x + W2 GEGLU(W1' LayerNorm(x) + b1') + b2 ----
 struct FFParams {
@@ -465,3 +506,5 @@ int launch_rmsnorm(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, 
 int launch_t5_pos_bias(const float* table, const int* bucket, float* out, int heads, int L, hipStream_t s);
 
 }  // namespace tango
+
+#include "problem.h"   // the constructors of GemmParams (host only)

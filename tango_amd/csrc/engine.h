@@ -42,15 +42,6 @@ struct Arena {
   void release(size_t m) { off = m; }
 };
 
-// a dense (no gather) problem out[M, N] = A[M, K] @ W[N, K]^T with row strides lda / Kp
-inline GemmParams dense_gemm(const void* A, int64_t lda, const void* W, int64_t Kp, int M, int N, int K) {
-  GemmParams p;
-  p.A = A; p.lda = lda; p.W = W; p.Kp = Kp;
-  p.M = M; p.N = N; p.K = K; p.Cin = K;
-  p.mode = GATHER_1D; p.rows_pb = M; p.Lin = M; p.Lout = M; p.taps = 1;
-  return p;
-}
-
 struct TView {
   void* p = nullptr;
   int64_t ld = 0;

@@ -84,13 +84,12 @@ struct Builder {
   }
   void gemm(GemmParams p, const char* what = "gemm") {
     const int d = dt;
-    const int sk = gemm_pick_splitk(d, p);
-    if (sk > 1) {   // the workspace may alias later temporaries: the whole program is stream-ordered
+    const int sk = gemm_apply_splitk(d, p, [&](size_t floats) {   // the workspace may alias later temporaries: the whole program is stream-ordered
       const size_t m = A.mark();
-      p.splitk = sk;
-      p.ws = alloc_f32((size_t)sk * p.M * p.N);
+      float* ws = alloc_f32(floats);
       A.release(m);
-    }
+      return ws;
+    });
     char buf[160];
     snprintf(buf, sizeof buf, "%s M=%d N=%d K=%d%s%s", what, p.M, p.N, p.K, p.batch > 1 ? " batched" : "", sk > 1 ? " splitK" : "");
     push([p, d](hipStream_t s) { return launch_gemm(d, p, s); }, buf, 2.0 * p.M * (double)p.N * p.K * p.batch);
@@ -111,38 +110,24 @@ struct Builder {
     apply(p, o);
     if (o.vt) { p.epi = EPI_VT; p.vt = o.vt; p.vt_n0 = o.vt_n0; p.vt_S = o.vt_S; p.vt_ld = o.vt_ld; p.vt_perm = o.vt_perm; }
     if (o.ln) {
-      GemmParams q = p;
-      q.W = w.Wln; q.bias = w.bln; q.ln_fold = 1; q.ln_eps = o.ln->eps; q.wsum = w.wsum;
-      // (a folded LayerNorm is never split along K: the split-K policy does not ask the 256 x 320 GEMM, so with the big tiles forced
-      //  onto a small problem it would split what only the unsplit kernel can fold)
-      if (w.Wln && gemm_ln_fold_ok(dt, q) && gemm_pick_splitk(dt, q) <= 1) {
-        const int rq = gemm_route(dt, q);
-        gemm(q, rq == ROUTE_WIDE ? "linear+ln(wide)" : rq == ROUTE_DUO ? "linear+ln(duo)" : "linear+ln(stream)");
-        return;
-      }
-      // GEGLU projections the in-loop-statistics kernels do not take (levels 1-2): row statistics in a read-only pass, then the
-      // folded weights on the 256 x 320 GEMM -- LayerNorm(x) is never written (round 4)
-      if (w.Wln && p.epi == EPI_GEGLU && !tuning().no_ln_xstats) {
-        const size_t m = A.mark();
-        float* st = alloc_f32((size_t)rows * 2);
-        GemmParams q2 = q;
-        q2.row_stats = st;
-        if (gemm_wide_ok(dt, q2) && gemm_route(dt, q2) == ROUTE_WIDE && gemm_pick_splitk(dt, q2) <= 1) {
-          const int d = dt;
-          const void* xp = x.p; const int64_t ldx = x.ld; const int r = (int)rows, c = o.ln->C; const float eps = o.ln->eps;
-          push([=](hipStream_t s) { return launch_ln_stats(d, xp, ldx, st, r, c, eps, s); }, "ln_stats C=" + std::to_string(c));
-          gemm(q2, "linear+ln(xstats)");
-          A.release(m);
-          return;
-        }
-        A.release(m);
-      }
-      // fallback: materialise LayerNorm(x), then the plain GEMM
+      const LnFold f{w.Wln, w.bln, w.wsum, o.ln->eps};
+      GemmPlan pl = plan_linear(dt, p, &f);
       const size_t m = A.mark();
-      TView t = alloc(rows, o.ln->C);
-      layernorm(x, rows, *o.ln, t);
-      p.A = t.p; p.lda = t.ld;
-      gemm(p, "linear");
+      if (pl.form == LIN_LN_FOLD) {
+        gemm(pl.g, pl.route == ROUTE_WIDE ? "linear+ln(wide)" : pl.route == ROUTE_DUO ? "linear+ln(duo)" : "linear+ln(stream)");
+      } else if (pl.form == LIN_LN_XSTATS) {   // LayerNorm(x) is never written: a read-only statistics pass feeds the folded weights
+        float* st = alloc_f32((size_t)rows * 2);
+        pl.g.row_stats = st;
+        const int d = dt;
+        const void* xp = x.p; const int64_t ldx = x.ld; const int r = (int)rows, c = o.ln->C; const float eps = o.ln->eps;
+        push([=](hipStream_t s) { return launch_ln_stats(d, xp, ldx, st, r, c, eps, s); }, "ln_stats C=" + std::to_string(c));
+        gemm(pl.g, "linear+ln(xstats)");
+      } else {                                 // materialise LayerNorm(x), then the plain GEMM
+        TView t = alloc(rows, o.ln->C);
+        layernorm(x, rows, *o.ln, t);
+        pl.g.A = t.p; pl.g.lda = t.ld;
+        gemm(pl.g, "linear");
+      }
       A.release(m);
       return;
     }
@@ -155,15 +140,14 @@ struct Builder {
         if (o.rowvec_done) *o.rowvec_done = true;
       }
     }
-    const int route = gemm_pick_splitk(dt, p) > 1 ? ROUTE_TILE : gemm_route(dt, p);
+    const int route = plan_linear(dt, p).route;      // (a split linear runs on the tile kernel)
     gemm(p, route == ROUTE_STREAM ? "linear(stream)" : route == ROUTE_WIDE ? "linear(wide)" : route == ROUTE_DUO ? "linear(duo)" : "linear");
   }
 
-  // 3x3 conv (pad 1) on NHWC: output grid B x H x W; source B x Hin x Win (nearest-upsampled x2 when ups)
-  void conv3x3(const TView& x, int B, int H, int W, int Hin, int Win, int stride, int ups, const WMat& w, const TView& out,
-               const GOpt& o = GOpt()) {
+  // 3x3 conv on NHWC: source B x H x W (nearest-upsampled x2 first when ups), padding o.pad; the output grid is conv2d_problem()'s
+  void conv3x3(const TView& x, int B, int H, int W, int stride, int ups, const WMat& w, const TView& out, const GOpt& o = GOpt()) {
     if (w.im2col) {
-      // tiny Cin: materialise im2col rows then plain GEMM
+      // tiny Cin (stride 1, pad 1): materialise im2col rows then plain GEMM
       const size_t m = A.mark();
       TView col = alloc((int64_t)B * H * W, (int)w.Kp);
       const int d = dt;
@@ -174,13 +158,11 @@ struct Builder {
       A.release(m);
       return;
     }
-    GemmParams p;
+    GemmParams p = conv2d_problem(B, w.Cin, H, W, w.N, stride, ups, o.pad);
     p.A = x.p; p.lda = x.ld; p.W = w.W; p.Kp = w.Kp; p.bias = o.use_bias ? w.b : nullptr;
-    p.M = B * H * W; p.N = w.N; p.K = w.K; p.Cin = w.Cin;
-    p.mode = GATHER_2D; p.H = H; p.Wd = W; p.Hin = Hin; p.Win = Win; p.stride = stride; p.ups = ups; p.pad = o.pad;
     p.out = out.p; p.ldo = out.ld;
     apply(p, o);
-    if (ups && w.Wph && gemm_pick_splitk(dt, p) <= 1 && gemm_route(dt, p) == ROUTE_CONV_WIDE && conv_ups_phase_ok(dt, p)) {
+    if (plan_conv3x3(dt, p, w.Wph != nullptr).phase) {
       // four 2x2-tap phase convolutions on the source grid: label and flop count say what is executed (K = 4 Cin)
       p.Wph = w.Wph;
       const int d = dt;
@@ -212,12 +194,13 @@ struct Builder {
     float* ws = alloc_f32(nf);
     gp.partial = ws; gp.scale_shift = nullptr;
     p.W = Wf; p.rowvec = bf;
-    if (gemm_pick_splitk(dt, p) > 1 || !gemm_rowvec_ok(dt, p)) { A.release(m); return false; }
+    const GemmPlan pl = plan_gemm(dt, p);
+    if (pl.splitk > 1 || !gemm_rowvec_ok(dt, p)) { A.release(m); return false; }
     const int d = dt;
     const void* Wsrc = w.W; const int64_t Kp = w.Kp; const float* bsrc = w.b; const int N = w.N;
     push([=](hipStream_t s) { return launch_gn_stats_fold(d, gp, Wsrc, Kp, bsrc, N, Wf, bf, s); },
          "groupnorm(fold) C=" + std::to_string(gn.C) + " rows=" + std::to_string(rows));
-    gemm(p, gemm_route(dt, p) == ROUTE_DUO ? "linear(duo)" : "linear(wide)");
+    gemm(p, pl.route == ROUTE_DUO ? "linear(duo)" : "linear(wide)");
     // (the folded weights are consumed by the GEMM that follows on the same stream: the slab region may be reused behind it)
     A.release(m);
     return true;
@@ -324,7 +307,7 @@ struct Builder {
     TView t1 = alloc(rows, w.cout);
     GOpt o1;
     if (w.has_temb) { o1.bias2 = w.temb_table; o1.bias2_stride = w.cout; }
-    conv3x3(t0, B, H, W, H, W, 1, 0, w.c1, t1, o1);
+    conv3x3(t0, B, H, W, 1, 0, w.c1, t1, o1);
     TView t2 = alloc(rows, w.cout);
     groupnorm(t1, B, H * W, w.n2, groups, ACT_SILU, t2);
     TView R = x;
@@ -334,7 +317,7 @@ struct Builder {
     }
     GOpt o2;
     o2.residual = &R;
-    conv3x3(t2, B, H, W, H, W, 1, 0, w.c2, out, o2);
+    conv3x3(t2, B, H, W, 1, 0, w.c2, out, o2);
     A.release(m);
   }
 
@@ -1116,10 +1099,8 @@ int Engine::finalize_weights() {
 // (embeddings.py:22-62,200-212; resnet.py:573-577) for all N steps at once, fp32 on the f32 MFMA path
 // ================================================================================================
 static GemmParams f32_linear(const float* x, int64_t lda, const WLinF32& w, float* out, int M, int a_act, int e_act) {
-  GemmParams p;
-  p.A = x; p.lda = lda; p.W = w.W; p.Kp = w.K; p.bias = w.b;
-  p.M = M; p.N = w.N; p.K = w.K; p.Cin = w.K;
-  p.mode = GATHER_1D; p.rows_pb = M; p.Lin = M; p.Lout = M; p.taps = 1;
+  GemmParams p = dense_gemm(x, lda, w.W, w.K, M, w.N, w.K);
+  p.bias = w.b;
   p.out = out; p.ldo = w.N;
   p.a_act = a_act; p.e_act = e_act;
   return p;
@@ -1253,7 +1234,7 @@ int Engine::build_unet(UNetPlan& P, Arena& A, bool record) {
   const bool shared = P.mode == UNetMode::CfgShared;
   const int Bh = B2 / 2;
   TView h = skip_dst();                                    // conv_in output = skip 0
-  b.conv3x3(xin, shared ? Bh : B2, HH(0), WW(0), HH(0), WW(0), 1, 0, conv_in, h);
+  b.conv3x3(xin, shared ? Bh : B2, HH(0), WW(0), 1, 0, conv_in, h);
   if (shared) {
     const int d = dt, c = ch[0];
     const int64_t rh = rows_at(0) / 2, ld = h.ld;
@@ -1283,7 +1264,7 @@ int Engine::build_unet(UNetPlan& P, Arena& A, bool record) {
     }
     if (down[i].has_ds) {
       TView o = skip_dst();
-      b.conv3x3(h, B2, HH(i + 1), WW(i + 1), HH(i), WW(i), 2, 0, down[i].ds, o);
+      b.conv3x3(h, B2, HH(i), WW(i), 2, 0, down[i].ds, o);
       h = o;
     }
   }
@@ -1323,7 +1304,7 @@ int Engine::build_unet(UNetPlan& P, Arena& A, bool record) {
     if (up[i].has_us) {
       // Upsample2D (resnet.py:95-161): nearest x2 folded into the conv gather
       TView dst = Builder::slice(cats[(i + 1) * (lpb + 1)].buf, 0, cats[(i + 1) * (lpb + 1)].c1, esz);
-      b.conv3x3(last, B2, HH(lvl - 1), WW(lvl - 1), HH(lvl), WW(lvl), 1, 1, up[i].us, dst);
+      b.conv3x3(last, B2, HH(lvl), WW(lvl), 1, 1, up[i].us, dst);
     }
   }
   // ---- out ----
@@ -1332,7 +1313,7 @@ int Engine::build_unet(UNetPlan& P, Arena& A, bool record) {
     b.groupnorm(last, B2, HH(0) * WW(0), norm_out, G, ACT_SILU, t);
     TView o; o.p = P.eps; o.ld = cfg.unet_out_channels; o.C = cfg.unet_out_channels;
     GOpt go; go.out_f32 = true;
-    b.conv3x3(t, B2, HH(0), WW(0), HH(0), WW(0), 1, 0, conv_out, o, go);
+    b.conv3x3(t, B2, HH(0), WW(0), 1, 0, conv_out, o, go);
   }
   return 0;
 }
@@ -1873,7 +1854,7 @@ int Engine::build_vae(VaePlan& P, Arena& A, bool record) {
   }
   int C = vae_conv_in.N;
   TView h = b.alloc((int64_t)B * HW0, C);
-  b.conv3x3(z, B, H0, W0, H0, W0, 1, 0, vae_conv_in, h);
+  b.conv3x3(z, B, H0, W0, 1, 0, vae_conv_in, h);
   {
     TView o = b.alloc((int64_t)B * HW0, C);
     b.resblock(vae_mid1, h, B, H0, W0, 32, o);
@@ -1895,7 +1876,7 @@ int Engine::build_vae(VaePlan& P, Arena& A, bool record) {
     }
     if (vae_up[lvl].has_up) {
       TView o = b.alloc((int64_t)B * Hc * Wc * 4, C);
-      b.conv3x3(h, B, Hc * 2, Wc * 2, Hc, Wc, 1, 1, vae_up[lvl].up, o);
+      b.conv3x3(h, B, Hc, Wc, 1, 1, vae_up[lvl].up, o);
       h = o; Hc *= 2; Wc *= 2;
     }
   }
@@ -1904,7 +1885,7 @@ int Engine::build_vae(VaePlan& P, Arena& A, bool record) {
     b.groupnorm(h, B, Hc * Wc, vae_norm_out, 32, ACT_SILU, t);
     TView o; o.p = P.out; o.ld = cfg.vae_out_ch; o.C = cfg.vae_out_ch;
     GOpt go; go.out_f32 = true;
-    b.conv3x3(t, B, Hc, Wc, Hc, Wc, 1, 0, vae_conv_out, o, go);
+    b.conv3x3(t, B, Hc, Wc, 1, 0, vae_conv_out, o, go);
   }
   return 0;
 }
@@ -1951,7 +1932,7 @@ int Engine::build_vae_enc(VaePlan& P, Arena& A, bool record) {
   }
   int C = vae_enc_conv_in.N;
   TView h = b.alloc((int64_t)B * Hc * Wc, C);
-  b.conv3x3(x, B, Hc, Wc, Hc, Wc, 1, 0, vae_enc_conv_in, h);
+  b.conv3x3(x, B, Hc, Wc, 1, 0, vae_enc_conv_in, h);
   for (int lvl = 0; lvl < nl; ++lvl) {
     for (size_t k = 0; k < vae_down[lvl].res.size(); ++k) {
       const ResW& r = vae_down[lvl].res[k];
@@ -1962,7 +1943,7 @@ int Engine::build_vae_enc(VaePlan& P, Arena& A, bool record) {
     if (vae_down[lvl].has_down) {
       TView o = b.alloc((int64_t)B * (Hc / 2) * (Wc / 2), C);
       GOpt go; go.pad = 0;                                  // F.pad(x, (0,1,0,1)) + conv(k3, s2, p0), modules.py:87-91
-      b.conv3x3(h, B, Hc / 2, Wc / 2, Hc, Wc, 2, 0, vae_down[lvl].down, o, go);
+      b.conv3x3(h, B, Hc, Wc, 2, 0, vae_down[lvl].down, o, go);
       h = o; Hc /= 2; Wc /= 2;
     }
   }
@@ -1984,7 +1965,7 @@ int Engine::build_vae_enc(VaePlan& P, Arena& A, bool record) {
     float* mom = b.alloc_f32((size_t)B * HW0 * mc);
     TView o; o.p = mom; o.ld = mc; o.C = mc;
     GOpt go; go.out_f32 = true;
-    b.conv3x3(t, B, Hc, Wc, Hc, Wc, 1, 0, vae_enc_conv_out, o, go);
+    b.conv3x3(t, B, Hc, Wc, 1, 0, vae_enc_conv_out, o, go);
     const float* W = qc_w; const float* bb = qc_b; float* dst = (float*)P.out; const int co = 2 * cfg.vae_embed_dim;
     b.push([=](hipStream_t s) { return launch_pointwise_out_nchw(mom, mc, W, bb, dst, B, mc, co, HW0, s); });
   }
@@ -2031,18 +2012,14 @@ int Engine::build_voc(VaePlan& P, Arena& A, bool record, int frames) {
   P.out = A.alloc(P.out_bytes);
   const int d = dt;
 
-  // `rows` output rows per item gathered from x [B][Lin][Cin] through the taps of w, written to out [B][Lout][N]
-  auto gather1d = [&](const TView& x, int Lin, const WMat& w, int rows, const TView& out, int Lout) {
-    GemmParams p;
+  // the buffers of a problem.h geometry: x [B][Lin][Cin] through the taps of w into out [B][Lout][N]
+  auto bind = [](GemmParams& p, const TView& x, const WMat& w, const TView& out) {
     p.A = x.p; p.lda = x.ld; p.W = w.W; p.Kp = w.Kp; p.bias = w.b;
-    p.M = B * rows; p.N = w.N; p.K = w.K; p.Cin = w.Cin;
-    p.mode = GATHER_1D; p.rows_pb = rows; p.Lin = Lin; p.taps = w.taps; p.in_mul = 1;
-    p.Lout = Lout; p.out = out.p; p.ldo = out.ld;
-    return p;
+    p.out = out.p; p.ldo = out.ld;
   };
   auto conv1d = [&](const TView& x, int L, const WMat& w, int dil, const TView& out, const GOpt& o, bool i16 = false) {
-    GemmParams p = gather1d(x, L, w, L, out, L);
-    p.tap_step = dil; p.in_off = -dil * (w.taps - 1) / 2;
+    GemmParams p = conv1d_problem(B, w.Cin, L, w.N, w.taps, dil);
+    bind(p, x, w, out);
     b.apply(p, o);
     if (i16) { p.epi = EPI_I16; p.out_scale = 32768.0f; }
     b.gemm(p);
@@ -2064,15 +2041,9 @@ int Engine::build_voc(VaePlan& P, Arena& A, bool record, int frames) {
     const int Lo = (L - 1) * u - 2 * pd + k;
     TView y = b.alloc((int64_t)B * Lo, ct.cout);
     for (int r = 0; r < u; ++r) {
-      // outputs t = u*q + r - pd; input index q - tap
-      const int qmin = (pd > r) ? (pd - r + u - 1) / u : 0;
-      const int qmax = (Lo - 1 + pd - r) / u;
-      const int Q = qmax - qmin + 1;
-      if (Q <= 0) continue;
-      const WMat& w = ct.phase[r];
-      GemmParams p = gather1d(h, L, w, Q, y, Lo);
-      p.tap_step = -1; p.in_off = qmin;
-      p.out_mul = u; p.out_off = u * qmin + r - pd;
+      GemmParams p;
+      if (!convt_phase_problem(B, ct.cin, L, ct.cout, k, u, pd, r, p)) continue;   // (taps per phase as reg_convt1d packed them)
+      bind(p, h, ct.phase[r], y);
       b.gemm(p);
     }
     L = Lo; C = ct.cout;

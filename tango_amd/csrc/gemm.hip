@@ -294,7 +294,7 @@ static int launch_cfg(const GemmParams& p, hipStream_t s) {
 // launch when K is short enough that a workgroup's serial k-loop stays a few microseconds.
 static bool small_tile_linear(const GemmParams& p, int esz) {
   if (tuning().no_small_tile || p.mode != GATHER_1D || p.epi != EPI_NONE || p.batch != 1 || p.splitk > 1 || p.bias_rows) return false;
-  if (!(p.taps == 1 && p.rows_pb == p.M && p.in_mul == 1 && p.in_off == 0 && p.out_mul == 1 && p.out_off == 0 && p.Lin >= p.M)) return false;
+  if (!gemm_is_plain_linear(p)) return false;
   if (p.N % 64 != 0 || (p.Cin * esz) % 128 != 0 || p.K > 1280) return false;
   const int bn = (p.N % 160 == 0) ? 160 : 128;
   const long big = (long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn);
@@ -324,9 +324,7 @@ static int launch_tile(const GemmParams& p, hipStream_t s) {
 template <typename T, int BKB>
 static int launch_mode(const GemmParams& p, hipStream_t s) {
   if (p.mode == GATHER_2D) return launch_tile<T, BKB, MODE_CONV2D>(p, s);
-  const bool linear = p.taps == 1 && p.rows_pb == p.M && p.in_mul == 1 && p.in_off == 0 && p.out_mul == 1 && p.out_off == 0 &&
-                      p.Lin >= p.M;
-  if (linear) return launch_tile<T, BKB, MODE_LINEAR>(p, s);
+  if (gemm_is_plain_linear(p)) return launch_tile<T, BKB, MODE_LINEAR>(p, s);
   return launch_tile<T, BKB, MODE_CONV1D>(p, s);
 }
 
@@ -357,8 +355,7 @@ int gemm_init() {
 int gemm_pick_splitk(int dtype, const GemmParams& p) {
   if (p.batch != 1 || p.epi != EPI_NONE || p.bias_rows || p.out_scale != 1.f || (p.N & 3) || (p.ldo & 3) || (p.R && (p.ldr & 3)))
     return 1;
-  if (p.mode == GATHER_1D && !(p.taps == 1 && p.rows_pb == p.M && p.in_mul == 1 && p.in_off == 0 && p.out_mul == 1 && p.out_off == 0))
-    return 1;
+  if (p.mode == GATHER_1D && !gemm_is_plain_linear(p)) return 1;   // (this site used to omit Lin >= M: no constructor of problem.h builds such a problem)
   if (gemm_duo_ok(dtype, p) || linear_stream_ok(dtype, p)) return 1;
   if (small_tile_linear(p, dtype == DT_F32 ? 4 : 2)) return 1;      // one launch of 64 x 64 tiles instead (launch_tile)
   if (p.N <= 32 && conv_halo_ok(dtype, p)) return 1;                // narrow-output convs (conv_out) on the halo kernel's 256 x 32 tile from 256 tiles on (round 6)
@@ -410,6 +407,72 @@ bool gemm_rowvec_ok(int dtype, const GemmParams& p) {
   if ((uintptr_t)p.rowvec & 15) return false;
   const int r = gemm_route(dtype, p);
   return r == ROUTE_WIDE || r == ROUTE_DUO;
+}
+
+// ---- the planner (common.h) ----
+// what a buffer the caller allocates after planning looks like to the *_ok() predicates: non-null and aligned, never dereferenced
+static void* const kPlanDummy = (void*)(uintptr_t)0x10000;
+
+GemmPlan plan_gemm(int dtype, const GemmParams& p) {
+  GemmPlan pl;
+  pl.g = p;
+  pl.splitk = gemm_pick_splitk(dtype, p);
+  GemmParams q = p;
+  if (pl.splitk > 1) { q.splitk = pl.splitk; q.ws = (float*)kPlanDummy; }
+  pl.route = gemm_route(dtype, q);
+  pl.pers = pl.route == ROUTE_WIDE && gemm_wide_persistent(dtype, q);
+  return pl;
+}
+
+GemmPlan plan_linear(int dtype, const GemmParams& p, const LnFold* ln) {
+  if (!ln) return plan_gemm(dtype, p);
+  if (ln->Wln) {
+    GemmParams q = p;
+    q.W = ln->Wln; q.bias = ln->bln; q.ln_fold = 1; q.ln_eps = ln->eps; q.wsum = ln->wsum;
+    // (a folded LayerNorm is never split along K: the split-K policy does not ask the 256 x 320 GEMM, so with the big tiles forced
+    //  onto a small problem it would split what only the unsplit kernel can fold)
+    if (gemm_ln_fold_ok(dtype, q) && gemm_pick_splitk(dtype, q) <= 1) {
+      GemmPlan pl = plan_gemm(dtype, q);
+      pl.form = LIN_LN_FOLD;
+      return pl;
+    }
+    // GEGLU projections the in-loop-statistics kernels do not take (levels 1-2): row statistics in a read-only pass, then the
+    // folded weights on the 256 x 320 GEMM -- LayerNorm(x) is never written (round 4)
+    if (p.epi == EPI_GEGLU && !p.R && !tuning().no_ln_xstats) {
+      q.row_stats = (const float*)kPlanDummy;
+      if (gemm_wide_ok(dtype, q) && gemm_route(dtype, q) == ROUTE_WIDE && gemm_pick_splitk(dtype, q) <= 1) {
+        GemmPlan pl = plan_gemm(dtype, q);
+        pl.form = LIN_LN_XSTATS;
+        pl.g.row_stats = nullptr;
+        return pl;
+      }
+    }
+  }
+  // materialise LayerNorm(x) as dense rows, then the plain problem under the ordinary split-K policy
+  GemmParams m = p;
+  m.A = kPlanDummy; m.lda = p.K;
+  GemmPlan pl = plan_gemm(dtype, m);
+  pl.form = LIN_LN_MATERIAL;
+  pl.g.A = nullptr;
+  return pl;
+}
+
+GemmPlan plan_conv3x3(int dtype, const GemmParams& p, bool allow_phase) {
+  GemmPlan pl = plan_gemm(dtype, p);
+  pl.phase = allow_phase && p.mode == GATHER_2D && p.ups == 1 && p.stride == 1 && pl.splitk <= 1 && pl.route == ROUTE_CONV_WIDE &&
+             conv_ups_phase_ok(dtype, p);
+  return pl;
+}
+
+std::string plan_name(const GemmPlan& pl) {
+  static const char* const names[] = {"none", "wide", "stream", "conv_wide", "conv_halo", "dma", "tile", "duo"};   // enum GemmRoute
+  std::string s = pl.form == LIN_LN_MATERIAL ? "layernorm+" : "";
+  s += names[pl.route];
+  if (pl.form == LIN_LN_XSTATS) s += "+xstats";
+  if (pl.pers) s += "+pers";
+  if (pl.splitk > 1) s += "+splitk";
+  if (pl.phase) s += "+phase";
+  return s;
 }
 
 int launch_gemm(int dtype, const GemmParams& p, hipStream_t s) {

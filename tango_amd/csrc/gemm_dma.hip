@@ -242,8 +242,7 @@ bool gemm_dma_ok(int dtype, const GemmParams& p) {
 template <typename T>
 static int launch_dma(const GemmParams& p, hipStream_t s) {
   if (!g_zero_page) TANGO_FAIL("gemm: gemm_init() was not called (zero page for the LDS-DMA gather)");
-  const bool linear = p.mode == GATHER_1D && p.taps == 1 && p.rows_pb == p.M && p.in_mul == 1 && p.in_off == 0 &&
-                      p.out_mul == 1 && p.out_off == 0 && p.Lin >= p.M;
+  const bool linear = gemm_is_plain_linear(p);
   const bool bn128 = (p.epi == EPI_GEGLU || p.N % 160 != 0);
   if (p.mode == GATHER_2D) return bn128 ? launch_dma_cfg<T, 128, MODE_CONV2D>(p, s) : launch_dma_cfg<T, 160, MODE_CONV2D>(p, s);
   if (linear) return bn128 ? launch_dma_cfg<T, 128, MODE_LINEAR>(p, s) : launch_dma_cfg<T, 160, MODE_LINEAR>(p, s);

@@ -191,9 +191,7 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(const GemmParams p, co
 // TANGO_DUO_MAXK >= 0 replaces the rule by "K <= that, >= TANGO_DUO_MIN_TILES tiles" (A/B runs, tests).
 bool gemm_duo_ok(int dtype, const GemmParams& p) {
   if (tuning().duo_maxk == 0 || dtype == DT_F32) return false;
-  const bool linear = p.mode == GATHER_1D && p.taps == 1 && p.rows_pb == p.M && p.in_mul == 1 && p.in_off == 0 && p.out_mul == 1 &&
-                      p.out_off == 0 && p.Lin >= p.M;
-  if (!linear || p.batch != 1 || p.a_act != ACT_NONE || p.bias_rows) return false;
+  if (!gemm_is_plain_linear(p) || p.batch != 1 || p.a_act != ACT_NONE || p.bias_rows) return false;
   if (p.splitk > 1 || p.out_f32 || p.e_act != ACT_NONE || p.row_stats) return false;
   if (p.ln_fold && (!p.wsum || ((uintptr_t)p.wsum & 15) || p.alpha != 1.f)) return false;
   if (p.epi != EPI_NONE && p.epi != EPI_GEGLU && p.epi != EPI_VT) return false;

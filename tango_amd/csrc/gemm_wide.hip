@@ -619,9 +619,16 @@ static int wide_pers_grid(long ntiles) {
   }
   return ntiles < cus ? (int)ntiles : cus;
 }
-// workgroups of the persistent form on this device (= its CU count; 256 when no device is visible): the route query of ops_abi.hip
-// labels "+pers" with the same number the launcher uses
-int gemm_wide_pers_cus() { return wide_pers_grid(1L << 30); }
+// The persistent form takes a problem of the 256 x 320 GEMM when it has at least `wide_pers` tiles per CU-workgroup to walk
+// (TANGO_WIDE_PERS; 0 = never; the workgroup count is the device's CU count, 256 when no device is visible) and its epilogue has a
+// persistent instantiation (launch_wide_pers_t: all but GEGLU with a residual or in-loop LayerNorm statistics).  One predicate for
+// launch_gemm_wide() and the planner's "+pers".  (TANGO_WIDE_PIPE's main loop, when switched on, is asked first.)
+bool gemm_wide_persistent(int dtype, const GemmParams& p) {
+  const int pers = tuning().wide_pers;
+  if (pers <= 0 || p.splitk > 1 || dtype == DT_F32) return false;
+  if (p.epi == EPI_GEGLU && !p.row_stats && (p.R || p.ln_fold)) return false;
+  return (long)(p.M / 256) * (p.N / 320) >= (long)pers * wide_pers_grid(1L << 30);
+}
 
 template <typename T, bool GEGLU, bool RES, bool LN, bool VT, bool XS>
 static int launch_wide_pers_cfg(const GemmParams& p, hipStream_t s) {
@@ -634,17 +641,12 @@ static int launch_wide_pers_cfg(const GemmParams& p, hipStream_t s) {
   return 0;
 }
 
-// the persistent form takes a problem when it has at least `wide_pers` tiles per CU-workgroup to walk (TANGO_WIDE_PERS; 0 = never)
+// the epilogue kinds of the persistent form (gemm_wide_persistent() has said yes)
 template <typename T>
-static int launch_wide_pers_t(const GemmParams& p, hipStream_t s, bool& taken) {
-  taken = true;
+static int launch_wide_pers_t(const GemmParams& p, hipStream_t s) {
   if (p.row_stats) return launch_wide_pers_cfg<T, true, false, true, false, true>(p, s);
   if (p.epi == EPI_VT) return p.ln_fold ? launch_wide_pers_cfg<T, false, false, true, true, false>(p, s) : launch_wide_pers_cfg<T, false, false, false, true, false>(p, s);
-  if (p.epi == EPI_GEGLU) {
-    if (!p.R && !p.ln_fold) return launch_wide_pers_cfg<T, true, false, false, false, false>(p, s);
-    taken = false;
-    return 0;
-  }
+  if (p.epi == EPI_GEGLU) return launch_wide_pers_cfg<T, true, false, false, false, false>(p, s);
   if (p.ln_fold) return p.R ? launch_wide_pers_cfg<T, false, true, true, false, false>(p, s) : launch_wide_pers_cfg<T, false, false, true, false, false>(p, s);
   return p.R ? launch_wide_pers_cfg<T, false, true, false, false, false>(p, s) : launch_wide_pers_cfg<T, false, false, false, false, false>(p, s);
 }
@@ -653,9 +655,7 @@ static int launch_wide_pers_t(const GemmParams& p, hipStream_t s, bool& taken) {
 // tiles to fill the chip
 bool gemm_wide_ok(int dtype, const GemmParams& p) {
   if (tuning().no_wide_gemm || dtype == DT_F32) return false;
-  const bool linear = p.mode == GATHER_1D && p.taps == 1 && p.rows_pb == p.M && p.in_mul == 1 && p.in_off == 0 && p.out_mul == 1 &&
-                      p.out_off == 0 && p.Lin >= p.M;
-  if (!linear || p.batch != 1 || p.a_act != ACT_NONE || p.bias_rows) return false;
+  if (!gemm_is_plain_linear(p) || p.batch != 1 || p.a_act != ACT_NONE || p.bias_rows) return false;
   // (split-K on this tile was measured in round 2 -- no gain over the 4-wave tiles' split-K at M = 4096 -- and is not compiled)
   if (p.splitk > 1 || p.out_f32) return false;
   if (p.ln_fold && (!p.wsum || ((uintptr_t)p.wsum & 15) || p.alpha != 1.f)) return false;
@@ -774,14 +774,7 @@ int launch_gemm_wide(int dtype, const GemmParams& p, hipStream_t s) {
     else if (dtype == DT_BF16) rc = launch_wide_pipe_t<bf16>(p, s, taken);
     if (taken) return rc;
   }
-  const int pers = tuning().wide_pers;
-  if (pers > 0 && p.splitk <= 1 && (long)(p.M / 256) * (p.N / 320) >= (long)pers * wide_pers_grid(1L << 30)) {
-    bool taken = false;
-    int rc = 0;
-    if (dtype == DT_F16) rc = launch_wide_pers_t<f16>(p, s, taken);
-    else if (dtype == DT_BF16) rc = launch_wide_pers_t<bf16>(p, s, taken);
-    if (taken) return rc;
-  }
+  if (gemm_wide_persistent(dtype, p)) return dtype == DT_F16 ? launch_wide_pers_t<f16>(p, s) : launch_wide_pers_t<bf16>(p, s);
   switch (dtype) {
     case DT_F16: return launch_wide_t<f16>(p, s);
     case DT_BF16: return launch_wide_t<bf16>(p, s);

@@ -405,8 +405,7 @@ bool linear_stream_ok(int dtype, const GemmParams& p) {
   if (p.row_stats) return false;
   const int esz = dtype == DT_F32 ? 4 : 2;
   const int rowb = p.K * esz;
-  if (p.mode != GATHER_1D || p.taps != 1 || p.rows_pb != p.M || p.in_mul != 1 || p.in_off != 0 || p.out_mul != 1 || p.out_off != 0)
-    return false;
+  if (!gemm_is_plain_linear(p)) return false;
   if (p.batch != 1 || p.bias2 || p.bias_rows || p.out_f32 || p.a_act != ACT_NONE || p.e_act != ACT_NONE || p.alpha != 1.f ||
       p.out_scale != 1.f)
     return false;

@@ -67,65 +67,29 @@ static int transpose_v(int dt, const void* v, void* vt, int B, int S, int C, int
 
 using namespace tango;
 
-// test wrappers honour the same split-K policy as the engine plans
+// test wrappers apply the split-K policy exactly as the engine plans do (gemm_apply_splitk), with the workspace from `sc`
 static int run_gemm(int dt, GemmParams& p, Scratch& sc, hipStream_t s) {
   TANGO_TRY(gemm_init());
-  const int sk = gemm_pick_splitk(dt, p);
-  if (sk > 1) {
-    p.splitk = sk;
-    p.ws = (float*)sc.get((size_t)sk * p.M * p.N * 4);
-    if (!p.ws) TANGO_FAIL("run_gemm: alloc");
-  }
+  gemm_apply_splitk(dt, p, [&](size_t floats) { return (float*)sc.get(floats * 4); });
+  if (p.splitk > 1 && !p.ws) TANGO_FAIL("run_gemm: alloc");
   return launch_gemm(dt, p, s);
 }
 
-// ---- the GemmParams of the op wrappers without their pointers.  The wrappers AND the host-only route queries (tango_debug_*_route)
-// build their problems here, so a query answers for exactly the problem the wrapper launches ----
-static int conv_out_dim(int n, int stride, int pad) { return (n + pad + 1 - 3) / stride + 1; }   // pad 1: symmetric; pad 0: zero row / column at the far edge only
-
-// 3x3 gather conv on NHWC (Cin * esz a multiple of 64 bytes); H, W are the SOURCE dims
-static GemmParams conv2d_problem(int B, int Cin, int H, int W, int Cout, int stride, int upsample, int pad) {
-  const int Hc = H << upsample, Wc = W << upsample;
-  const int Ho = conv_out_dim(Hc, stride, pad), Wo = conv_out_dim(Wc, stride, pad);
-  GemmParams p;
-  p.N = Cout; p.ldo = Cout;
-  p.lda = Cin; p.Kp = 9 * (int64_t)Cin; p.M = B * Ho * Wo; p.K = 9 * Cin; p.Cin = Cin;
-  p.mode = GATHER_2D; p.H = Ho; p.Wd = Wo; p.Hin = H; p.Win = W; p.stride = stride; p.ups = upsample; p.pad = pad;
-  return p;
-}
-// the same conv for tiny Cin: im2col rows [B*H*W][Kp] and a plain GEMM (stride 1, pad 1 only)
-static GemmParams conv2d_im2col_problem(int B, int Cin, int H, int W, int Cout) {
-  const int64_t Kp = ((9 * Cin + 31) / 32) * 32;
-  GemmParams p;
-  p.N = Cout; p.ldo = Cout;
-  p.lda = Kp; p.Kp = Kp; p.M = B * H * W; p.K = (int)Kp; p.Cin = (int)Kp;
-  p.mode = GATHER_1D; p.rows_pb = p.M; p.Lin = p.M; p.Lout = p.M;
-  return p;
-}
-// conv1d taps / transposed-conv1d phase taps on channels-last [B][Lin][Cin]: row q of a batch item reads q + in_off + tap * tap_step
-// and writes row q * out_mul + out_off of [B][Lout][Cout]
-static GemmParams gather1d_problem(int B, int Cin, int Lin, int Cout, int taps, int tap_step, int in_off, int rows_pb, int Lout, int out_mul,
-                                   int out_off) {
-  GemmParams p;
-  p.lda = Cin; p.Kp = (int64_t)taps * Cin; p.M = B * rows_pb; p.N = Cout; p.K = taps * Cin; p.Cin = Cin;
-  p.mode = GATHER_1D; p.rows_pb = rows_pb; p.Lin = Lin; p.taps = taps; p.tap_step = tap_step; p.in_off = in_off;
-  p.Lout = Lout; p.out_mul = out_mul; p.out_off = out_off; p.ldo = Cout;
-  return p;
-}
-static GemmParams conv1d_problem(int B, int Cin, int L, int Cout, int k, int dilation) {
-  return gather1d_problem(B, Cin, L, Cout, k, dilation, -dilation * (k - 1) / 2, L, L, 1, 0);
-}
-// phase r of ConvTranspose1d(k, stride u, padding pd): outputs t = u * q + r - pd read inputs q - tap; false: the phase has no taps or no rows
-static bool convt_phase_problem(int B, int Cin, int L, int Cout, int k, int u, int pd, int r, GemmParams& p) {
-  const int Lo = (L - 1) * u - 2 * pd + k;
-  const int T = (k - r + u - 1) / u;
-  if (T <= 0) return false;
-  const int qmin = (pd > r) ? (pd - r + u - 1) / u : 0;
-  const int qmax = (Lo - 1 + pd - r) / u;
-  const int Q = qmax - qmin + 1;
-  if (Q <= 0) return false;
-  p = gather1d_problem(B, Cin, L, Cout, T, -1, qmin, Q, Lo, u, u * qmin + r - pd);
-  return true;
+// mean time of `reps` back-to-back repeats of an op's launches (HIP events on `s`), for same-process A/Bs
+template <typename Once> static int time_reps(Once&& once, int reps, float* ms_out, hipStream_t s) {
+  hipEvent_t e0, e1;
+  TANGO_HIP(hipEventCreate(&e0));
+  TANGO_HIP(hipEventCreate(&e1));
+  TANGO_HIP(hipEventRecord(e0, s));
+  for (int i = 0; i < reps; ++i) TANGO_TRY(once());
+  TANGO_HIP(hipEventRecord(e1, s));
+  TANGO_HIP(hipEventSynchronize(e1));
+  float ms = 0.f;
+  TANGO_HIP(hipEventElapsedTime(&ms, e0, e1));
+  *ms_out = ms / (float)reps;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return 0;
 }
 
 // phases: -1 = as the engine decides (phase form where conv_ups_phase_ok), 0 = nine-tap form, 1 = phase form or an error
@@ -171,8 +135,7 @@ static int op_conv2d_impl(int dt, const float* x, const float* w, const float* b
   if (rt) { p.R = rt; p.ldr = Cout; }
   if (bias2) { p.bias2 = bias2; p.bias2_stride = Cout; }
   if (!im2col) {
-    const bool ph_ok = upsample == 1 && stride == 1 && phases != 0 && gemm_pick_splitk(dt, p) <= 1 &&
-                       gemm_route(dt, p) == ROUTE_CONV_WIDE && conv_ups_phase_ok(dt, p);
+    const bool ph_ok = plan_conv3x3(dt, p, phases != 0).phase;
     if (phases == 1 && !ph_ok) TANGO_FAIL("op_conv2d_ups: the phase form does not take this problem");
     if (ph_ok) {
       void* wph = sc.get((size_t)16 * Cout * Cin * esz);
@@ -187,25 +150,62 @@ static int op_conv2d_impl(int dt, const float* x, const float* w, const float* b
   return 0;
 }
 
-// ---- host-only route queries: never-dereferenced aligned pointers, the wrappers' split-K policy (run_gemm), then the dispatcher's pick ----
-static void* const kRouteDummy = (void*)(uintptr_t)0x10000;
-static const char* route_answer(int dt, GemmParams p, int* splitk_out, const char* suffix = "") {
-  static thread_local std::string out;
-  const int sk = gemm_pick_splitk(dt, p);
-  if (sk > 1) { p.splitk = sk; p.ws = (float*)kRouteDummy; }
-  if (splitk_out) *splitk_out = sk;
-  switch (gemm_route(dt, p)) {
-    case ROUTE_WIDE: out = "wide"; break;
-    case ROUTE_DUO: out = "duo"; break;
-    case ROUTE_STREAM: out = "stream"; break;
-    case ROUTE_CONV_WIDE: out = "conv_wide"; break;
-    case ROUTE_CONV_HALO: out = "conv_halo"; break;
-    case ROUTE_DMA: out = "dma"; break;
-    case ROUTE_TILE: out = "tile"; break;
-    default: out = "none"; break;
+// [LayerNorm when gamma](x) @ W^T (+bias, activations, GEGLU, +residual) in the form the engine's planner picks (plan_linear): LayerNorm folded
+// in the kernel, statistics pass + XS GEMM, or layernorm + plain GEMM under the ordinary split-K policy
+static int op_linear_impl(int dt, const float* x, const float* w, const float* bias, const float* gamma, const float* beta, const float* residual,
+                          float* out, int M, int N, int K, int a_act, int e_act, int geglu, float eps, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype_size(dt);
+  Scratch sc;
+  const int No = geglu ? N / 2 : N;
+  void* xt = sc.get((size_t)M * K * esz);
+  void* wt = sc.get((size_t)N * K * esz);
+  void* ot = sc.get((size_t)M * No * esz);
+  void* rt = residual ? sc.get((size_t)M * No * esz) : nullptr;
+  float* bt = bias ? (float*)sc.get((size_t)N * 4) : nullptr;
+  if (!xt || !wt || !ot || (residual && !rt) || (bias && !bt)) TANGO_FAIL("op_linear: alloc");
+  TANGO_TRY(launch_cast_rows(dt, x, xt, K, M, K, s));
+  TANGO_TRY(launch_pack(dt, w, wt, N, 1, K, K, 0, 1, K, geglu ? -1 : 0, s));
+  if (residual) TANGO_TRY(launch_cast_rows(dt, residual, rt, No, M, No, s));
+  if (bias) {
+    if (geglu) TANGO_TRY(launch_permute_geglu_bias(bias, bt, N, s));
+    else TANGO_HIP(hipMemcpyAsync(bt, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
   }
-  if (sk > 1) out += "+splitk";
-  out += suffix;
+  GemmParams p = dense_gemm(xt, K, wt, K, M, N, K);
+  p.bias = bt; p.out = ot; p.ldo = No; p.R = rt; p.ldr = No; p.a_act = a_act; p.e_act = e_act; p.epi = geglu ? EPI_GEGLU : EPI_NONE;
+  LnFold f;
+  if (gamma) {
+    void* wl = sc.get((size_t)N * K * esz);
+    float* bl = (float*)sc.get((size_t)N * 4);
+    float* ws = (float*)sc.get((size_t)N * 4);
+    if (!wl || !bl || !ws) TANGO_FAIL("op_linear_ln: alloc");
+    TANGO_TRY(launch_fold_ln(dt, wt, K, gamma, beta, bt, wl, bl, ws, N, K, s));
+    f = LnFold{wl, bl, ws, eps};
+  }
+  GemmPlan pl = plan_linear(dt, p, gamma ? &f : nullptr);
+  if (pl.form == LIN_LN_XSTATS) {
+    float* st = (float*)sc.get((size_t)M * 2 * 4);
+    if (!st) TANGO_FAIL("op_linear_ln: alloc");
+    TANGO_TRY(launch_ln_stats(dt, xt, K, st, M, K, eps, s));
+    pl.g.row_stats = st;
+  } else if (pl.form == LIN_LN_MATERIAL) {
+    void* nt = sc.get((size_t)M * K * esz);
+    if (!nt) TANGO_FAIL("op_linear_ln: alloc");
+    TANGO_TRY(launch_layernorm(dt, xt, K, nt, K, gamma, beta, M, K, eps, s));
+    pl.g.A = nt; pl.g.lda = K;
+  }
+  TANGO_TRY(run_gemm(dt, pl.g, sc, s));
+  TANGO_TRY(to_f32(dt, ot, No, out, M, No, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// ---- host-only route queries: the wrappers' problems with never-dereferenced aligned pointers, planned as the wrappers plan them ----
+static void* const kRouteDummy = (void*)(uintptr_t)0x10000;
+static const char* route_answer(const GemmPlan& pl, int* splitk_out = nullptr) {
+  static thread_local std::string out;
+  if (splitk_out) *splitk_out = pl.splitk;
+  out = plan_name(pl);
   return out.c_str();
 }
 
@@ -230,121 +230,25 @@ int tango_op_pack_ups_phase(int dt, const float* w, void* out, int Cout, int Cin
 
 int tango_op_linear(int dt, const float* x, const float* w, const float* bias, const float* residual, float* out, int M, int N,
                     int K, int a_act, int e_act, int geglu, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const size_t esz = dtype_size(dt);
-  Scratch sc;
-  const int No = geglu ? N / 2 : N;
-  void* xt = sc.get((size_t)M * K * esz);
-  void* wt = sc.get((size_t)N * K * esz);
-  void* ot = sc.get((size_t)M * No * esz);
-  void* rt = residual ? sc.get((size_t)M * No * esz) : nullptr;
-  float* bt = bias ? (float*)sc.get((size_t)N * 4) : nullptr;
-  if (!xt || !wt || !ot) TANGO_FAIL("op_linear: alloc");
-  TANGO_TRY(launch_cast_rows(dt, x, xt, K, M, K, s));
-  TANGO_TRY(launch_pack(dt, w, wt, N, 1, K, K, 0, 1, K, geglu ? -1 : 0, s));
-  if (residual) TANGO_TRY(launch_cast_rows(dt, residual, rt, No, M, No, s));
-  if (bias) {
-    if (geglu) TANGO_TRY(launch_permute_geglu_bias(bias, bt, N, s));
-    else TANGO_HIP(hipMemcpyAsync(bt, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
-  }
-  GemmParams p;
-  p.A = xt; p.lda = K; p.W = wt; p.Kp = K; p.bias = bt; p.M = M; p.N = N; p.K = K; p.Cin = K;
-  p.mode = GATHER_1D; p.rows_pb = M; p.Lin = M; p.Lout = M;
-  p.out = ot; p.ldo = No; p.R = rt; p.ldr = No; p.a_act = a_act; p.e_act = e_act; p.epi = geglu ? EPI_GEGLU : EPI_NONE;
-  TANGO_TRY(run_gemm(dt, p, sc, s));
-  TANGO_TRY(to_f32(dt, ot, No, out, M, No, s));
-  TANGO_HIP(hipStreamSynchronize(s));
-  return 0;
+  return op_linear_impl(dt, x, w, bias, nullptr, nullptr, residual, out, M, N, K, a_act, e_act, geglu, 0.f, stream);
 }
 
 int tango_op_linear_ln(int dt, const float* x, const float* w, const float* bias, const float* gamma, const float* beta,
                        const float* residual, float* out, int M, int N, int K, int geglu, float eps, void* stream) {
-  // LayerNorm(x) @ W^T (+bias, GEGLU, +residual): streaming kernel with folded LN when eligible, else LN + GEMM
-  hipStream_t s = (hipStream_t)stream;
-  const size_t esz = dtype_size(dt);
-  Scratch sc;
-  const int No = geglu ? N / 2 : N;
-  void* xt = sc.get((size_t)M * K * esz);
-  void* wt = sc.get((size_t)N * K * esz);
-  void* wl = sc.get((size_t)N * K * esz);
-  void* ot = sc.get((size_t)M * No * esz);
-  void* rt = residual ? sc.get((size_t)M * No * esz) : nullptr;
-  float* bt = (float*)sc.get((size_t)N * 4);
-  float* bl = (float*)sc.get((size_t)N * 4);
-  float* ws = (float*)sc.get((size_t)N * 4);
-  if (!xt || !wt || !wl || !ot || !bt || !bl || !ws) TANGO_FAIL("op_linear_ln: alloc");
-  TANGO_TRY(launch_cast_rows(dt, x, xt, K, M, K, s));
-  TANGO_TRY(launch_pack(dt, w, wt, N, 1, K, K, 0, 1, K, geglu ? -1 : 0, s));
-  if (residual) TANGO_TRY(launch_cast_rows(dt, residual, rt, No, M, No, s));
-  if (bias) {
-    if (geglu) TANGO_TRY(launch_permute_geglu_bias(bias, bt, N, s));
-    else TANGO_HIP(hipMemcpyAsync(bt, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
-  }
-  TANGO_TRY(launch_fold_ln(dt, wt, K, gamma, beta, bias ? bt : nullptr, wl, bl, ws, N, K, s));
-  GemmParams p;
-  p.A = xt; p.lda = K; p.W = wl; p.Kp = K; p.bias = bl; p.M = M; p.N = N; p.K = K; p.Cin = K;
-  p.mode = GATHER_1D; p.rows_pb = M; p.Lin = M; p.Lout = M;
-  p.out = ot; p.ldo = No; p.R = rt; p.ldr = No; p.epi = geglu ? EPI_GEGLU : EPI_NONE;
-  p.ln_fold = 1; p.ln_eps = eps; p.wsum = ws;
-  TANGO_TRY(gemm_init());
-  GemmParams px = p;
-  px.row_stats = (float*)sc.get((size_t)M * 2 * 4);
-  // (as Builder::linear: a folded LayerNorm is never split along K)
-  if (gemm_ln_fold_ok(dt, p) && gemm_pick_splitk(dt, p) <= 1) {
-    TANGO_TRY(launch_gemm(dt, p, s));
-  } else if (geglu && !residual && px.row_stats && !tuning().no_ln_xstats && gemm_wide_ok(dt, px) && gemm_route(dt, px) == ROUTE_WIDE &&
-             gemm_pick_splitk(dt, px) <= 1) {
-    // the engine's route for the GEGLU projections of levels 1-2: read-only statistics pass + folded weights (gemm_wide.hip XS)
-    TANGO_TRY(launch_ln_stats(dt, xt, K, (float*)px.row_stats, M, K, eps, s));
-    TANGO_TRY(launch_gemm(dt, px, s));
-  } else {
-    void* nt = sc.get((size_t)M * K * esz);
-    if (!nt) TANGO_FAIL("op_linear_ln: alloc");
-    TANGO_TRY(launch_layernorm(dt, xt, K, nt, K, gamma, beta, M, K, eps, s));
-    p.A = nt; p.W = wt; p.bias = bias ? bt : nullptr; p.ln_fold = 0; p.wsum = nullptr;
-    TANGO_TRY(launch_gemm(dt, p, s));
-  }
-  TANGO_TRY(to_f32(dt, ot, No, out, M, No, s));
-  TANGO_HIP(hipStreamSynchronize(s));
-  return 0;
+  return op_linear_impl(dt, x, w, bias, gamma, beta, residual, out, M, N, K, ACT_NONE, ACT_NONE, geglu, eps, stream);
 }
 
 const char* tango_debug_linear_route(int dt, int M, int N, int K, int geglu, int ln_fold, int residual, int vt) {
-  static thread_local std::string out;
-  void* const dummy = (void*)(uintptr_t)0x10000;           // aligned, never dereferenced: the *_ok() predicates only look at alignment
-  GemmParams p;
-  p.A = dummy; p.lda = K; p.W = dummy; p.Kp = K; p.bias = (const float*)dummy; p.M = M; p.N = N; p.K = K; p.Cin = K;
-  p.mode = GATHER_1D; p.rows_pb = M; p.Lin = M; p.Lout = M;
+  // aligned, never dereferenced: the *_ok() predicates only look at alignment
+  GemmParams p = dense_gemm(kRouteDummy, K, kRouteDummy, K, M, N, K);
+  p.bias = (const float*)kRouteDummy;
   const int No = geglu ? N / 2 : N;
-  p.out = dummy; p.ldo = vt ? 2 * (N / 3) : No;
-  if (residual) { p.R = dummy; p.ldr = No; }
+  p.out = kRouteDummy; p.ldo = vt ? 2 * (N / 3) : No;
+  if (residual) { p.R = kRouteDummy; p.ldr = No; }
   p.epi = geglu ? EPI_GEGLU : (vt ? EPI_VT : EPI_NONE);
-  if (vt) { p.vt = dummy; p.vt_n0 = 2 * (N / 3); p.vt_S = 256; p.vt_ld = 256; }
-  auto name = [&](const GemmParams& g) -> std::string {
-    if (gemm_pick_splitk(dt, g) > 1) return "tile+splitk";
-    switch (gemm_route(dt, g)) {
-      case ROUTE_WIDE: {
-        const long tiles = (long)(g.M / 256) * (g.N / 320);
-        if (g.row_stats) return tuning().wide_pers > 0 && tiles >= (long)gemm_wide_pers_cus() * tuning().wide_pers ? "wide+xstats+pers" : "wide+xstats";
-        const bool pers_ok = !(g.epi == EPI_GEGLU && (g.R || g.ln_fold));
-        return tuning().wide_pers > 0 && pers_ok && tiles >= (long)gemm_wide_pers_cus() * tuning().wide_pers ? "wide+pers" : "wide";
-      }
-      case ROUTE_DUO: return "duo";
-      case ROUTE_STREAM: return "stream";
-      case ROUTE_DMA: return "dma";
-      case ROUTE_TILE: return "tile";
-      default: return "none";
-    }
-  };
-  if (!ln_fold) { out = name(p); return out.c_str(); }
-  GemmParams q = p;
-  q.ln_fold = 1; q.wsum = (const float*)dummy;
-  if (gemm_ln_fold_ok(dt, q) && gemm_pick_splitk(dt, q) <= 1) { out = name(q); return out.c_str(); }
-  GemmParams q2 = q;
-  q2.row_stats = (const float*)dummy;
-  if (geglu && !residual && !tuning().no_ln_xstats && gemm_wide_ok(dt, q2) && gemm_route(dt, q2) == ROUTE_WIDE && gemm_pick_splitk(dt, q2) <= 1) { out = name(q2); return out.c_str(); }
-  out = "layernorm+" + name(p);
-  return out.c_str();
+  if (vt) { p.vt = kRouteDummy; p.vt_n0 = 2 * (N / 3); p.vt_S = 256; p.vt_ld = 256; }
+  const LnFold f{kRouteDummy, (const float*)kRouteDummy, (const float*)kRouteDummy};
+  return route_answer(plan_linear(dt, p, ln_fold ? &f : nullptr));
 }
 
 int tango_op_linear_qkv(int dt, const float* x, const float* w, const float* gamma, const float* beta, float* out_qk, float* out_vt,
@@ -371,27 +275,21 @@ int tango_op_linear_qkv_perm(int dt, const float* x, const float* w, const float
   if (!xt || !wt || !wl || !qk || !vt || !bl || !ws) TANGO_FAIL("op_linear_qkv: alloc");
   TANGO_TRY(launch_cast_rows(dt, x, xt, K, M, K, s));
   TANGO_TRY(launch_pack(dt, w, wt, N, 1, K, K, 0, 1, K, 0, s));
-  GemmParams p;
-  p.A = xt; p.lda = K; p.W = wt; p.Kp = K; p.bias = nullptr; p.M = M; p.N = N; p.K = K; p.Cin = K;
-  p.mode = GATHER_1D; p.rows_pb = M; p.Lin = M; p.Lout = M;
+  GemmParams p = dense_gemm(xt, K, wt, K, M, N, K);
   p.out = qk; p.ldo = 2 * C; p.epi = EPI_VT; p.vt = vt; p.vt_n0 = 2 * C; p.vt_S = S; p.vt_ld = S; p.vt_perm = vt_perm;
-  TANGO_TRY(gemm_init());
+  LnFold f;
   if (gamma) {
     TANGO_TRY(launch_fold_ln(dt, wt, K, gamma, beta, nullptr, wl, bl, ws, N, K, s));
-    GemmParams q = p;
-    q.W = wl; q.bias = bl; q.ln_fold = 1; q.ln_eps = eps; q.wsum = ws;
-    if (gemm_ln_fold_ok(dt, q)) {
-      TANGO_TRY(launch_gemm(dt, q, s));
-    } else {
-      void* nt = sc.get((size_t)M * K * esz);
-      if (!nt) TANGO_FAIL("op_linear_qkv: alloc");
-      TANGO_TRY(launch_layernorm(dt, xt, K, nt, K, gamma, beta, M, K, eps, s));
-      p.A = nt;
-      TANGO_TRY(launch_gemm(dt, p, s));
-    }
-  } else {
-    TANGO_TRY(launch_gemm(dt, p, s));
+    f = LnFold{wl, bl, ws, eps};
   }
+  GemmPlan pl = plan_linear(dt, p, gamma ? &f : nullptr);
+  if (pl.form == LIN_LN_MATERIAL) {      // (EPI_VT has no XS form)
+    void* nt = sc.get((size_t)M * K * esz);
+    if (!nt) TANGO_FAIL("op_linear_qkv: alloc");
+    TANGO_TRY(launch_layernorm(dt, xt, K, nt, K, gamma, beta, M, K, eps, s));
+    pl.g.A = nt; pl.g.lda = K;
+  }
+  TANGO_TRY(run_gemm(dt, pl.g, sc, s));
   TANGO_TRY(to_f32(dt, qk, 2 * C, out_qk, M, 2 * C, s));
   TANGO_TRY(to_f32(dt, vt, S, out_vt, B * C, S, s));
   TANGO_HIP(hipStreamSynchronize(s));
@@ -428,12 +326,10 @@ int tango_op_ff_fused(int dt, const float* x, const float* w1, const float* b1, 
   FFParams f;
   f.x = xt; f.ldx = C; f.w1 = w1l; f.ld1 = C; f.b1 = b1l; f.w2 = w2t; f.ld2 = H; f.b2 = b2t; f.out = ot; f.ldo = C;
   f.M = M; f.C = C; f.H = H; f.eps = eps;
-  GemmParams p1, p2;
-  p1.A = xt; p1.lda = C; p1.W = w1l; p1.Kp = C; p1.bias = b1l; p1.M = M; p1.N = N1; p1.K = C; p1.Cin = C;
-  p1.mode = GATHER_1D; p1.rows_pb = M; p1.Lin = M; p1.Lout = M; p1.out = gg; p1.ldo = H; p1.epi = EPI_GEGLU;
+  GemmParams p1 = dense_gemm(xt, C, w1l, C, M, N1, C), p2 = dense_gemm(gg, H, w2t, H, M, C, H);
+  p1.bias = b1l; p1.out = gg; p1.ldo = H; p1.epi = EPI_GEGLU;
   p1.ln_fold = 1; p1.ln_eps = eps; p1.wsum = ws;
-  p2.A = gg; p2.lda = H; p2.W = w2t; p2.Kp = H; p2.bias = b2t; p2.M = M; p2.N = C; p2.K = H; p2.Cin = H;
-  p2.mode = GATHER_1D; p2.rows_pb = M; p2.Lin = M; p2.Lout = M; p2.out = ot; p2.ldo = C; p2.R = xt; p2.ldr = C;
+  p2.bias = b2t; p2.out = ot; p2.ldo = C; p2.R = xt; p2.ldr = C;
   if (mode == 1 && !gemm_ln_fold_ok(dt, p1)) TANGO_FAIL("op_ff_fused: mode 1 needs a LayerNorm-folding GEMM for this shape");
   auto once = [&]() -> int {
     if (mode == 0) return launch_ff_fused(dt, f, s);
@@ -441,20 +337,7 @@ int tango_op_ff_fused(int dt, const float* x, const float* w1, const float* b1, 
     return launch_gemm(dt, p2, s);
   };
   TANGO_TRY(once());
-  if (reps > 0 && ms_out) {
-    hipEvent_t e0, e1;
-    TANGO_HIP(hipEventCreate(&e0));
-    TANGO_HIP(hipEventCreate(&e1));
-    TANGO_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < reps; ++i) TANGO_TRY(once());
-    TANGO_HIP(hipEventRecord(e1, s));
-    TANGO_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    TANGO_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_out = ms / (float)reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  if (reps > 0 && ms_out) TANGO_TRY(time_reps(once, reps, ms_out, s));
   TANGO_TRY(to_f32(dt, ot, C, out, M, C, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
@@ -487,28 +370,13 @@ int tango_op_qkv_stat(int dt, const float* x, const float* w, const float* gamma
   const int perm = (mode & 2) ? 1 : 0;
   mode &= 1;
   q.vt_perm = perm;
-  GemmParams g;
-  g.A = xt; g.lda = K; g.W = wl; g.Kp = K; g.bias = bl; g.M = M; g.N = N; g.K = K; g.Cin = K;
-  g.mode = GATHER_1D; g.rows_pb = M; g.Lin = M; g.Lout = M;
-  g.out = qk; g.ldo = 2 * C; g.epi = EPI_VT; g.vt = vt; g.vt_n0 = 2 * C; g.vt_S = S; g.vt_ld = S; g.vt_perm = perm;
+  GemmParams g = dense_gemm(xt, K, wl, K, M, N, K);
+  g.bias = bl; g.out = qk; g.ldo = 2 * C; g.epi = EPI_VT; g.vt = vt; g.vt_n0 = 2 * C; g.vt_S = S; g.vt_ld = S; g.vt_perm = perm;
   g.ln_fold = 1; g.ln_eps = eps; g.wsum = ws;
   if (mode == 1 && !gemm_ln_fold_ok(dt, g)) TANGO_FAIL("op_qkv_stat: mode 1 needs a LayerNorm-folding GEMM for this shape");
   auto once = [&]() -> int { return mode == 0 ? launch_qkv_stat(dt, q, s) : launch_gemm(dt, g, s); };
   TANGO_TRY(once());
-  if (reps > 0 && ms_out) {
-    hipEvent_t e0, e1;
-    TANGO_HIP(hipEventCreate(&e0));
-    TANGO_HIP(hipEventCreate(&e1));
-    TANGO_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < reps; ++i) TANGO_TRY(once());
-    TANGO_HIP(hipEventRecord(e1, s));
-    TANGO_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    TANGO_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_out = ms / (float)reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  if (reps > 0 && ms_out) TANGO_TRY(time_reps(once, reps, ms_out, s));
   TANGO_TRY(to_f32(dt, qk, 2 * C, out_qk, M, 2 * C, s));
   TANGO_TRY(to_f32(dt, vt, S, out_vt, B * C, S, s));
   TANGO_HIP(hipStreamSynchronize(s));
@@ -571,17 +439,10 @@ int tango_op_conv2d_ex(int dt, const float* x, const float* w, const float* bias
 
 const char* tango_debug_conv2d_route(int dt, int B, int Cin, int H, int W, int Cout, int stride, int ups, int pad, int residual, int e_act,
                                      int out_f32, int* splitk) {
-  GemmParams p;
-  if ((Cin * dtype_size(dt)) % 64 != 0) {
-    p = conv2d_im2col_problem(B, Cin, H, W, Cout);
-  } else {
-    p = conv2d_problem(B, Cin, H, W, Cout, stride, ups, pad);
-  }
+  GemmParams p = (Cin * dtype_size(dt)) % 64 != 0 ? conv2d_im2col_problem(B, Cin, H, W, Cout) : conv2d_problem(B, Cin, H, W, Cout, stride, ups, pad);
   p.A = kRouteDummy; p.W = kRouteDummy; p.bias = (const float*)kRouteDummy; p.out = kRouteDummy; p.out_f32 = out_f32; p.e_act = e_act;
   if (residual) { p.R = kRouteDummy; p.ldr = Cout; }
-  const bool phase = p.mode == GATHER_2D && ups == 1 && stride == 1 && gemm_pick_splitk(dt, p) <= 1 && gemm_route(dt, p) == ROUTE_CONV_WIDE &&
-                     conv_ups_phase_ok(dt, p);
-  return route_answer(dt, p, splitk, phase ? "+phase" : "");
+  return route_answer(plan_conv3x3(dt, p, true), splitk);
 }
 
 const char* tango_debug_conv1d_route(int dt, int B, int Cin, int L, int Cout, int taps, int tap_step, int in_off, int rows_pb, int out_mul,
@@ -590,7 +451,7 @@ const char* tango_debug_conv1d_route(int dt, int B, int Cin, int L, int Cout, in
   GemmParams p = gather1d_problem(B, Cin, L, Cout, taps, tap_step, in_off, rows_pb, rows_pb * out_mul + out_off, out_mul, out_off);
   p.A = kRouteDummy; p.W = kRouteDummy; p.bias = (const float*)kRouteDummy; p.out = kRouteDummy; p.a_act = a_act; p.e_act = e_act;
   if (residual) { p.R = kRouteDummy; p.ldr = Cout; }
-  return route_answer(dt, p, splitk);
+  return route_answer(plan_gemm(dt, p), splitk);
 }
 
 int tango_debug_conv_transpose1d_phase(int B, int Cin, int L, int Cout, int k, int u, int pd, int r, int* geom6) {
@@ -615,10 +476,8 @@ int tango_op_gemm_batched(int dt, const float* a, const float* w, const float* b
   if (!at || !ot || (w && !wt)) TANGO_FAIL("op_gemm_batched: alloc");
   TANGO_TRY(launch_cast_rows(dt, a, at, lda, na * M, lda, s));
   if (w) TANGO_TRY(launch_cast_rows(dt, w, wt, ldw, batch * N, ldw, s));
-  GemmParams p;
-  p.A = at; p.lda = lda; p.W = w ? (const void*)wt : (const void*)((const char*)at + (size_t)w_col_off * esz); p.Kp = ldw;
+  GemmParams p = dense_gemm(at, lda, w ? (const void*)wt : (const void*)((const char*)at + (size_t)w_col_off * esz), ldw, M, N, K);
   p.bias = bias; p.bias_rows = bias_rows;
-  p.M = M; p.N = N; p.K = K; p.Cin = K; p.mode = GATHER_1D; p.rows_pb = M; p.Lin = M; p.Lout = M; p.taps = 1;
   p.out = ot; p.ldo = N; p.alpha = alpha;
   p.batch = batch; p.sA = a_shared ? 0 : (int64_t)M * lda; p.sW = (int64_t)N * ldw; p.sO = (int64_t)M * N;
   TANGO_TRY(run_gemm(dt, p, sc, s));

@@ -266,6 +266,37 @@ def test_linear_ln_rows_on_offsets(lib, name, env, M, N, K, geglu, res, dtype, r
     check_rows("linear_ln %s (%s) M=%d N=%d K=%d" % (name, route, M, N, K), dtype, [("y", out, ref, r32)])
 
 
+# shapes where a materialised LayerNorm is followed by a split-K GEMM: the wrapper, its route query and the engine plan one way (gemm.hip plan_linear)
+LN_SPLITK_CASES = [(300, 320, 320, "fp32"), (512, 1280, 1280, "fp16"), (512, 1280, 1280, "bf16")]
+
+
+@pytest.mark.parametrize("M,N,K,dtype", LN_SPLITK_CASES, ids=["%dx%dx%d-%s" % c for c in LN_SPLITK_CASES])
+def test_linear_ln_wrapper_equals_its_query_and_its_parts(lib, M, N, K, dtype):
+    """LayerNorm, no GEGLU, no residual: the query names layernorm + split-K tile GEMM, and tango_op_linear_ln runs exactly those two launches, so its
+    output is bit-identical to tango_op_linear(tango_op_layernorm(x)).  (Before the wrapper shared the engine's planner it ran the GEMM unsplit
+    while the query said split: max |wrapper - parts| was 3.3e-6 in fp32, 3.9e-3 in fp16 and 1.6e-2 in bf16 on outputs of scale 6.5, all three cases failing.)"""
+    g = torch.Generator().manual_seed(M + N + K)
+    x = ln_rows(g, M, K, dtype)
+    w = q(torch.randn(N, K, generator=g) / K ** 0.5, dtype)
+    b = torch.randn(N, generator=g)
+    ga, be = ln_affine(g, K)
+    xg, wg, bg, gg, eg = (t.cuda() for t in (x, w, b, ga, be))
+    route = lib.tango_debug_linear_route(DT[dtype], M, N, K, 0, 1, 0, 0).decode()
+    assert route == "layernorm+tile+splitk", route
+    fused = torch.zeros(M, N, device="cuda")
+    rc = lib.tango_op_linear_ln(DT[dtype], p(xg), p(wg), p(bg), p(gg), p(eg), None, p(fused), M, N, K, 0, 1e-5, None)
+    assert rc == 0, lib.tango_last_error().decode()
+    xn = torch.zeros(M, K, device="cuda")
+    rc = lib.tango_op_layernorm(DT[dtype], p(xg), p(gg), p(eg), p(xn), M, K, 1e-5, None)
+    assert rc == 0, lib.tango_last_error().decode()
+    parts = torch.zeros(M, N, device="cuda")
+    rc = lib.tango_op_linear(DT[dtype], p(xn), p(wg), p(bg), None, p(parts), M, N, K, 0, 0, 0, None)
+    assert rc == 0, lib.tango_last_error().decode()
+    diff = (fused - parts).abs().max().item()
+    print("linear_ln %dx%dx%d %s (%s): max |wrapper - parts| = %.3e of scale %.3e" % (M, N, K, dtype, route, diff, parts.abs().max().item()))
+    assert torch.equal(fused, parts)
+
+
 # tango_op_qkv_stat (the activation-stationary kernel) takes the 16-bit types only: (qkv_stat, fp32) is the one combination left out
 QKV_CASES = [("qkv_stat", d) for d in DTYPES[1:]] + [("linear_qkv", d) for d in DTYPES]
 

@@ -1,7 +1,8 @@
 """Which kernel takes the gather-GEMM problems that only the mel-VAE and HiFi-GAN plans (and the large-batch UNet downsampler) pose:
 the shapes of tests/test_vae_voc_ops_gpu.py, pinned through the host-side queries tango_debug_conv2d_route / tango_debug_conv1d_route
--- no GPU needed.  The queries build their GemmParams with the code of the tango_op_* wrappers, so the answer is the wrapper's route;
-the GPU tests assert the same table again, under the same switches, before they run a case.
+-- no GPU needed.  The queries, the tango_op_* wrappers and the engine's plan builders build their GemmParams with the same constructors
+(csrc/problem.h) and take split-K, route and phase form from the same planner (csrc/gemm.hip plan_gemm / plan_conv3x3), so the answer is
+the wrapper's route and the plan's; the GPU tests assert the same table again, under the same switches, before they run a case.
 
 Why these shapes (csrc/gemm_dma.hip gemm_dma_ok, csrc/gemm.hip gemm_pick_splitk):
   * gemm_dma_kernel takes convs from 448 tiles of 256 rows on, or any number under TANGO_FORCE_DMA_GEMM=1; it is the only 8-wave kernel
