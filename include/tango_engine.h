@@ -303,6 +303,30 @@ int tango_op_linear(int dtype, const float* x, const float* w, const float* bias
                     int N, int K, int a_act, int e_act, int geglu, void* stream);
 int tango_op_linear_ln(int dtype, const float* x, const float* w, const float* bias, const float* gamma, const float* beta,
                        const float* residual, float* out, int M, int N, int K, int geglu, float eps, void* stream);
+/* out[M,N] = x[M,K] W^T (+ bias) (+ bias2[step]) (+ residual) with the epilogue arms only the engine's plan builders set (tests/
+ * test_gemm_engine_arms_gpu.py); split-K as the engine applies it.  All tensors fp32 on the device.
+ *   bias2 [steps][N] or NULL: the per-step bias table; `step` goes into a device int the kernels read.  step = -1: no step pointer (row 0).
+ *   rowvec [ceil(rowvec_rows / rowvec_per)][N] or NULL: rows m < rowvec_rows also get rowvec[m / rowvec_per] and are written to out_lo, not out.
+ *   wb_rows != 0: w holds M / wb_rows matrices [N][K] back to back, rows [s wb_rows, (s + 1) wb_rows) multiply with the s-th.  The weight
+ *   rows are dense inside (row stride Kp = K, so wb_stride = N K): K must be a whole number of 16-byte vectors or the launch is refused.
+ *   pad (0 or a multiple of 8): the activation, residual and out rows are pitched to K + pad / N + pad elements inside; out is fp32
+ *   [M][N + pad] and out_lo (required with rowvec) fp32 [M][N + (pad ? pad + 8 : 0)].  Both are copied INTO the launch's output buffers first,
+ *   pitch columns included, and copied back whole: what the launch did not write comes back as the caller left it (rounded to the dtype).
+ *   plan (may be NULL): receives the plan name of the launch ("wide", "wide+pers", "duo", "tile", "tile+splitk", "dma", ...). */
+int tango_op_linear_ex(int dtype, const float* x, const float* w, const float* bias, const float* bias2, int steps, int step,
+                       const float* residual, const float* rowvec, int rowvec_rows, int rowvec_per, int wb_rows, int pad, float* out,
+                       float* out_lo, int M, int N, int K, char* plan, int plan_cap, void* stream);
+/* host-side query, no GPU needed: "" when launch_gemm accepts the problem tango_op_linear_ex builds for these arguments (the int flags say which
+ * pointers are set; geglu puts the GEGLU epilogue on top), else the message it fails with; plan as above.  tests/test_gemm_refusals.py */
+const char* tango_debug_linear_ex_check(int dtype, int M, int N, int K, int residual, int bias2, int rowvec, int rowvec_rows, int rowvec_per,
+                                        int out_lo, int wb_rows, int pad, int geglu, char* plan, int plan_cap);
+/* conv1 of a ResNet block: 3x3 / stride 1 / pad 1 conv + bias + bias2[step] (the time-embedding table [steps][Cout], step in a device int)
+ * (+ residual [B][Cout][H][W] or NULL); plan as above */
+int tango_op_conv2d_temb(int dtype, const float* x, const float* w, const float* bias, const float* bias2, int steps, int step,
+                         const float* residual, float* out, int B, int Cin, int H, int W, int Cout, char* plan, int plan_cap, void* stream);
+/* tango_op_conv2d_ups with bias2 as such a table */
+int tango_op_conv2d_ups_temb(int dtype, const float* x, const float* w, const float* bias, const float* bias2, int steps, int step, float* out,
+                             int B, int Cin, int H, int W, int Cout, int phases, char* plan, int plan_cap, void* stream);
 /* fused self-attention projection as the engine runs it (reference: diffusers attention_processor.py Attention.to_q/to_k/to_v on
    LayerNorm(x), transformer_2d BasicTransformerBlock.norm1): q | k row-major into out_qk [B*S, 2C], v TRANSPOSED into out_vt
    [B][C][S]; gamma == NULL skips the LayerNorm */

@@ -120,6 +120,7 @@ SYMBOLS = [
     "tango_op_conv2d_ex", "tango_op_gemm_batched", "tango_op_softmax_rows", "tango_op_conv1d_i16", "tango_op_avg3_act",
     "tango_op_pointwise_small", "tango_op_pointwise_out_nchw", "tango_debug_conv2d_route", "tango_debug_conv1d_route",
     "tango_debug_conv_transpose1d_phase",
+    "tango_op_linear_ex", "tango_debug_linear_ex_check", "tango_op_conv2d_temb", "tango_op_conv2d_ups_temb",
 ]
 
 _lib = None
@@ -211,6 +212,11 @@ def load():
     lib.tango_debug_conv1d_route.argtypes = [ci] * 14 + [C.POINTER(ci)]
     lib.tango_debug_conv1d_route.restype = C.c_char_p
     lib.tango_debug_conv_transpose1d_phase.argtypes = [ci] * 8 + [C.POINTER(ci)]
+    lib.tango_op_linear_ex.argtypes = [ci, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, C.c_char_p, ci, vp]
+    lib.tango_debug_linear_ex_check.argtypes = [ci] * 13 + [C.c_char_p, ci]
+    lib.tango_debug_linear_ex_check.restype = C.c_char_p
+    lib.tango_op_conv2d_temb.argtypes = [ci, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, ci, C.c_char_p, ci, vp]
+    lib.tango_op_conv2d_ups_temb.argtypes = [ci, vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, C.c_char_p, ci, vp]
     _lib = lib
     return lib
 

@@ -200,14 +200,16 @@ struct GemmParams {
   // Per-sample row vector for a leading range of rows (round 4; gemm_wide_device.h wide_epilogue only -- the 256 x 320 and 256 x 160
   // kernels): rows m < rowvec_rows additionally get rowvec[(m / rowvec_per) * N + n] (fp32) and are written to out_lo (row stride
   // ldo_lo) instead of `out`.  The single-key cross-attention rows of a CFG batch (engine.hip transformer()): attn1's to_out + residual
-  // writes x + attn1 + [to_out2(v_key) + b] for the unconditional samples in one pass.  rowvec_rows % 64 == 0, rowvec_per % 64 == 0.
+  // writes x + attn1 + [to_out2(v_key) + b] for the unconditional samples in one pass.  rowvec_rows % 64 == 0, rowvec_per % 64 == 0, and
+  // rowvec set means out_lo set (gemm_rowvec_ok refuses otherwise; rowvec_rows == 0 is legal and writes nothing to out_lo).
   const float* rowvec = nullptr;
   int64_t rowvec_rows = 0;
   int rowvec_per = 1;
   void* out_lo = nullptr;
   int64_t ldo_lo = 0;
   // Per-sample weights (round 6: GroupNorm folded into proj_in, norm.hip gn_fold_kernel): rows [s * wb_rows, (s + 1) * wb_rows) multiply with
-  // W + s * wb_stride elements (wb_rows % 256 == 0: a tile never straddles two samples).  256 x 320 GEMM kernels only.
+  // W + s * wb_stride elements (wb_rows % 256 == 0: a tile never straddles two samples; M % wb_rows == 0; launch_gemm refuses otherwise).
+  // 256 x 320 / 256 x 160 GEMM kernels only.
   int64_t wb_stride = 0;
   int wb_rows = 0;
   // LayerNorm folded into the weights (linear_stream.hip): y = rstd*(W'x - mean*wsum) + b'
@@ -228,6 +230,9 @@ struct GemmParams {
 
 int launch_gemm(int dtype, const GemmParams& p, hipStream_t s);
 enum GemmRoute : int { ROUTE_NONE = 0, ROUTE_WIDE, ROUTE_STREAM, ROUTE_CONV_WIDE, ROUTE_CONV_HALO, ROUTE_DMA, ROUTE_TILE, ROUTE_DUO };
+// the message launch_gemm() fails with before it picks a kernel, or nullptr (host only: shapes, strides and pointer alignment);
+// *route_out, if given, receives gemm_route() of the problem
+const char* gemm_launch_refusal(int dtype, const GemmParams& p, int* route_out = nullptr);
 int gemm_route(int dtype, const GemmParams& p);   // which kernel family launch_gemm() picks for this problem
 bool gemm_rowvec_ok(int dtype, const GemmParams& p);   // the kernel that takes this problem implements GemmParams::rowvec
 bool conv_halo_ok(int dtype, const GemmParams& p);

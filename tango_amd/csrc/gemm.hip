@@ -402,7 +402,9 @@ int gemm_route(int dtype, const GemmParams& p) {
 // can the kernel that will take this problem apply GemmParams::rowvec?  (the engine asks at plan-build time; launch_gemm re-checks)
 bool gemm_rowvec_ok(int dtype, const GemmParams& p) {
   if (p.epi != EPI_NONE || p.splitk > 1 || gemm_pick_splitk(dtype, p) > 1) return false;
-  if (p.rowvec_rows % 64 != 0 || p.rowvec_per % 64 != 0 || p.rowvec_rows > p.M) return false;
+  if (p.rowvec_rows < 0 || p.rowvec_rows % 64 != 0 || p.rowvec_per <= 0 || p.rowvec_per % 64 != 0 || p.rowvec_rows > p.M) return false;
+  // rowvec set = the epilogue may store through out_lo (rowvec_rows == 0 stores nothing there and stays legal, with a valid out_lo)
+  if (p.rowvec && !p.out_lo) return false;
   if (p.out_lo && (p.ldo_lo % 8 != 0 || ((uintptr_t)p.out_lo & 15))) return false;
   if ((uintptr_t)p.rowvec & 15) return false;
   const int r = gemm_route(dtype, p);
@@ -475,14 +477,27 @@ std::string plan_name(const GemmPlan& pl) {
   return s;
 }
 
-int launch_gemm(int dtype, const GemmParams& p, hipStream_t s) {
-  if (p.rowvec && !gemm_rowvec_ok(dtype, p)) TANGO_FAIL("gemm: rowvec is only implemented by the 256 x 320 / 256 x 160 GEMM epilogues");
+// Why launch_gemm() refuses this problem before it picks a kernel (nullptr: it does not).  Host only, looks at shapes, strides and pointer
+// alignment: the route queries ask it for problems built on never-dereferenced pointers.
+const char* gemm_launch_refusal(int dtype, const GemmParams& p, int* route_out) {
+  if (p.rowvec && !gemm_rowvec_ok(dtype, p))
+    return "gemm: rowvec needs the plain epilogue of the unsplit 256 x 320 / 256 x 160 GEMMs, whole 64-row blocks and an aligned out_lo";
   const int route = gemm_route(dtype, p);
-  if (p.epi == EPI_VT && p.vt_perm && (p.vt_S % 32 != 0 || dtype == DT_F32)) TANGO_FAIL("gemm: vt_perm permutes whole blocks of 32 tokens of a 16-bit V^T (vt_S % 32 == 0)");
-  if (p.wb_rows && route != ROUTE_WIDE && route != ROUTE_DUO) TANGO_FAIL("gemm: per-sample weights are implemented by the 256 x 320 / 256 x 160 GEMMs only");
+  if (route_out) *route_out = route;
+  if (p.epi == EPI_VT && p.vt_perm && (p.vt_S % 32 != 0 || dtype == DT_F32)) return "gemm: vt_perm permutes whole blocks of 32 tokens of a 16-bit V^T (vt_S % 32 == 0)";
+  if (p.wb_rows && route != ROUTE_WIDE && route != ROUTE_DUO) return "gemm: per-sample weights are implemented by the 256 x 320 / 256 x 160 GEMMs only";
+  // a 256-row tile multiplies with ONE sample's weights (W + (m0 / wb_rows) * wb_stride): samples are whole tiles, the rows whole samples
+  if (p.wb_rows && (p.wb_rows < 0 || p.wb_rows % 256 != 0 || p.M % p.wb_rows != 0))
+    return "gemm: per-sample weights need wb_rows % 256 == 0 and M % wb_rows == 0";
   if (p.glu_tanh && dtype != DT_F32 && route != ROUTE_WIDE && route != ROUTE_DUO)
-    TANGO_FAIL("gemm: the tanh-GELU gate (T5 gated-gelu) is implemented by the fp32 kernels and the 256 x 320 / 256 x 160 GEMMs only");
-  if (p.Wph && route != ROUTE_CONV_WIDE) TANGO_FAIL("gemm: upsampler phase weights are implemented by the 256 x 320 conv only");
+    return "gemm: the tanh-GELU gate (T5 gated-gelu) is implemented by the fp32 kernels and the 256 x 320 / 256 x 160 GEMMs only";
+  if (p.Wph && route != ROUTE_CONV_WIDE) return "gemm: upsampler phase weights are implemented by the 256 x 320 conv only";
+  return nullptr;
+}
+
+int launch_gemm(int dtype, const GemmParams& p, hipStream_t s) {
+  int route = ROUTE_NONE;
+  if (const char* why = gemm_launch_refusal(dtype, p, &route)) TANGO_FAIL(why);
   switch (route) {
     case ROUTE_WIDE: return launch_gemm_wide(dtype, p, s);
     case ROUTE_DUO: return launch_gemm_duo(dtype, p, s);

@@ -75,6 +75,30 @@ static int run_gemm(int dt, GemmParams& p, Scratch& sc, hipStream_t s) {
   return launch_gemm(dt, p, s);
 }
 
+// plan_name() of the problem as launch_gemm() takes it (after run_gemm's split-K), into the caller's buffer
+static void report_plan(int dt, const GemmParams& p, char* plan, int plan_cap) {
+  if (!plan || plan_cap <= 0) return;
+  GemmPlan pl;
+  pl.splitk = p.splitk;
+  pl.route = gemm_route(dt, p);
+  pl.pers = pl.route == ROUTE_WIDE && gemm_wide_persistent(dt, p);
+  pl.phase = p.Wph != nullptr;
+  snprintf(plan, (size_t)plan_cap, "%s", plan_name(pl).c_str());
+}
+
+// the step of a per-step bias table [steps][N] as the engine passes it, in a device int (steps == 0: one row, *step_ptr stays null)
+static int device_step(int steps, int step, Scratch& sc, hipStream_t s, const int** step_ptr) {
+  *step_ptr = nullptr;
+  if (steps <= 0) return 0;
+  if (step < 0 || step >= steps) TANGO_FAIL("op: step must be in [0, steps)");
+  int* dstep = (int*)sc.get(256);
+  if (!dstep) TANGO_FAIL("op: alloc");
+  TANGO_HIP(hipMemcpyAsync(dstep, &step, 4, hipMemcpyHostToDevice, s));
+  TANGO_HIP(hipStreamSynchronize(s));     // `step` is this call's stack
+  *step_ptr = dstep;
+  return 0;
+}
+
 // mean time of `reps` back-to-back repeats of an op's launches (HIP events on `s`), for same-process A/Bs
 template <typename Once> static int time_reps(Once&& once, int reps, float* ms_out, hipStream_t s) {
   hipEvent_t e0, e1;
@@ -94,9 +118,11 @@ template <typename Once> static int time_reps(Once&& once, int reps, float* ms_o
 
 // phases: -1 = as the engine decides (phase form where conv_ups_phase_ok), 0 = nine-tap form, 1 = phase form or an error
 // residual [B][Cout][Ho][Wo] or null; out_f32: the GEMM writes fp32 rows (ldo = Cout) itself, as the VAE plans do for conv_out
+// bias2: one row [Cout] (steps == 0), or the engine's form: a table [steps][Cout] indexed by `step` through a device int.  plan: plan_name() of the launch
 static int op_conv2d_impl(int dt, const float* x, const float* w, const float* bias, const float* bias2, float* out, int B, int Cin, int H, int W,
                           int Cout, int stride, int upsample, int phases, void* stream, int pad = 1, const float* residual = nullptr,
-                          int e_act = ACT_NONE, float e_slope = 0.f, int out_f32 = 0) {
+                          int e_act = ACT_NONE, float e_slope = 0.f, int out_f32 = 0, int steps = 0, int step = 0, char* plan = nullptr,
+                          int plan_cap = 0) {
   hipStream_t s = (hipStream_t)stream;
   const size_t esz = dtype_size(dt);
   Scratch sc;
@@ -133,7 +159,10 @@ static int op_conv2d_impl(int dt, const float* x, const float* w, const float* b
   }
   p.bias = bias; p.out = ot; p.out_f32 = out_f32; p.e_act = e_act; p.e_slope = e_slope;
   if (rt) { p.R = rt; p.ldr = Cout; }
-  if (bias2) { p.bias2 = bias2; p.bias2_stride = Cout; }
+  if (bias2) {
+    p.bias2 = bias2; p.bias2_stride = Cout;
+    TANGO_TRY(device_step(steps, step, sc, s, &p.step_ptr));
+  }
   if (!im2col) {
     const bool ph_ok = plan_conv3x3(dt, p, phases != 0).phase;
     if (phases == 1 && !ph_ok) TANGO_FAIL("op_conv2d_ups: the phase form does not take this problem");
@@ -145,6 +174,7 @@ static int op_conv2d_impl(int dt, const float* x, const float* w, const float* b
     }
   }
   TANGO_TRY(run_gemm(dt, p, sc, s));
+  report_plan(dt, p, plan, plan_cap);
   TANGO_TRY(launch_nhwc_to_nchw_f32(out_f32 ? (int)DT_F32 : dt, ot, Cout, out, B, Cout, Ho * Wo, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
@@ -200,6 +230,62 @@ static int op_linear_impl(int dt, const float* x, const float* w, const float* b
   return 0;
 }
 
+// The linear with the epilogue arms only the engine's plan builders set (tango_op_linear_ex and its host-only query build it here): per-step
+// bias table, rowvec / out_lo, per-sample weights; `pad` elements of pitch on the activation, output and residual rows, and a different
+// pitch on out_lo, as the engine's views have
+static int64_t linear_ex_ldo_lo(int N, int pad) { return N + (pad ? pad + 8 : 0); }
+static GemmParams linear_ex_problem(const void* x, const void* w, const float* bias, const float* bias2, const int* step_ptr, const void* residual,
+                                    const float* rowvec, int rowvec_rows, int rowvec_per, void* out, void* out_lo, int wb_rows, int pad, int M,
+                                    int N, int K) {
+  GemmParams p = dense_gemm(x, K + pad, w, K, M, N, K);
+  p.bias = bias; p.out = out; p.ldo = N + pad;
+  if (residual) { p.R = residual; p.ldr = N + pad; }
+  if (bias2) { p.bias2 = bias2; p.bias2_stride = N; p.step_ptr = step_ptr; }
+  if (rowvec) { p.rowvec = rowvec; p.rowvec_rows = rowvec_rows; p.rowvec_per = rowvec_per; p.out_lo = out_lo; p.ldo_lo = linear_ex_ldo_lo(N, pad); }
+  if (wb_rows) { p.wb_rows = wb_rows; p.wb_stride = (int64_t)N * K; }
+  return p;
+}
+
+static int op_linear_ex_impl(int dt, const float* x, const float* w, const float* bias, const float* bias2, int steps, int step,
+                             const float* residual, const float* rowvec, int rowvec_rows, int rowvec_per, int wb_rows, int pad, float* out,
+                             float* out_lo, int M, int N, int K, char* plan, int plan_cap, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const size_t esz = dtype_size(dt);
+  if (M <= 0 || N <= 0 || K <= 0 || pad < 0 || pad % 8 != 0 || wb_rows < 0) TANGO_FAIL("op_linear_ex: bad sizes (pad: 0 or a multiple of 8)");
+  if (bias2 && steps > 0 && (step < -1 || step >= steps)) TANGO_FAIL("op_linear_ex: step must be in [0, steps), or -1 for no step pointer");
+  if (rowvec && (rowvec_rows < 0 || rowvec_rows > M || rowvec_per <= 0)) TANGO_FAIL("op_linear_ex: rowvec_rows must be in [0, M], rowvec_per > 0");
+  Scratch sc;
+  const int64_t lda = K + pad, ldo = N + pad, ldl = linear_ex_ldo_lo(N, pad);
+  const int nw = wb_rows ? (M + wb_rows - 1) / wb_rows : 1;
+  void* xt = sc.get((size_t)M * lda * esz);
+  void* wt = sc.get((size_t)nw * N * K * esz);
+  void* ot = sc.get((size_t)M * ldo * esz);
+  void* lt = (rowvec && out_lo) ? sc.get((size_t)M * ldl * esz) : nullptr;
+  void* rt = residual ? sc.get((size_t)M * ldo * esz) : nullptr;
+  if (!xt || !wt || !ot || (rowvec && out_lo && !lt) || (residual && !rt)) TANGO_FAIL("op_linear_ex: alloc");
+  const int* dstep = nullptr;
+  if (bias2) TANGO_TRY(device_step(step < 0 ? 0 : steps, step, sc, s, &dstep));
+  GemmParams p = linear_ex_problem(xt, wt, bias, bias2, dstep, rt, rowvec, rowvec_rows, rowvec_per, ot, lt, wb_rows, pad, M, N, K);
+  // what launch_gemm() refuses, before anything of the caller's is read: w holds M / wb_rows matrices only if wb_rows passes
+  if (const char* why = gemm_launch_refusal(dt, p)) TANGO_FAIL(why);
+  TANGO_HIP(hipMemsetAsync(xt, 0, (size_t)M * lda * esz, s));
+  TANGO_TRY(launch_cast_rows(dt, x, xt, lda, M, K, s));
+  TANGO_TRY(launch_pack(dt, w, wt, nw * N, 1, K, K, 0, 1, K, 0, s));
+  if (residual) {
+    TANGO_HIP(hipMemsetAsync(rt, 0, (size_t)M * ldo * esz, s));
+    TANGO_TRY(launch_cast_rows(dt, residual, rt, ldo, M, N, s));
+  }
+  // the caller's out / out_lo, pitch columns included, are what the launch finds in its output buffers
+  TANGO_TRY(launch_cast_rows(dt, out, ot, ldo, M, (int)ldo, s));
+  if (lt) TANGO_TRY(launch_cast_rows(dt, out_lo, lt, ldl, M, (int)ldl, s));
+  TANGO_TRY(run_gemm(dt, p, sc, s));
+  report_plan(dt, p, plan, plan_cap);
+  TANGO_TRY(to_f32(dt, ot, ldo, out, M, (int)ldo, s));
+  if (lt) TANGO_TRY(to_f32(dt, lt, ldl, out_lo, M, (int)ldl, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 // ---- host-only route queries: the wrappers' problems with never-dereferenced aligned pointers, planned as the wrappers plan them ----
 static void* const kRouteDummy = (void*)(uintptr_t)0x10000;
 static const char* route_answer(const GemmPlan& pl, int* splitk_out = nullptr) {
@@ -219,6 +305,20 @@ int tango_op_conv2d(int dt, const float* x, const float* w, const float* bias, f
 int tango_op_conv2d_ups(int dt, const float* x, const float* w, const float* bias, const float* bias2, float* out, int B, int Cin, int H,
                         int W, int Cout, int phases, void* stream) {
   return op_conv2d_impl(dt, x, w, bias, bias2, out, B, Cin, H, W, Cout, 1, 1, phases ? 1 : 0, stream);
+}
+
+int tango_op_conv2d_ups_temb(int dt, const float* x, const float* w, const float* bias, const float* bias2, int steps, int step, float* out,
+                             int B, int Cin, int H, int W, int Cout, int phases, char* plan, int plan_cap, void* stream) {
+  if (!bias2 || steps <= 0) TANGO_FAIL("op_conv2d_ups_temb: a bias2 table of steps > 0 rows is required");
+  return op_conv2d_impl(dt, x, w, bias, bias2, out, B, Cin, H, W, Cout, 1, 1, phases ? 1 : 0, stream, 1, nullptr, ACT_NONE, 0.f, 0, steps, step,
+                        plan, plan_cap);
+}
+
+int tango_op_conv2d_temb(int dt, const float* x, const float* w, const float* bias, const float* bias2, int steps, int step,
+                         const float* residual, float* out, int B, int Cin, int H, int W, int Cout, char* plan, int plan_cap, void* stream) {
+  if (!bias2 || steps <= 0) TANGO_FAIL("op_conv2d_temb: a bias2 table of steps > 0 rows is required");
+  return op_conv2d_impl(dt, x, w, bias, bias2, out, B, Cin, H, W, Cout, 1, 0, 0, stream, 1, residual, ACT_NONE, 0.f, 0, steps, step, plan,
+                        plan_cap);
 }
 
 int tango_op_pack_ups_phase(int dt, const float* w, void* out, int Cout, int Cin, void* stream) {
@@ -249,6 +349,29 @@ const char* tango_debug_linear_route(int dt, int M, int N, int K, int geglu, int
   if (vt) { p.vt = kRouteDummy; p.vt_n0 = 2 * (N / 3); p.vt_S = 256; p.vt_ld = 256; }
   const LnFold f{kRouteDummy, (const float*)kRouteDummy, (const float*)kRouteDummy};
   return route_answer(plan_linear(dt, p, ln_fold ? &f : nullptr));
+}
+
+int tango_op_linear_ex(int dt, const float* x, const float* w, const float* bias, const float* bias2, int steps, int step, const float* residual,
+                       const float* rowvec, int rowvec_rows, int rowvec_per, int wb_rows, int pad, float* out, float* out_lo, int M, int N, int K,
+                       char* plan, int plan_cap, void* stream) {
+  return op_linear_ex_impl(dt, x, w, bias, bias2, steps, step, residual, rowvec, rowvec_rows, rowvec_per, wb_rows, pad, out, out_lo, M, N, K, plan,
+                           plan_cap, stream);
+}
+
+const char* tango_debug_linear_ex_check(int dt, int M, int N, int K, int residual, int bias2, int rowvec, int rowvec_rows, int rowvec_per,
+                                        int out_lo, int wb_rows, int pad, int geglu, char* plan, int plan_cap) {
+  // tango_op_linear_ex's problem (geglu: with the GEGLU epilogue on top, which the wrapper itself does not offer), split as run_gemm splits it
+  const float* const fd = (const float*)kRouteDummy;
+  GemmParams p = linear_ex_problem(kRouteDummy, kRouteDummy, fd, bias2 ? fd : nullptr, bias2 ? (const int*)kRouteDummy : nullptr,
+                                   residual ? kRouteDummy : nullptr, rowvec ? fd : nullptr, rowvec_rows, rowvec_per, kRouteDummy,
+                                   out_lo ? kRouteDummy : nullptr, wb_rows, pad, M, N, K);
+  if (geglu) { p.epi = EPI_GEGLU; p.ldo = N / 2 + pad; if (p.R) p.ldr = p.ldo; }
+  gemm_apply_splitk(dt, p, [](size_t) { return (float*)kRouteDummy; });
+  report_plan(dt, p, plan, plan_cap);
+  static thread_local std::string why;
+  const char* r = gemm_launch_refusal(dt, p);
+  why = r ? r : "";
+  return why.c_str();
 }
 
 int tango_op_linear_qkv(int dt, const float* x, const float* w, const float* gamma, const float* beta, float* out_qk, float* out_vt,

@@ -130,6 +130,14 @@ def test_bias_and_per_step_bias_once_per_output_pixel_in_every_phase(lib, dtype)
     for py in (0, 1):
         for px in (0, 1):
             assert (out_b[:, :, py::2, px::2] - out_a[:, :, py::2, px::2]).abs().max().item() > 0.5     # each phase got it
+    # as the engine passes it: row `step` of a table through the device step counter (the other rows are O(1) away from b2)
+    table = torch.stack([b2 + 3.0, b2 - 2.0, b2]).contiguous()
+    out_t = torch.empty_like(out_b)
+    plan = C.create_string_buffer(64)
+    _KEEP.extend([table, out_t])
+    check(lib, lib.tango_op_conv2d_ups_temb(DT[dtype], ptr(x), ptr(w), ptr(b), ptr(table), 3, 2, ptr(out_t), B, Cc, H, W, Cc, 1, plan, 64, None))
+    assert plan.value.decode() == "conv_wide+phase"
+    assert torch.equal(out_t, out_b), "row 2 of the table through the step counter is not the single row b2"
 
 
 def test_full_size_unet_forward_switch_on_against_off(lib):
