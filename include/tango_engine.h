@@ -200,6 +200,33 @@ int tango_engine_finalize_weights(tango_engine_t* h);
 
 int tango_engine_denoise(tango_engine_t* h, const tango_denoise_args_t* args, void* stream);
 
+/* Guidance beyond one scalar (tango_denoise_args_t itself is frozen: its last field stays latent_h).
+ * table:   HOST [N][B] fp32 or NULL.  Entry [i][b] is the guidance scale of latents row b at loop index i; it replaces
+ *          args->guidance_scale, which is then not read.  A table always runs the [uncond; cond] batch (prompt_embeds hold 2B rows,
+ *          whatever the entries): 1.0 gives the conditional output, 0.0 the unconditional one.  Entries must be finite and >= 0.
+ * rescale: phi in [0, 1], the guidance rescale of Lin et al. 2023 (section 3.4; diffusers' guidance_rescale).  Per sample b and step,
+ *          over the n = C_lat * H * W values of the model output (u, c the unconditional and the conditional half, g the scale):
+ *            cfg = u + g * (c - u)                  as without it (models.py:246)
+ *            s_b = std(c) / std(cfg)                unbiased (n - 1), like torch.std
+ *            v   = phi * (cfg * s_b) + (1 - phi) * cfg
+ *          and the scheduler rule runs on v.  Each line is evaluated in fp32 in that order without FMA contraction (1 - phi is an fp32
+ *          subtraction); s_b comes from fp64 sums about the sample's first element, added in a fixed order, so it does not depend on
+ *          the batch size, the row of the sample or sample_offset.  std(cfg) == 0 gives s_b = 1 where the formula gives NaN: the one
+ *          deviation.  phi > 0 needs guidance: a table, or guidance_scale > 1.
+ * With guide NULL, or table NULL and rescale 0, the call is tango_engine_denoise: the same kernels and the same bits.  Otherwise every
+ * step runs two small statistics launches and a table-reading variant of the update kernel, in a captured graph of its own; phi and
+ * the table are read from device memory refreshed per call, so one captured graph serves every phi and every table. */
+typedef struct tango_guidance_args {
+  const float* table;          /* HOST [N][B] or NULL */
+  float rescale;
+} tango_guidance_args_t;
+int tango_engine_denoise_guided(tango_engine_t* h, const tango_denoise_args_t* args, const tango_guidance_args_t* guide, void* stream);
+/* host-side query, no GPU needed: "" when tango_engine_denoise_guided accepts these arguments as far as its argument checks go (no
+ * engine state: shapes against the configuration are checked by the call itself), else the message it fails with: rescale outside
+ * [0, 1] or NaN, rescale > 0 without guidance, a table entry negative or not finite, and every refusal of tango_engine_denoise's own
+ * checks (rule, coef_width, multistep table rows, masking pointers).  Reads args->coef (multistep rule) and guide->table. */
+const char* tango_debug_denoise_guided_check(const tango_denoise_args_t* args, const tango_guidance_args_t* guide);
+
 /* one UNet call: sample [B2,C,H,W] fp32 NCHW, timestep, embeds [B2,L,d], mask [B2,L] -> out [B2,C,H,W] fp32 */
 int tango_engine_unet_forward(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
                               const uint8_t* prompt_mask, float* out, int batch2, int text_len, void* stream);
@@ -433,6 +460,15 @@ int tango_op_sched_masked(float* latents, const float* model_out_nchw, const flo
                           int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
                           const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
                           int pred_type, int rule, void* stream);
+
+/* tango_op_sched_masked's arguments, for every rule, masked (known_latents, latent_mask and blend_coef set) or not (all three and
+ * blend_noise NULL), through the guided kernels: guidance_row HOST [B] is the scale of each sample at this step (cfg must be 1; the
+ * scalar `guidance` is not read), rescale = phi as in tango_guidance_args_t, scale_out HOST [B] or NULL receives the s_b the kernel
+ * used (1.0 everywhere when rescale == 0: no statistics are taken).  Synchronises. */
+int tango_op_sched_guided(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
+                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
+                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
+                          int pred_type, int rule, const float* guidance_row, float rescale, float* scale_out, void* stream);
 
 /* the N(0,1) values the masked loop's device Philox generator uses as the blend noise n_step of loop index `step` (the step noise's
  * counter with bit 31 of the step word set): out fp32 [B, C, HW] */

@@ -103,6 +103,14 @@ class DenoiseArgs(C.Structure):
     ]
 
 
+class GuidanceArgs(C.Structure):
+    """tango_guidance_args_t: what tango_engine_denoise_guided takes beside DenoiseArgs (which stays as it is)"""
+    _fields_ = [
+        ("table", C.c_void_p),
+        ("rescale", C.c_float),
+    ]
+
+
 #: every symbol include/tango_engine.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "tango_last_error", "tango_version", "tango_tuning_reload", "tango_debug_linear_route", "tango_debug_groupnorm_form", "tango_engine_create", "tango_engine_destroy",
@@ -121,6 +129,7 @@ SYMBOLS = [
     "tango_op_pointwise_small", "tango_op_pointwise_out_nchw", "tango_debug_conv2d_route", "tango_debug_conv1d_route",
     "tango_debug_conv_transpose1d_phase",
     "tango_op_linear_ex", "tango_debug_linear_ex_check", "tango_op_conv2d_temb", "tango_op_conv2d_ups_temb",
+    "tango_engine_denoise_guided", "tango_debug_denoise_guided_check", "tango_op_sched_guided",
 ]
 
 _lib = None
@@ -149,6 +158,9 @@ def load():
     lib.tango_engine_set_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), ci]
     lib.tango_engine_finalize_weights.argtypes = [vp]
     lib.tango_engine_denoise.argtypes = [vp, C.POINTER(DenoiseArgs), vp]
+    lib.tango_engine_denoise_guided.argtypes = [vp, C.POINTER(DenoiseArgs), C.POINTER(GuidanceArgs), vp]
+    lib.tango_debug_denoise_guided_check.argtypes = [C.POINTER(DenoiseArgs), C.POINTER(GuidanceArgs)]
+    lib.tango_debug_denoise_guided_check.restype = C.c_char_p
     lib.tango_engine_unet_forward.argtypes = [vp, vp, i64, vp, vp, vp, ci, ci, vp]
     lib.tango_engine_unet_forward_music.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.tango_engine_vae_decode.argtypes = [vp, vp, vp, ci, vp]
@@ -198,6 +210,7 @@ def load():
     lib.tango_op_philox_normal.argtypes = [vp, ci, ci, ci, ci, C.c_uint64, ci, vp]
     lib.tango_op_philox_normal_blend.argtypes = [vp, ci, ci, ci, ci, C.c_uint64, ci, vp]
     lib.tango_op_sched_masked.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, C.c_uint64, ci, ci, ci, ci, ci, cf, ci, ci, vp]
+    lib.tango_op_sched_guided.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, C.c_uint64, ci, ci, ci, ci, ci, cf, ci, ci, vp, cf, vp, vp]
     lib.tango_op_latent_encode.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, cf, cf, cf, cf, cf, ci, C.c_uint64, ci, vp]
     lib.tango_op_philox_normal_encode.argtypes = [vp, ci, ci, ci, ci, C.c_uint64, ci, vp]
     lib.tango_op_conv2d_ex.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, vp]
@@ -225,6 +238,6 @@ def check(rc, what="tango engine call"):
     if rc != 0:
         msg = load().tango_last_error()
         msg = msg.decode() if msg else "unknown error"
-        if "cannot be larger" in msg or "unknown prediction" in msg:
+        if "cannot be larger" in msg or "unknown prediction" in msg or "guidance" in msg:
             raise ValueError(msg)
         raise RuntimeError("%s failed: %s" % (what, msg))

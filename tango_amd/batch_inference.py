@@ -48,14 +48,20 @@ def write_wav(path: str, samples: np.ndarray, sample_rate: int = SAMPLE_RATE) ->
 
 def generate_and_save(generator, prompts: Sequence[str], num_steps: int = 200, guidance: float = 3, batch_size: int = 8,
                       num_samples: int = 1, out_root: str = "outputs", tag: str = "", exp_id: Optional[str] = None,
-                      duration: float = 10) -> dict:
+                      duration: float = 10, negative_prompt=None, guidance_rescale: float = 0.0) -> dict:
     """Returns the summary record (also appended to <out_root>/summary.jsonl).  `duration`: seconds of audio per prompt (2.5 .. 20
-    on the 2.5 s grid); any other value than the default 10 is handed to the generator's `generate_for_batch(..., duration=)`."""
+    on the 2.5 s grid); any other value than the default 10 is handed to the generator's `generate_for_batch(..., duration=)`.  `negative_prompt`
+    (a str, or one per prompt) and `guidance_rescale` reach the generator as keywords only when they are set, so a generator without
+    them keeps working."""
     if num_samples < 1 or batch_size < 1:
         raise ValueError("num_samples and batch_size must be >= 1")
     from .inpaint import duration_geometry
     duration_geometry(duration)
     length = {} if duration == 10 else {"duration": duration}
+    if negative_prompt:
+        length["negative_prompt"] = negative_prompt
+    if guidance_rescale:
+        length["guidance_rescale"] = guidance_rescale
     exp_id = exp_id or str(int(time.time()))
     name = "{}_{}steps_{}_guidance_{}".format(exp_id, (tag + "_") if tag else "", num_steps, guidance)
     out_dir = os.path.join(out_root, name)
@@ -117,6 +123,9 @@ def parse_args(argv: Optional[Iterable[str]] = None):
     ap.add_argument("--batch_size", type=int, default=8)
     ap.add_argument("--num_samples", type=int, default=1)
     ap.add_argument("--duration", type=float, default=10, help="seconds of audio per prompt: 2.5 .. 20 in steps of 2.5")
+    ap.add_argument("--negative_prompt", type=str, default="", help="text every prompt is steered away from (the unconditional half of "
+                                                                    "the guidance batch); empty: the reference's empty text")
+    ap.add_argument("--guidance_rescale", type=float, default=0.0, help="guidance rescale phi in [0, 1] (Lin et al. 2023); 0: off")
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--dtype", type=str, default="fp16", choices=["fp32", "fp16", "bf16"])
     ap.add_argument("--out_root", type=str, default="outputs")
@@ -137,7 +146,8 @@ def main(argv: Optional[Iterable[str]] = None) -> dict:
     tango.scheduler = make_scheduler(args.scheduler, tango.scheduler.config, args.solver_order)
     prompts = read_prompts(args.test_file, args.text_key, args.prefix)
     rec = generate_and_save(tango, prompts, args.num_steps, args.guidance, args.batch_size, args.num_samples, args.out_root,
-                            tag="_".join(p for p in args.model.strip("/").split("/")[-2:] if p), duration=args.duration)
+                            tag="_".join(p for p in args.model.strip("/").split("/")[-2:] if p), duration=args.duration,
+                            negative_prompt=args.negative_prompt or None, guidance_rescale=args.guidance_rescale)
     print(json.dumps(rec))
     return rec
 

@@ -452,11 +452,27 @@ struct SchedParams {
   const float* blend_coef;  // [steps][2] device: sqrt(abar_t), sqrt(1 - abar_t)
   const float* blend_noise; // [steps][B*C*HW] or null -> philox, step word | 0x80000000
   int num_steps;
+  // guided kernels only (include/tango_engine.h tango_guidance_args_t): the guidance scale of sample b at loop index i is
+  // gtable[i * B + b] (`guidance` above is not read), and with rescale = phi > 0 the guided output is pulled towards the conditional
+  // output's per-sample standard deviation: v = phi * (cfg * gscale[b]) + (1 - phi) * cfg, gscale[b] = std(cond) / std(cfg) of this step
+  const float* gtable;      // [steps][B] device
+  float rescale;            // phi in [0, 1]; 0: no statistics are taken and gscale is not read
+  double* gpart;            // [B][ceil(HW / kGuideChunk)][4] partial sums of guidance_stats_kernel (written and read every step)
+  float* gscale;            // [B] written by guidance_scale_kernel
 };
 // `dev_params` is a DEVICE copy of SchedParams; the grid covers max_positions >= B*HW (one thread per latent position).
 // `rule` (host copy of the block's rule) picks the kernel: 0 / 1 sched_step_kernel, 2 sched_multistep_kernel; `masked` their
-// inpainting variants (the blend for the next loop index fused after the update)
-int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule = 0, bool masked = false);
+// inpainting variants (the blend for the next loop index fused after the update); `guided` the variants that read the guidance
+// table and apply the rescale (they need cfg = 1 and launch_guidance_stats in front of them)
+int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule = 0, bool masked = false,
+                      bool guided = false);
+// positions of one sample per workgroup of the statistics pass: the partition of a sample depends on HW alone
+constexpr int kGuideChunk = 256;
+inline int guidance_chunks(int HW) { return (HW + kGuideChunk - 1) / kGuideChunk; }
+// the two launches in front of a guided update: per-chunk partial sums of the step's cond and cfg outputs into gpart, then their
+// fixed-order combination into gscale.  B and HW are the block's (host copies: the grid is fixed at capture).  Both kernels return at
+// once when the block's rescale is 0.
+int launch_guidance_stats(const SchedParams* dev_params, int B, int HW, hipStream_t s);
 // the blend of loop index 0 (before the first UNet call): lat and both CFG halves of xin, from the block's step-0 entries
 int launch_inpaint_blend0(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s);
 int launch_step_inc(int* step_ptr, hipStream_t s);

@@ -68,11 +68,94 @@ __device__ __forceinline__ float blend_at(const SchedParams& p, int step, int b,
   return inpaint_blend(x, p.x0[o], n, p.blend_coef[2 * step], p.blend_coef[2 * step + 1], m);
 }
 
+// ------------------------------------------------------------------------------------------
+// Guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4; diffusers'
+// guidance_rescale): per sample b, over the n = C * HW values of this step's model output,
+//   cfg = u + g * (c - u)        s_b = std(c) / std(cfg)   (unbiased, n - 1)        v = phi * (cfg * s_b) + (1 - phi) * cfg
+// and the scheduler rule runs on v.  std(cfg) == 0 gives s_b = 1 (the formula would give NaN): the one deviation.
+// Two launches in front of the guided update kernels:
+//   guidance_stats_kernel  grid (ceil(HW / 256), B), one position (C channels of both halves) per thread: sum and sum of squares of
+//     c - c[first] and cfg - cfg[first] (about the sample's first element, like the norm kernels), cfg evaluated with the update
+//     kernel's own fp32 operations, accumulated in fp64; registers -> 64 lanes by shuffles -> 4 waves through LDS -> one partial.
+//   guidance_scale_kernel  one thread per sample adds the partials in chunk order in fp64 and writes s_b as fp32.
+// No atomics and a partition that depends on HW alone: s_b has the same bits whatever B, the sample's row or sample_offset.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float cfg_combine(float u, float c, float g) {
+#pragma clang fp contract(off)
+  const float dlt = c - u; const float gd = g * dlt;
+  return u + gd;
+}
+
+__global__ __launch_bounds__(kGuideChunk) void guidance_stats_kernel(const SchedParams* __restrict__ pp) {
+  const SchedParams p = *pp;
+  if (!(p.rescale > 0.f)) return;
+  __shared__ double red[kGuideChunk / 64][4];
+  const int b = blockIdx.y, hw = blockIdx.x * kGuideChunk + threadIdx.x;
+  const int C = p.C;
+  const float g = p.gtable[*p.step_ptr * p.B + b];
+  const float* u0 = p.eps + (int64_t)b * p.HW * C;
+  const float* c0 = p.eps + (int64_t)(p.B + b) * p.HW * C;
+  const double pc = (double)c0[0], pg = (double)cfg_combine(u0[0], c0[0], g);
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  if (hw < p.HW) {
+    const float* eu = u0 + (int64_t)hw * C;
+    const float* ec = c0 + (int64_t)hw * C;
+    for (int c = 0; c < C; ++c) {
+      const double dc = (double)ec[c] - pc, dg = (double)cfg_combine(eu[c], ec[c], g) - pg;
+      a[0] += dc; a[1] += dc * dc; a[2] += dg; a[3] += dg * dg;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
+  if ((threadIdx.x & 63) == 0)
+    for (int k = 0; k < 4; ++k) red[threadIdx.x >> 6][k] = a[k];
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    double t = red[0][threadIdx.x];
+    for (int w = 1; w < kGuideChunk / 64; ++w) t += red[w][threadIdx.x];
+    p.gpart[((int64_t)b * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(64) void guidance_scale_kernel(const SchedParams* __restrict__ pp, int chunks) {
+  const SchedParams p = *pp;
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (!(p.rescale > 0.f) || b >= p.B) return;
+  double t[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int j = 0; j < chunks; ++j)
+    for (int k = 0; k < 4; ++k) t[k] += p.gpart[((int64_t)b * chunks + j) * 4 + k];
+  const double n = (double)p.C * (double)p.HW;
+  const double vc = (t[1] - t[0] * t[0] / n) / (n - 1.0), vg = (t[3] - t[2] * t[2] / n) / (n - 1.0);
+  p.gscale[b] = vg > 0.0 ? (float)(sqrt(vc > 0.0 ? vc : 0.0) / sqrt(vg)) : 1.0f;
+}
+
+int launch_guidance_stats(const SchedParams* dev_params, int B, int HW, hipStream_t s) {
+  const int chunks = guidance_chunks(HW);
+  hipLaunchKernelGGL(guidance_stats_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(kGuideChunk), 0, s, dev_params);
+  TANGO_HIP(hipGetLastError());
+  hipLaunchKernelGGL(guidance_scale_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, dev_params, chunks);
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+// the model output the guided kernels run the scheduler rule on: CFG (models.py:246) with the table's scale g, then the rescale above
+// with s = gscale[b]; phi == 0 leaves cfg as it is.  1 - phi is an fp32 subtraction.
+__device__ __forceinline__ float guided_output(float u, float c, float g, float s, float phi) {
+#pragma clang fp contract(off)
+  const float cfg = cfg_combine(u, c, g);
+  if (!(phi > 0.f)) return cfg;
+  const float r = cfg * s;
+  const float t0 = phi * r; const float om = 1.0f - phi; const float t1 = om * cfg;
+  return t0 + t1;
+}
+
 // The parameter block is read from DEVICE memory (wave-uniform scalar loads): the launch itself then carries only one
 // pointer, so the captured hipGraph of a denoise step stays valid when the caller's latents / noise pointers, guidance
 // or prediction type change between calls (engine.hip refreshes the block with one hipMemcpyAsync per call).
 // MASK: the inpainting variant -- after the update, the blend of loop index step + 1 (none after the last step)
-template <typename T, bool MASK = false>
+// GUIDED: the guidance scale comes from the block's table and the rescale is applied (the block has cfg = 1)
+template <typename T, bool MASK = false, bool GUIDED = false>
 __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __restrict__ pp) {
   // plain operators + contract(off): the HIP _rn intrinsics are inlined header operators that still fuse
 #pragma clang fp contract(off)
@@ -92,11 +175,14 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __re
   float nb[4] = {0.f, 0.f, 0.f, 0.f};
   const bool blend = MASK && step + 1 < p.num_steps;
   const float m = MASK ? p.mask[(int64_t)b * p.HW + hw] : 0.f;
+  const float gg = GUIDED ? p.gtable[step * p.B + b] : 0.f;
+  const float gs = GUIDED && p.rescale > 0.f ? p.gscale[b] : 1.f;
   for (int c = 0; c < C; ++c) {
     float* lp = p.lat + ((int64_t)b * C + c) * p.HW + hw;
     const float x = *lp;
     float v = eu[c];
-    if (p.cfg) { const float dlt = ec[c] - v; const float gd = p.guidance * dlt; v = v + gd; }   // models.py:246
+    if constexpr (GUIDED) v = guided_output(v, ec[c], gg, gs, p.rescale);
+    else if (p.cfg) { const float dlt = ec[c] - v; const float gd = p.guidance * dlt; v = v + gd; }   // models.py:246
     float x0;
     if (p.pred_type == 0) { const float m0 = sb * v; const float d0 = x - m0; x0 = d0 / sa; }   // epsilon
     else if (p.pred_type == 1) x0 = v;                                               // sample
@@ -286,8 +372,8 @@ int launch_philox_normal_encode(float* out, int B, int C, int HW, int which, uns
 // The converted output m0 of this step goes to ring slot step % 3; m1 / m2 (steps - 1, - 2) are read from the other two slots
 // only when the row's order asks for them, i.e. only once an earlier step of the same loop has written them.  No noise term.
 // ------------------------------------------------------------------------------------------
-// MASK: the inpainting variant, as sched_step_kernel's (the blended sample is the next step's `sample`)
-template <typename T, bool MASK = false>
+// MASK: the inpainting variant, as sched_step_kernel's (the blended sample is the next step's `sample`); GUIDED: as sched_step_kernel's
+template <typename T, bool MASK = false, bool GUIDED = false>
 __global__ __launch_bounds__(256) void sched_multistep_kernel(const SchedParams* __restrict__ pp) {
 #pragma clang fp contract(off)
   const SchedParams p = *pp;
@@ -311,11 +397,14 @@ __global__ __launch_bounds__(256) void sched_multistep_kernel(const SchedParams*
   float nb[4] = {0.f, 0.f, 0.f, 0.f};
   const bool blend = MASK && step + 1 < p.num_steps;
   const float m = MASK ? p.mask[(int64_t)b * p.HW + hw] : 0.f;
+  const float gg = GUIDED ? p.gtable[step * p.B + b] : 0.f;
+  const float gs = GUIDED && p.rescale > 0.f ? p.gscale[b] : 1.f;
   for (int c = 0; c < C; ++c) {
     const int64_t o = ((int64_t)b * C + c) * p.HW + hw;
     const float x = p.lat[o];
     float v = eu[c];
-    if (p.cfg) { const float dlt = ec[c] - v; const float gd = p.guidance * dlt; v = v + gd; }   // models.py:246
+    if constexpr (GUIDED) v = guided_output(v, ec[c], gg, gs, p.rescale);
+    else if (p.cfg) { const float dlt = ec[c] - v; const float gd = p.guidance * dlt; v = v + gd; }   // models.py:246
     float m0;                                                                                  // convert_model_output
     if (p.algo == 0) {                                                                         // x0
       if (p.pred_type == 0) { const float t0 = s_s0 * v; const float d0 = x - t0; m0 = d0 / a_s0; }
@@ -387,45 +476,33 @@ int launch_inpaint_blend0(int dtype, const SchedParams* dev_params, int max_posi
   return 0;
 }
 
-int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule, bool masked) {
-  const unsigned nb = (unsigned)((max_positions + 255) / 256);   // >= B*HW of the block; surplus threads exit
-  if (masked) {
-    if (rule == 2) {
-      switch (dtype) {
-        case DT_F32: hipLaunchKernelGGL((sched_multistep_kernel<float, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
-        case DT_F16: hipLaunchKernelGGL((sched_multistep_kernel<f16, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
-        case DT_BF16: hipLaunchKernelGGL((sched_multistep_kernel<bf16, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
-        default: TANGO_FAIL("sched_multistep (masked): bad dtype");
-      }
-    } else {
-      switch (dtype) {
-        case DT_F32: hipLaunchKernelGGL((sched_step_kernel<float, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
-        case DT_F16: hipLaunchKernelGGL((sched_step_kernel<f16, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
-        case DT_BF16: hipLaunchKernelGGL((sched_step_kernel<bf16, true>), dim3(nb), dim3(256), 0, s, dev_params); break;
-        default: TANGO_FAIL("sched_step (masked): bad dtype");
-      }
-    }
-    TANGO_HIP(hipGetLastError());
-    return 0;
-  }
+template <bool MASK, bool GUIDED>
+static int launch_sched_variant(int dtype, const SchedParams* dev_params, unsigned nb, hipStream_t s, int rule) {
   if (rule == 2) {
     switch (dtype) {
-      case DT_F32: hipLaunchKernelGGL((sched_multistep_kernel<float>), dim3(nb), dim3(256), 0, s, dev_params); break;
-      case DT_F16: hipLaunchKernelGGL((sched_multistep_kernel<f16>), dim3(nb), dim3(256), 0, s, dev_params); break;
-      case DT_BF16: hipLaunchKernelGGL((sched_multistep_kernel<bf16>), dim3(nb), dim3(256), 0, s, dev_params); break;
+      case DT_F32: hipLaunchKernelGGL((sched_multistep_kernel<float, MASK, GUIDED>), dim3(nb), dim3(256), 0, s, dev_params); break;
+      case DT_F16: hipLaunchKernelGGL((sched_multistep_kernel<f16, MASK, GUIDED>), dim3(nb), dim3(256), 0, s, dev_params); break;
+      case DT_BF16: hipLaunchKernelGGL((sched_multistep_kernel<bf16, MASK, GUIDED>), dim3(nb), dim3(256), 0, s, dev_params); break;
       default: TANGO_FAIL("sched_multistep: bad dtype");
     }
-    TANGO_HIP(hipGetLastError());
-    return 0;
-  }
-  switch (dtype) {
-    case DT_F32: hipLaunchKernelGGL((sched_step_kernel<float>), dim3(nb), dim3(256), 0, s, dev_params); break;
-    case DT_F16: hipLaunchKernelGGL((sched_step_kernel<f16>), dim3(nb), dim3(256), 0, s, dev_params); break;
-    case DT_BF16: hipLaunchKernelGGL((sched_step_kernel<bf16>), dim3(nb), dim3(256), 0, s, dev_params); break;
-    default: TANGO_FAIL("sched_step: bad dtype");
+  } else {
+    switch (dtype) {
+      case DT_F32: hipLaunchKernelGGL((sched_step_kernel<float, MASK, GUIDED>), dim3(nb), dim3(256), 0, s, dev_params); break;
+      case DT_F16: hipLaunchKernelGGL((sched_step_kernel<f16, MASK, GUIDED>), dim3(nb), dim3(256), 0, s, dev_params); break;
+      case DT_BF16: hipLaunchKernelGGL((sched_step_kernel<bf16, MASK, GUIDED>), dim3(nb), dim3(256), 0, s, dev_params); break;
+      default: TANGO_FAIL("sched_step: bad dtype");
+    }
   }
   TANGO_HIP(hipGetLastError());
   return 0;
+}
+
+int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule, bool masked, bool guided) {
+  const unsigned nb = (unsigned)((max_positions + 255) / 256);   // >= B*HW of the block; surplus threads exit
+  if (guided) return masked ? launch_sched_variant<true, true>(dtype, dev_params, nb, s, rule)
+                            : launch_sched_variant<false, true>(dtype, dev_params, nb, s, rule);
+  return masked ? launch_sched_variant<true, false>(dtype, dev_params, nb, s, rule)
+                : launch_sched_variant<false, false>(dtype, dev_params, nb, s, rule);
 }
 
 __global__ void step_inc_kernel(int* sp) { if (threadIdx.x == 0 && blockIdx.x == 0) *sp = *sp + 1; }

@@ -164,10 +164,11 @@ struct UNetPlan : Plan {
   // T5("") = one valid token), so their text cross-attention output is the constant to_out(v_key) + b, independent of the query
   int n_short = 0;
   int* key0 = nullptr;      // i32 [B2]: index of that key per sample (entries >= n_short unused)
-  // [masked][multistep]: the update kernel is chosen at launch (launch_sched_step: DDPM and DDIM share one, the multistep rule has
+  // [masked][multistep][guided]: the update kernel is chosen at launch (launch_sched_step: DDPM and DDIM share one, the multistep rule has
   // its own, and the masked (inpainting) variants fuse the blend of the next loop index into either), so a graph captured with one
-  // cannot replay a loop that needs another; everything else is shared
-  StepGraphs graphs[2][2];
+  // cannot replay a loop that needs another; everything else is shared.  [guided]: the table / rescale variants, with the two
+  // statistics launches in front of the update (a default call replays the [.][.][0] graphs: today's kernel sequence)
+  StepGraphs graphs[2][2][2];
   // Two independent chains (round 5; Engine::denoise): a "dual" plan owns only the UNet input / output buffers of the whole batch; its
   // two children run the first and the second half of the samples (no op of the UNet crosses samples) as two branches of the captured
   // graph, so that one branch's dispatch gaps and kernel tails are filled by the other's kernels.  A child takes xin / eps from its
@@ -216,7 +217,7 @@ class Engine {
 
   int set_weight(const char* name, const float* dev, const int64_t* shape, int ndim);
   int finalize_weights();
-  int denoise(const tango_denoise_args_t& a, hipStream_t s);
+  int denoise(const tango_denoise_args_t& a, const tango_guidance_args_t* g, hipStream_t s);   // g may be null: scalar guidance, no rescale
   struct Cond { const float* emb = nullptr; const uint8_t* mask = nullptr; int len = 0; const uint8_t* mask_host = nullptr; };
   // latent_h: the latent height of the call, 0 = cfg.latent_h (the width is always cfg.latent_w)
   int unet_forward(const float* sample, int64_t t, const Cond (&c)[3], float* out, int B2, int latent_h, hipStream_t s);
@@ -330,6 +331,10 @@ class Engine {
   float* d_bcoef = nullptr;      // [max_steps][2] add_noise scalars of the masked loop's blend (tango_denoise_args_t.blend_coef)
   float* d_ring = nullptr;       // multistep history [3][B][C][HW] fp32 of the call (hipMalloc'd, grown on demand; not in `owned`)
   size_t ring_elems = 0;         // its capacity in floats
+  // guided calls (tango_guidance_args_t): one allocation, grown like d_ring, that holds the call's guidance table [N][B] fp32, the
+  // statistics partials [B][chunks][4] fp64 and the rescale factors [B] fp32 (SchedParams gtable / gpart / gscale point into it)
+  char* d_guide = nullptr;
+  size_t guide_bytes = 0;
   float* d_sin = nullptr;        // [max_steps][ch0]
   float* d_t1 = nullptr;         // [max_steps][temb]
   float* d_temb = nullptr;       // [max_steps][temb]  silu(emb)
@@ -395,8 +400,8 @@ class Engine {
   bool cfg_shared_ok(int B2, int n_short) const;
   // how a guidance / plain batch of B2 UNet rows runs; profile_unet() asks with two_chains_ok = false
   UNetMode unet_mode_for(int B2, int n_short, bool cfg_on, bool two_chains_ok) const;
-  int run_step(const UNetPlan& P, int rule, bool masked, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
-  int capture_steps(const UNetPlan& P, int rule, bool masked, int n, hipGraph_t* g_out, hipGraphExec_t* x_out);
+  int run_step(const UNetPlan& P, int rule, bool masked, bool guided, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
+  int capture_steps(const UNetPlan& P, int rule, bool masked, bool guided, int n, hipGraph_t* g_out, hipGraphExec_t* x_out);
   int single_key_prefix(const uint8_t* mask_dev, const uint8_t* mask_host, int B2, int L, std::vector<int>& key0, hipStream_t s);
   int build_unet(UNetPlan& P, Arena& A, bool record);
   int get_vae_plan(int B, int H, VaePlan** out);

@@ -486,6 +486,7 @@ Engine::~Engine() {
   for (auto& kv : plans) free_plan(*kv.second);
   for (void* p : owned) (void)hipFree(p);
   if (d_ring) (void)hipFree(d_ring);
+  if (d_guide) (void)hipFree(d_guide);
   for (auto& hs : hslots) {
     if (hs.ev) (void)hipEventDestroy(hs.ev);
     if (hs.buf) (void)hipHostFree(hs.buf);
@@ -549,14 +550,15 @@ void Engine::free_plan(Plan& P) {
     //  a replay of this plan may still be in flight -- denoise() no longer waits for its stream, and destroying an
     // executing graph is not safe on HIP: drain the device first (hipFree would do so anyway, but only AFTER the destroy)
     (void)hipDeviceSynchronize();
-    for (auto& row : U.graphs)
-      for (StepGraphs& g : row) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-        if (g.exec_k) (void)hipGraphExecDestroy(g.exec_k);
-        if (g.graph_k) (void)hipGraphDestroy(g.graph_k);
-        g = StepGraphs();
-      }
+    for (auto& plane : U.graphs)
+      for (auto& row : plane)
+        for (StepGraphs& g : row) {
+          if (g.exec) (void)hipGraphExecDestroy(g.exec);
+          if (g.graph) (void)hipGraphDestroy(g.graph);
+          if (g.exec_k) (void)hipGraphExecDestroy(g.exec_k);
+          if (g.graph_k) (void)hipGraphDestroy(g.graph_k);
+          g = StepGraphs();
+        }
     for (auto& c : U.child) if (c) { free_plan(*c); c.reset(); }
   }
   // a slab may still be read by work queued on a stream: hipFree synchronises the device before it releases memory
@@ -1491,9 +1493,23 @@ static int check_denoise_args(const tango_denoise_args_t& a) {
   return 0;
 }
 
+// the checks of a guided call (tango_guidance_args_t) on top of check_denoise_args(): callers read these messages too
+static int check_guidance_args(const tango_denoise_args_t& a, const tango_guidance_args_t& g) {
+  if (!(g.rescale >= 0.0f && g.rescale <= 1.0f)) TANGO_FAIL("denoise: guidance rescale must be in [0, 1]");
+  if (g.rescale > 0.0f && !g.table && !(a.guidance_scale > 1.0f))
+    TANGO_FAIL("denoise: guidance rescale needs classifier-free guidance (guidance_scale > 1 or a guidance table)");
+  if (g.table) {
+    if (a.batch <= 0) TANGO_FAIL("denoise: a guidance table needs batch > 0");
+    const size_t n = (size_t)a.num_steps * (size_t)a.batch;
+    for (size_t i = 0; i < n; ++i)
+      if (!(g.table[i] >= 0.0f) || std::isinf(g.table[i])) TANGO_FAIL("denoise: guidance table entries must be finite and >= 0");
+  }
+  return 0;
+}
+
 // one denoise step = UNet forward, fused CFG combine + scheduler update (writes the next UNet input), step counter++
-// (two chains: fork after the previous step's update, join before this step's)
-int Engine::run_step(const UNetPlan& P, int rule, bool masked, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join) {
+// (two chains: fork after the previous step's update, join before this step's); guided: the statistics of the rescale in between
+int Engine::run_step(const UNetPlan& P, int rule, bool masked, bool guided, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join) {
   if (P.mode != UNetMode::TwoChains) {
     TANGO_TRY(P.step.run(st));
   } else {
@@ -1504,18 +1520,19 @@ int Engine::run_step(const UNetPlan& P, int rule, bool masked, hipStream_t st, h
     TANGO_HIP(hipEventRecord(join, st2));
     TANGO_HIP(hipStreamWaitEvent(st, join, 0));
   }
-  TANGO_TRY(launch_sched_step(dt, d_sched, P.B2 * P.H * cfg.latent_w, st, rule, masked));
+  if (guided) TANGO_TRY(launch_guidance_stats(d_sched, P.B2 / 2, P.H * cfg.latent_w, st));
+  TANGO_TRY(launch_sched_step(dt, d_sched, P.B2 * P.H * cfg.latent_w, st, rule, masked, guided));
   return launch_step_inc(d_step, st);
 }
 
 // capture `n` steps; every per-step quantity is read through d_step / d_sched
 // (captured on an engine-owned stream: the caller's stream may be the legacy null stream,
 // which cannot be captured; the instantiated graph is then launched on the caller's stream)
-int Engine::capture_steps(const UNetPlan& P, int rule, bool masked, int n, hipGraph_t* g_out, hipGraphExec_t* x_out) {
+int Engine::capture_steps(const UNetPlan& P, int rule, bool masked, bool guided, int n, hipGraph_t* g_out, hipGraphExec_t* x_out) {
   if (!cap_stream) TANGO_HIP(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
   TANGO_HIP(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeRelaxed));
   int rc = 0;
-  for (int i = 0; i < n && rc == 0; ++i) rc = run_step(P, rule, masked, cap_stream, cap_stream2, ev_fork, ev_join);
+  for (int i = 0; i < n && rc == 0; ++i) rc = run_step(P, rule, masked, guided, cap_stream, cap_stream2, ev_fork, ev_join);
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(cap_stream, &g);
   if (rc != 0) return rc;
@@ -1525,12 +1542,15 @@ int Engine::capture_steps(const UNetPlan& P, int rule, bool masked, int n, hipGr
   return 0;
 }
 
-int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
+int Engine::denoise(const tango_denoise_args_t& a, const tango_guidance_args_t* g, hipStream_t s) {
   TANGO_TRY(check_denoise_args(a));
+  if (g) TANGO_TRY(check_guidance_args(a, *g));
+  // a table, or a rescale, takes the guided update kernels; a null / all-default block is today's call
+  const bool gd = g && (g->table || g->rescale > 0.0f);
   const bool ms = a.rule == TANGO_RULE_DPM_MULTISTEP;
   const int coef_w = ms ? 16 : 8;
   const bool mk = a.known_latents != nullptr;       // masked-latent inpainting
-  const bool cfg_on = a.guidance_scale > 1.0f;
+  const bool cfg_on = a.guidance_scale > 1.0f || (g && g->table);   // a table always runs the [uncond; cond] batch
   const int B = a.batch, B2 = cfg_on ? 2 * B : B;
   UNetPlan* P;
   std::vector<int> key0;
@@ -1549,6 +1569,13 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
     if (hipMalloc(&d_ring, ring_need * 4) != hipSuccess) { d_ring = nullptr; TANGO_FAIL("denoise: hipMalloc of the multistep ring failed"); }
     ring_elems = ring_need;
   }
+  const size_t gt_bytes = ((size_t)a.num_steps * B * 4 + 255) & ~(size_t)255, gs_bytes = ((size_t)B * 4 + 255) & ~(size_t)255;
+  const size_t guide_need = gt_bytes + gs_bytes + (size_t)B * guidance_chunks(HW) * 4 * 8;
+  if (gd && guide_need > guide_bytes) {      // like the ring: outside any capture, after every earlier use of the old buffer
+    if (d_guide) { TANGO_HIP(hipDeviceSynchronize()); (void)hipFree(d_guide); d_guide = nullptr; guide_bytes = 0; }
+    if (hipMalloc((void**)&d_guide, guide_need) != hipSuccess) { d_guide = nullptr; TANGO_FAIL("denoise: hipMalloc of the guidance workspace failed"); }
+    guide_bytes = guide_need;
+  }
   SchedParams sp;
   sp.lat = a.latents; sp.eps = P->eps; sp.xin = P->xin; sp.xin_ld = 8;
   sp.noise = a.noise; sp.coef = d_coef; sp.step_ptr = d_step;
@@ -1558,6 +1585,14 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
   sp.ring = ms ? d_ring : nullptr; sp.coef_w = coef_w; sp.algo = ms ? (int)a.coef[11] : 0;
   sp.x0 = a.known_latents; sp.mask = a.latent_mask; sp.blend_coef = mk ? d_bcoef : nullptr; sp.blend_noise = mk ? a.blend_noise : nullptr;
   sp.num_steps = a.num_steps;
+  sp.gtable = gd ? (const float*)d_guide : nullptr; sp.rescale = gd ? g->rescale : 0.0f;
+  sp.gscale = gd ? (float*)(d_guide + gt_bytes) : nullptr; sp.gpart = gd ? (double*)(d_guide + gt_bytes + gs_bytes) : nullptr;
+  if (gd) {
+    // a rescale without a table: the scalar in every entry (the guided kernels read the table only)
+    std::vector<float> flat;
+    if (!g->table) flat.assign((size_t)a.num_steps * B, a.guidance_scale);
+    TANGO_TRY(stage_h2d(d_guide, g->table ? g->table : flat.data(), (size_t)a.num_steps * B * 4, s));
+  }
   // per-call tables and the scheduler parameter block live in device memory, so the captured graph of one denoise
   // step (UNet + CFG/scheduler update + step counter) is independent of the call's pointers and scalars
   // (both sources are pageable / transient host memory: pinned staging slots, no host sync -- stage_h2d)
@@ -1583,9 +1618,9 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
     TANGO_HIP(hipStreamCreateWithFlags(&aux_stream, hipStreamNonBlocking));
     for (hipEvent_t* e : {&ev_fork, &ev_join, &ev_fork_e, &ev_join_e}) TANGO_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
-  // the update kernel is fixed at capture: each (masked, multistep) pair replays graphs of its own, captured once per plan
-  StepGraphs& G = P->graphs[mk][ms];
-  if (a.use_graph && !G.exec) TANGO_TRY(capture_steps(*P, a.rule, mk, 1, &G.graph, &G.exec));
+  // the update kernel is fixed at capture: each (masked, multistep, guided) triple replays graphs of its own, captured once per plan
+  StepGraphs& G = P->graphs[mk][ms][gd];
+  if (a.use_graph && !G.exec) TANGO_TRY(capture_steps(*P, a.rule, mk, gd, 1, &G.graph, &G.exec));
   // k steps per replay (round 5; north_star: "the 100-200 denoise steps captured as a hipGraph"): the same kernel sequence captured k
   // times back to back -- every per-step quantity is read through the device-side step counter, so a k-step graph is just k copies.
   // What it removes is the host-side launch of every replay and the gap between two replays, which only shows at small batches
@@ -1594,7 +1629,7 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
   if (kk > a.num_steps) kk = a.num_steps;
   if (a.use_graph && kk > 1 && (!G.exec_k || G.k_steps != kk)) {
     if (G.exec_k) { TANGO_HIP(hipStreamSynchronize(s)); (void)hipGraphExecDestroy(G.exec_k); (void)hipGraphDestroy(G.graph_k); G.exec_k = nullptr; G.graph_k = nullptr; }
-    TANGO_TRY(capture_steps(*P, a.rule, mk, kk, &G.graph_k, &G.exec_k));
+    TANGO_TRY(capture_steps(*P, a.rule, mk, gd, kk, &G.graph_k, &G.exec_k));
     G.k_steps = kk;
   }
   TANGO_HIP(hipEventRecord(ev0, s));
@@ -1604,7 +1639,7 @@ int Engine::denoise(const tango_denoise_args_t& a, hipStream_t s) {
       for (; i + kk <= a.num_steps; i += kk) TANGO_HIP(hipGraphLaunch(G.exec_k, s));
     for (; i < a.num_steps; ++i) {
       if (a.use_graph) TANGO_HIP(hipGraphLaunch(G.exec, s));
-      else TANGO_TRY(run_step(*P, a.rule, mk, s, aux_stream, ev_fork_e, ev_join_e));
+      else TANGO_TRY(run_step(*P, a.rule, mk, gd, s, aux_stream, ev_fork_e, ev_join_e));
     }
   }
   TANGO_HIP(hipEventRecord(ev1, s));
@@ -2159,8 +2194,18 @@ int tango_engine_set_weight(tango_engine_t* h, const char* name, const float* de
 int tango_engine_finalize_weights(tango_engine_t* h) { return h->e->finalize_weights(); }
 
 int tango_engine_denoise(tango_engine_t* h, const tango_denoise_args_t* a, void* stream) {
+  return tango_engine_denoise_guided(h, a, nullptr, stream);
+}
+int tango_engine_denoise_guided(tango_engine_t* h, const tango_denoise_args_t* a, const tango_guidance_args_t* g, void* stream) {
   if (!a) { tango::set_error("denoise: null args"); return -1; }
-  return h->e->denoise(*a, (hipStream_t)stream);
+  return h->e->denoise(*a, g, (hipStream_t)stream);
+}
+const char* tango_debug_denoise_guided_check(const tango_denoise_args_t* a, const tango_guidance_args_t* g) {
+  static thread_local std::string msg;
+  msg.clear();
+  if (!a) return "denoise: null args";
+  if (tango::check_denoise_args(*a) != 0 || (g && tango::check_guidance_args(*a, *g) != 0)) msg = tango_last_error();
+  return msg.c_str();
 }
 int tango_engine_unet_forward_h(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
                                 const uint8_t* prompt_mask, float* out, int batch2, int text_len, int latent_h, void* stream) {

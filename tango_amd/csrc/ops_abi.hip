@@ -836,6 +836,7 @@ int tango_op_sched_step(float* latents, const float* model_out_nchw, const float
   p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = rule; p.clip = clip;
   p.clip_range = clip_range; p.seed = 0; p.sample_offset = 0; p.ring = nullptr; p.coef_w = 8; p.algo = 0;
   p.x0 = nullptr; p.mask = nullptr; p.blend_coef = nullptr; p.blend_noise = nullptr; p.num_steps = 1;
+  p.gtable = nullptr; p.rescale = 0.0f; p.gpart = nullptr; p.gscale = nullptr;
   SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
   if (!dp) TANGO_FAIL("op_sched_step: alloc");
   TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
@@ -866,6 +867,7 @@ int tango_op_sched_multistep(float* latents, const float* model_out_nchw, float*
   p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = TANGO_RULE_DPM_MULTISTEP;
   p.clip = 0; p.clip_range = 1.0f; p.seed = 0; p.sample_offset = 0; p.ring = ring; p.coef_w = 16; p.algo = algo;
   p.x0 = nullptr; p.mask = nullptr; p.blend_coef = nullptr; p.blend_noise = nullptr; p.num_steps = step + 1;
+  p.gtable = nullptr; p.rescale = 0.0f; p.gpart = nullptr; p.gscale = nullptr;
   SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
   if (!dp) TANGO_FAIL("op_sched_multistep: alloc");
   TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
@@ -888,48 +890,89 @@ int tango_op_philox_normal_blend(float* out, int B, int C, int HW, int step, uin
   return 0;
 }
 
-int tango_op_sched_masked(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
-                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
-                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
-                          int pred_type, int rule, void* stream) {
-  if (B <= 0 || C <= 0 || HW <= 0 || num_steps <= 0 || step < 0 || step >= num_steps) TANGO_FAIL("op_sched_masked: bad sizes");
-  if (!known_latents || !latent_mask || !blend_coef) TANGO_FAIL("op_sched_masked: known_latents, latent_mask and blend_coef are required");
+// tango_op_sched_masked and tango_op_sched_guided: one step on caller-owned buffers.  guided: guidance_row / rescale / scale_out as the header says
+static int op_sched_any(const char* who, bool guided, float* latents, const float* model_out_nchw, const float* noise, float* ring,
+                        const float* coef, int coef_width, int step, int num_steps, const float* known_latents, const float* latent_mask,
+                        const float* blend_coef, const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg,
+                        float guidance, int pred_type, int rule, const float* guidance_row, float rescale, float* scale_out, void* stream) {
+  const std::string w(who);
+  if (B <= 0 || C <= 0 || HW <= 0 || num_steps <= 0 || step < 0 || step >= num_steps) TANGO_FAIL(w + ": bad sizes");
+  const bool mk = known_latents || latent_mask || blend_coef || blend_noise;
+  if (!guided || mk) {
+    if (!known_latents || !latent_mask || !blend_coef) TANGO_FAIL(w + ": known_latents, latent_mask and blend_coef are required");
+  }
+  if (guided) {
+    if (!cfg || !guidance_row) TANGO_FAIL(w + ": the guided kernels need cfg = 1 and a guidance row");
+    if (!(rescale >= 0.0f && rescale <= 1.0f)) TANGO_FAIL(w + ": rescale must be in [0, 1]");
+    for (int b = 0; b < B; ++b)
+      if (!(guidance_row[b] >= 0.0f) || std::isinf(guidance_row[b])) TANGO_FAIL(w + ": guidance entries must be finite and >= 0");
+  }
   const bool ms = rule == TANGO_RULE_DPM_MULTISTEP;
-  if (rule != TANGO_RULE_DDPM && rule != TANGO_RULE_DDIM && !ms) TANGO_FAIL("op_sched_masked: unknown rule");
-  if (coef_width != (ms ? 16 : 8)) TANGO_FAIL("op_sched_masked: coef_width must be 16 for the multistep rule, else 8");
+  if (rule != TANGO_RULE_DDPM && rule != TANGO_RULE_DDIM && !ms) TANGO_FAIL(w + ": unknown rule");
+  if (coef_width != (ms ? 16 : 8)) TANGO_FAIL(w + ": coef_width must be 16 for the multistep rule, else 8");
   int algo = 0;
   if (ms) {
-    if (noise || !ring) TANGO_FAIL("op_sched_masked: the multistep rule takes a ring and no step noise");
+    if (noise || !ring) TANGO_FAIL(w + ": the multistep rule takes a ring and no step noise");
     const int order = (int)coef[(size_t)step * 16 + 10];
-    if (order < 1 || order > 3 || order > step + 1) TANGO_FAIL("op_sched_masked: row order must be in [1, min(3, step + 1)]");
+    if (order < 1 || order > 3 || order > step + 1) TANGO_FAIL(w + ": row order must be in [1, min(3, step + 1)]");
     algo = (int)coef[11];
-    if (algo != 0 && algo != 1) TANGO_FAIL("op_sched_masked: table column 11 (algorithm) must be 0 or 1");
+    if (algo != 0 && algo != 1) TANGO_FAIL(w + ": table column 11 (algorithm) must be 0 or 1");
   }
   hipStream_t s = (hipStream_t)stream;
   Scratch sc;
   const int B2 = cfg ? 2 * B : B;
+  const int chunks = guidance_chunks(HW);
   float* eps = (float*)sc.get((size_t)B2 * HW * C * 4);
   float* xin = (float*)sc.get((size_t)B2 * HW * C * 4);
   float* dcoef = (float*)sc.get((size_t)num_steps * coef_width * 4);
   float* dbc = (float*)sc.get((size_t)num_steps * 2 * 4);
   int* dstep = (int*)sc.get(256);
   SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
-  if (!eps || !xin || !dcoef || !dbc || !dstep || !dp) TANGO_FAIL("op_sched_masked: alloc");
+  float* dgt = (float*)sc.get((size_t)num_steps * B * 4);
+  float* dgs = (float*)sc.get((size_t)B * 4);
+  double* dgp = (double*)sc.get((size_t)B * chunks * 4 * 8);
+  if (!eps || !xin || !dcoef || !dbc || !dstep || !dp || !dgt || !dgs || !dgp) TANGO_FAIL(w + ": alloc");
   TANGO_TRY(launch_nchw_to_nhwc(DT_F32, model_out_nchw, eps, C, B2, C, HW, 1, 1.0f, s));
   TANGO_HIP(hipMemcpyAsync(dcoef, coef, (size_t)num_steps * coef_width * 4, hipMemcpyHostToDevice, s));
-  TANGO_HIP(hipMemcpyAsync(dbc, blend_coef, (size_t)num_steps * 2 * 4, hipMemcpyHostToDevice, s));
+  if (mk) TANGO_HIP(hipMemcpyAsync(dbc, blend_coef, (size_t)num_steps * 2 * 4, hipMemcpyHostToDevice, s));
   TANGO_HIP(hipMemcpyAsync(dstep, &step, 4, hipMemcpyHostToDevice, s));
+  // the row of THIS step: the kernels read gtable[step * B + b]
+  if (guided) TANGO_HIP(hipMemcpyAsync(dgt + (size_t)step * B, guidance_row, (size_t)B * 4, hipMemcpyHostToDevice, s));
   SchedParams p;
   p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = C; p.noise = noise; p.coef = dcoef; p.step_ptr = dstep;
   p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = rule;
   p.clip = 0; p.clip_range = 1.0f; p.seed = seed; p.sample_offset = sample_offset; p.ring = ms ? ring : nullptr; p.coef_w = coef_width;
   p.algo = algo;
-  p.x0 = known_latents; p.mask = latent_mask; p.blend_coef = dbc; p.blend_noise = blend_noise; p.num_steps = num_steps;
+  p.x0 = known_latents; p.mask = latent_mask; p.blend_coef = mk ? dbc : nullptr; p.blend_noise = blend_noise; p.num_steps = num_steps;
+  p.gtable = guided ? dgt : nullptr; p.rescale = guided ? rescale : 0.0f; p.gpart = guided ? dgp : nullptr; p.gscale = guided ? dgs : nullptr;
   TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
-  if (step == 0) TANGO_TRY(launch_inpaint_blend0(DT_F32, dp, B * HW, s));
-  TANGO_TRY(launch_sched_step(DT_F32, dp, B * HW, s, rule, true));
+  if (mk && step == 0) TANGO_TRY(launch_inpaint_blend0(DT_F32, dp, B * HW, s));
+  if (guided) TANGO_TRY(launch_guidance_stats(dp, B, HW, s));
+  TANGO_TRY(launch_sched_step(DT_F32, dp, B * HW, s, rule, mk, guided));
+  if (scale_out) {
+    if (rescale > 0.0f) TANGO_HIP(hipMemcpyAsync(scale_out, dgs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    else for (int b = 0; b < B; ++b) scale_out[b] = 1.0f;
+  }
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
+}
+
+int tango_op_sched_masked(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
+                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
+                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
+                          int pred_type, int rule, void* stream) {
+  return op_sched_any("op_sched_masked", false, latents, model_out_nchw, noise, ring, coef, coef_width, step, num_steps, known_latents,
+                      latent_mask, blend_coef, blend_noise, seed, sample_offset, B, C, HW, cfg, guidance, pred_type, rule, nullptr, 0.0f,
+                      nullptr, stream);
+}
+
+int tango_op_sched_guided(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
+                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
+                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
+                          int pred_type, int rule, const float* guidance_row, float rescale, float* scale_out, void* stream) {
+  return op_sched_any("op_sched_guided", true, latents, model_out_nchw, noise, ring, coef, coef_width, step, num_steps, known_latents,
+                      latent_mask, blend_coef, blend_noise, seed, sample_offset, B, C, HW, cfg, guidance, pred_type, rule, guidance_row,
+                      rescale, scale_out, stream);
 }
 
 int tango_op_latent_encode(const float* moments, int moments_batch, float* z0_out, float* xt_out, const float* eps, const float* noise,

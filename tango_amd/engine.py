@@ -267,7 +267,7 @@ class Engine:
     def denoise(self, latents, prompt_embeds, prompt_mask, timesteps, coef, guidance_scale, prediction_type="v_prediction",
                 rule="ddpm", clip_sample=False, clip_sample_range=1.0, noise=None, seed=0, sample_offset=0, use_graph=True,
                 beat_embeds=None, beat_mask=None, chord_embeds=None, chord_mask=None, prompt_mask_host=None, known_latents=None,
-                latent_mask=None, blend_coef=None, blend_noise=None, latent_h=None):
+                latent_mask=None, blend_coef=None, blend_noise=None, latent_h=None, guidance_table=None, guidance_rescale=0.0):
         """In-place denoise of `latents` [B,8,H,16] (fp32 cuda; H = 256, or `latent_h`: a height of the duration grid, which every
         [.., 256, 16] below then follows).  `timesteps` int64 [N] and `coef`
         float32 [N,8] ([N,16] for rule "dpmsolver") are host tables from tango_amd.scheduler.  `prompt_mask_host`: the caller's CPU copy of a `prompt_mask`
@@ -277,7 +277,12 @@ class Engine:
         Masked-latent inpainting (audioldm/ldm.py:724-818, ddim.py:210-217), any rule: `known_latents` [B,8,256,16] and `latent_mask`
         [B,1,256,16] (1 keeps the known audio, 0 regenerates it), `blend_coef` the scheduler's `blend_table()` [N,2] and optionally
         `blend_noise` [N,B,8,256,16] (else the device Philox generator's blend stream, keyed by `seed`).  Before the UNet call of every
-        loop index i, the latents become add_noise(known, n_i, t_i) * m + (1 - m) * latents; there is no blend after the last step."""
+        loop index i, the latents become add_noise(known, n_i, t_i) * m + (1 - m) * latents; there is no blend after the last step.
+
+        `guidance_table`: float32 [N, B] (tango_amd.scheduler.guidance_table), the guidance scale per step and latents row; it replaces
+        `guidance_scale` and always runs the [uncond; cond] batch.  `guidance_rescale` = phi in [0, 1] (Lin et al. 2023): the guided
+        output is v = phi * (cfg * std(cond) / std(cfg)) + (1 - phi) * cfg per sample (include/tango_engine.h
+        tango_guidance_args_t).  With neither, the call and its result are the plain tango_engine_denoise."""
         assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
         H = self._check_latents("latents", latents, latent_h)
         enc = self._f32(prompt_embeds)
@@ -296,9 +301,15 @@ class Engine:
             if os.environ.get("TANGO_DEBUG_MASK") and not torch.equal(mask.cpu(), mask_host):
                 raise ValueError("prompt_mask_host differs from the device prompt_mask")
             mask = mask_host.to(self.device, non_blocking=True)
-        rows = 2 * latents.shape[0] if guidance_scale > 1.0 else latents.shape[0]
+        rows = 2 * latents.shape[0] if guidance_scale > 1.0 or guidance_table is not None else latents.shape[0]
         self._check_cond("prompt_embeds", enc, mask, rows)
         ts = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int64))
+        gt = None
+        if guidance_table is not None:
+            gt = np.ascontiguousarray(np.asarray(guidance_table, dtype=np.float32))
+            if gt.shape != (len(ts), latents.shape[0]):
+                raise ValueError("guidance_table must be [num_steps, batch] = [%d, %d], got %s" % (len(ts), latents.shape[0], gt.shape))
+        guidance_rescale = float(guidance_rescale)
         cf = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
         width = 16 if rule == "dpmsolver" else 8
         if cf.shape != (len(ts), width):
@@ -351,7 +362,13 @@ class Engine:
             a.beat_embeds, a.beat_len, a.beat_mask = be.data_ptr(), be.shape[1], bm.data_ptr() if bm is not None else None
             a.chord_embeds, a.chord_len, a.chord_mask = ce.data_ptr(), ce.shape[1], cm.data_ptr() if cm is not None else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.tango_engine_denoise(self._h, C.byref(a), _stream_ptr()), "denoise")
+            if gt is None and guidance_rescale == 0.0:
+                _lib.check(self.lib.tango_engine_denoise(self._h, C.byref(a), _stream_ptr()), "denoise")
+            else:
+                g = _lib.GuidanceArgs()
+                g.table = gt.ctypes.data if gt is not None else None
+                g.rescale = guidance_rescale
+                _lib.check(self.lib.tango_engine_denoise_guided(self._h, C.byref(a), C.byref(g), _stream_ptr()), "denoise")
         return latents
 
     def _check_inpaint(self, latents, n, known_latents, latent_mask, blend_coef, blend_noise):

@@ -16,7 +16,7 @@ import torch
 from .engine import Engine, normalize_unet_config
 from .inpaint import check_latent_h, duration_geometry
 from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler  # noqa: F401  (re-exported like `from models import DDPMScheduler`)
-from .scheduler import DDIMInverseScheduler, from_diffusers
+from .scheduler import DDIMInverseScheduler, cfg_enabled, check_guidance_rescale, from_diffusers, guidance_table
 
 _TEXT_BUCKETS = (16, 32, 64, 128, 256, 512)
 
@@ -161,16 +161,30 @@ class AudioDiffusion:
             hs = self.text_encoder(input_ids=ids, attention_mask=am)[0]
         return hs, (am == 1).to(self.device)
 
-    def encode_text_classifier_free(self, prompt: List[str], num_samples_per_prompt: int):
-        """models.py:266-305: returns [uncond; cond] embeddings and the boolean mask."""
-        pe, pm, _ = self._encode_text_classifier_free(prompt, num_samples_per_prompt)
+    def encode_text_classifier_free(self, prompt: List[str], num_samples_per_prompt: int, negative_prompt=None):
+        """models.py:266-305: returns [uncond; cond] embeddings and the boolean mask.  `negative_prompt`: as in
+        _encode_text_classifier_free."""
+        pe, pm, _ = self._encode_text_classifier_free(prompt, num_samples_per_prompt, negative_prompt)
         return pe, pm
 
-    def _encode_text_classifier_free(self, prompt: List[str], num_samples_per_prompt: int):
+    def _encode_text_classifier_free(self, prompt: List[str], num_samples_per_prompt: int, negative_prompt=None):
         """the same, plus the tokenizer's own HOST copy of the mask (third value): `inference` hands it to the engine beside the device
-        mask, so that the plan is chosen without a device -> host read-back"""
+        mask, so that the plan is chosen without a device -> host read-back.
+
+        `negative_prompt`: None -- the unconditional half is T5("") padded to the prompt's length (models.py:282-289), one valid key
+        per row; a str -- that text against every prompt; or a list of len(prompt) strings.  Both halves are then tokenised to one
+        common length, the longer of the two (padded keys are masked, which is exact: _pad_text); a negative prompt longer than
+        the prompt is NOT cut to the prompt's length, as the reference's max_length=pe.shape[1], truncation=True would.  The order
+        stays [negative; cond]."""
         self._ensure_text()
         dev = self.device
+        if negative_prompt is not None:
+            if isinstance(negative_prompt, str):
+                negative_prompt = [negative_prompt] * len(prompt)
+            negative_prompt = list(negative_prompt)
+            if len(negative_prompt) != len(prompt):
+                raise ValueError("negative_prompt holds %d strings for %d prompts" % (len(negative_prompt), len(prompt)))
+            return self._encode_text_pair(prompt, negative_prompt, num_samples_per_prompt)
         batch = self.tokenizer(prompt, max_length=self.tokenizer.model_max_length, padding=True, truncation=True,
                                return_tensors="pt")
         ids, am = batch.input_ids.to(dev), batch.attention_mask.to(dev)
@@ -188,6 +202,27 @@ class AudioDiffusion:
         host = torch.cat([ub.attention_mask.repeat_interleave(num_samples_per_prompt, 0),
                           batch.attention_mask.repeat_interleave(num_samples_per_prompt, 0)]) == 1      # tokenizer outputs: CPU tensors
         return torch.cat([ne, pe]), (torch.cat([uam, am]) == 1).to(dev), host.cpu()
+
+    def _encode_text_pair(self, prompt, negative_prompt, num_samples_per_prompt):
+        """[negative; cond] with both halves at one length: each is tokenised on its own (padding=True: its longest row), then the
+        shorter one again with padding="max_length" at the longer one's length -- no row of either is truncated below the
+        tokenizer's model_max_length"""
+        dev = self.device
+        tok = lambda texts, **kw: self.tokenizer(texts, truncation=True, return_tensors="pt", **kw)   # noqa: E731
+        limit = self.tokenizer.model_max_length
+        cb, nb = tok(list(prompt), max_length=limit, padding=True), tok(negative_prompt, max_length=limit, padding=True)
+        L = max(cb.input_ids.shape[1], nb.input_ids.shape[1])
+        if cb.input_ids.shape[1] < L:
+            cb = tok(list(prompt), max_length=L, padding="max_length")
+        if nb.input_ids.shape[1] < L:
+            nb = tok(negative_prompt, max_length=L, padding="max_length")
+        halves = []
+        for b in (nb, cb):
+            with torch.no_grad():
+                e = self.text_encoder(input_ids=b.input_ids.to(dev), attention_mask=b.attention_mask.to(dev))[0]
+            halves.append((e.repeat_interleave(num_samples_per_prompt, 0), b.attention_mask.repeat_interleave(num_samples_per_prompt, 0)))
+        host = (torch.cat([halves[0][1], halves[1][1]]) == 1).cpu()
+        return torch.cat([halves[0][0], halves[1][0]]), host.to(dev), host
 
     # ---- latents -----------------------------------------------------------------------------
     def prepare_latents(self, batch_size, inference_scheduler, num_channels_latents, dtype, device, latent_h=256):
@@ -219,14 +254,16 @@ class AudioDiffusion:
 
     def _denoise(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
                  sample_offset, mask_host=None, known_latents=None, latent_mask=None, blend_noise=None, start=0, count=None,
-                 latent_h=256, **extra_conditions):
+                 latent_h=256, guidance_rescale=0.0, **extra_conditions):
         """the shared body of the loop of models.py:224-249 / mustango/models.py:563-598: seed derivation, text bucketing, scheduler
         tables, one engine call (`extra_conditions`: the Music UNet's beat / chord streams; `known_latents` / `latent_mask` /
         `blend_noise`: the masked loop of audioldm/ldm.py:724-818, Engine.denoise).  `start` > 0: the truncated loop of an edit over
         `timesteps[start:]` with the scheduler's truncated tables; `count`: the first `count` steps of a DDIMInverseScheduler.
         The clip length is the height of `latents` (a height of the duration grid); `latent_h` sizes the latents drawn here when
-        none are given."""
-        cfg_on = guidance_scale > 1.0
+        none are given.  `guidance_scale`: a scalar, or a per-sample [B] / per-step [N, B] table (scheduler.guidance_table; N counts
+        the EXECUTED steps of a truncated loop); `guidance_rescale`: phi of Engine.denoise."""
+        cfg_on = cfg_enabled(guidance_scale)
+        guidance_rescale = check_guidance_rescale(guidance_scale, guidance_rescale)
         B = prompt_embeds.shape[0] // 2 if cfg_on else prompt_embeds.shape[0]
         if not hasattr(inference_scheduler, "coef_table"):
             # a diffusers / fork scheduler object (the reference's loop takes any): the engine's class of the same name and config
@@ -262,7 +299,9 @@ class AudioDiffusion:
                            blend_noise=blend_noise)
         elif blend_noise is not None:
             raise ValueError("blend_noise needs known_latents and latent_mask")
-        self.engine.denoise(latents, pe, pm, timesteps.cpu().numpy(), coef, guidance_scale,
+        table = guidance_table(guidance_scale, len(timesteps), latents.shape[0])
+        self.engine.denoise(latents, pe, pm, timesteps.cpu().numpy(), coef, 1.0 if table is not None else guidance_scale,
+                            guidance_table=table, guidance_rescale=guidance_rescale,
                             prediction_type=c.prediction_type, rule=inference_scheduler.rule, clip_sample=c.clip_sample,
                             clip_sample_range=getattr(c, "clip_sample_range", 1.0), noise=noise, seed=seed,
                             sample_offset=sample_offset, use_graph=self.use_graph, prompt_mask_host=mask_host,
@@ -271,43 +310,48 @@ class AudioDiffusion:
 
     @torch.no_grad()
     def inference_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20,
-                                  guidance_scale=3, latents=None, noise=None, seed=None, sample_offset=0, mask_host=None, duration=10):
+                                  guidance_scale=3, latents=None, noise=None, seed=None, sample_offset=0, mask_host=None, duration=10,
+                                  guidance_rescale=0.0):
         """Loop of models.py:224-249 given the encoder outputs ([uncond; cond] when guidance > 1).  `mask_host`: optional CPU copy of
         a device-resident `boolean_prompt_mask` (see Engine.denoise).  `duration` (seconds, 2.5 .. 20 on the 2.5 s grid) sizes the
-        initial latents when `latents` is None; given latents carry their own height."""
+        initial latents when `latents` is None; given latents carry their own height.  `guidance_scale` may be a per-sample [B] or
+        per-step [N, B] table and `guidance_rescale` the rescale factor phi (_denoise)."""
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
-                             sample_offset, mask_host=mask_host, latent_h=duration_geometry(duration)[0])
+                             sample_offset, mask_host=mask_host, latent_h=duration_geometry(duration)[0],
+                             guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def inference(self, prompt, inference_scheduler, num_steps=20, guidance_scale=3, num_samples_per_prompt=1,
-                  disable_progress=True, duration=10):
+                  disable_progress=True, duration=10, negative_prompt=None, guidance_rescale=0.0):
         """models.py:210-257 (same signature, same return: latents [B*S, 8, 256, 16]); `duration` seconds of audio instead of 10:
-        latents [B*S, 8, int(duration * 25.6), 16] (audioldm/pipeline.py:94-95,113-126)."""
+        latents [B*S, 8, int(duration * 25.6), 16] (audioldm/pipeline.py:94-95,113-126).  `negative_prompt` (None, a str or one str per
+        prompt) replaces the empty unconditional text; it is read only when guidance is on."""
         host = None
-        if guidance_scale > 1.0:
-            pe, pm, host = self._encode_text_classifier_free(prompt, num_samples_per_prompt)
+        if cfg_enabled(guidance_scale):
+            pe, pm, host = self._encode_text_classifier_free(prompt, num_samples_per_prompt, negative_prompt)
         else:
             pe, pm = self.encode_text(prompt)
             pe = pe.repeat_interleave(num_samples_per_prompt, 0)
             pm = pm.repeat_interleave(num_samples_per_prompt, 0)
         return self.inference_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, mask_host=host,
-                                              duration=duration)
+                                              duration=duration, guidance_rescale=guidance_rescale)
 
     # ---- masked-latent inpainting (audioldm/pipeline.py:249-301, ldm.py:724-818, ddim.py:207-233) ------------------------------
     @torch.no_grad()
     def inpaint_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
                                 known_latents, latent_mask, latents=None, noise=None, blend_noise=None, seed=None, sample_offset=0,
-                                mask_host=None):
+                                mask_host=None, guidance_rescale=0.0):
         """The loop of inference_from_embeddings with the region where `latent_mask` [B, 1, 256, 16] is 1 held to the known latents
         `known_latents` [B, 8, 256, 16] (scale_factor * posterior sample of the encoded mel): before every UNet call the latents
         become inference_scheduler.add_noise(known, n_i, t_i) * m + (1 - m) * latents (ddim.py:210-217), none after the last step.
         `blend_noise` [N, B, 8, 256, 16] injects the n_i; by default they come from the engine's Philox generator under `seed`."""
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
                              sample_offset, mask_host=mask_host, known_latents=known_latents, latent_mask=latent_mask,
-                             blend_noise=blend_noise)
+                             blend_noise=blend_noise, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
-    def inpaint(self, prompt, known_latents, latent_mask, inference_scheduler, num_steps=20, guidance_scale=3, num_samples_per_prompt=1):
+    def inpaint(self, prompt, known_latents, latent_mask, inference_scheduler, num_steps=20, guidance_scale=3, num_samples_per_prompt=1,
+                negative_prompt=None, guidance_rescale=0.0):
         """inference() with masking: `known_latents` [K, 8, 256, 16] and `latent_mask` [K, 1, 256, 16] for the K prompts; with
         num_samples_per_prompt = S > 1, row k * S + j of the result pairs with clip k (the repeat_interleave order of the text
         embeddings, not ldm.py:791's candidate-major cat).  Returns latents [K * S, 8, 256, 16]."""
@@ -316,21 +360,22 @@ class AudioDiffusion:
             raise ValueError("known_latents and latent_mask need one row per prompt (%d), got %d and %d"
                              % (len(prompt), known_latents.shape[0], latent_mask.shape[0]))
         host = None
-        if guidance_scale > 1.0:
-            pe, pm, host = self._encode_text_classifier_free(prompt, S)
+        if cfg_enabled(guidance_scale):
+            pe, pm, host = self._encode_text_classifier_free(prompt, S, negative_prompt)
         else:
             pe, pm = self.encode_text(prompt)
             pe = pe.repeat_interleave(S, 0)
             pm = pm.repeat_interleave(S, 0)
         return self.inpaint_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale,
                                             known_latents=known_latents.repeat_interleave(S, 0),
-                                            latent_mask=latent_mask.repeat_interleave(S, 0), mask_host=host)
+                                            latent_mask=latent_mask.repeat_interleave(S, 0), mask_host=host,
+                                            guidance_rescale=guidance_rescale)
 
     # ---- audio-to-audio editing (audioldm/pipeline.py:145-247 style_transfer; latent_diffusion/ddim.py:246-304) ------------------
     @torch.no_grad()
     def edit_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
                              start_latents, strength, known_latents=None, latent_mask=None, noise=None, blend_noise=None, seed=None,
-                             sample_offset=0, mask_host=None):
+                             sample_offset=0, mask_host=None, guidance_rescale=0.0):
         """The last k = int(strength * num_steps) steps of the loop of inference_from_embeddings, from `start_latents` [B, 8, 256,
         16]: an existing clip's latents noised (AutoencoderKL.encode_start_latents) or inverted (invert_from_embeddings) to the
         level `inference_scheduler.edit_plan(num_steps, strength)` names.  The engine runs `timesteps[start:]` with the scheduler's
@@ -344,26 +389,26 @@ class AudioDiffusion:
         start, _ = inference_scheduler.edit_plan(num_steps, strength)
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, start_latents, noise,
                              seed, sample_offset, mask_host=mask_host, known_latents=known_latents, latent_mask=latent_mask,
-                             blend_noise=blend_noise, start=start)
+                             blend_noise=blend_noise, start=start, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def edit(self, prompt, start_latents, inference_scheduler, num_steps=20, guidance_scale=3, strength=0.5, num_samples_per_prompt=1,
-             known_latents=None, latent_mask=None, seed=None):
+             known_latents=None, latent_mask=None, seed=None, negative_prompt=None, guidance_rescale=0.0):
         """edit_from_embeddings() for prompt strings, encoded like inference() / inpaint(): `start_latents` (and `known_latents`
         / `latent_mask` when given) hold one row per prompt and sample, row k * S + j for sample j of prompt k."""
         S = num_samples_per_prompt
         if start_latents.shape[0] != len(prompt) * S:
             raise ValueError("start_latents need one row per prompt and sample (%d), got %d" % (len(prompt) * S, start_latents.shape[0]))
         host = None
-        if guidance_scale > 1.0:
-            pe, pm, host = self._encode_text_classifier_free(prompt, S)
+        if cfg_enabled(guidance_scale):
+            pe, pm, host = self._encode_text_classifier_free(prompt, S, negative_prompt)
         else:
             pe, pm = self.encode_text(prompt)
             pe = pe.repeat_interleave(S, 0)
             pm = pm.repeat_interleave(S, 0)
         return self.edit_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, start_latents=start_latents,
                                          strength=strength, known_latents=known_latents, latent_mask=latent_mask, seed=seed,
-                                         mask_host=host)
+                                         mask_host=host, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def invert_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, *, latents, count,
@@ -411,7 +456,7 @@ class MusicAudioDiffusion(AudioDiffusion):
     def inference_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3,
                                   latents=None, noise=None, seed=None, sample_offset=0, *, encoded_beats=None, beat_mask=None,
                                   encoded_chords=None, chord_mask=None, known_latents=None, latent_mask=None, blend_noise=None,
-                                  duration=10):
+                                  duration=10, guidance_rescale=0.0):
         """mustango/models.py:540-598 given the three encoder outputs ([uncond; cond] when guidance > 1); with `known_latents` /
         `latent_mask` (/ `blend_noise`) the masked loop of AudioDiffusion.inpaint_from_embeddings.  `duration` sizes the initial
         latents when none are given, as in AudioDiffusion.inference_from_embeddings."""
@@ -419,18 +464,18 @@ class MusicAudioDiffusion(AudioDiffusion):
             raise ValueError("encoded_beats and encoded_chords are required (mustango/models.py:548-550)")
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
                              sample_offset, known_latents=known_latents, latent_mask=latent_mask, blend_noise=blend_noise,
-                             latent_h=duration_geometry(duration)[0],
+                             latent_h=duration_geometry(duration)[0], guidance_rescale=guidance_rescale,
                              beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
 
     @torch.no_grad()
     def inpaint_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
                                 known_latents, latent_mask, latents=None, noise=None, blend_noise=None, seed=None, sample_offset=0,
-                                encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None):
+                                encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None, guidance_rescale=0.0):
         """AudioDiffusion.inpaint_from_embeddings with the beat / chord streams of inference_from_embeddings"""
         return self.inference_from_embeddings(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale,
                                               latents, noise, seed, sample_offset, encoded_beats=encoded_beats, beat_mask=beat_mask,
                                               encoded_chords=encoded_chords, chord_mask=chord_mask, known_latents=known_latents,
-                                              latent_mask=latent_mask, blend_noise=blend_noise)
+                                              latent_mask=latent_mask, blend_noise=blend_noise, guidance_rescale=guidance_rescale)
 
     @staticmethod
     def _need_music(encoded_beats, encoded_chords):
@@ -440,7 +485,8 @@ class MusicAudioDiffusion(AudioDiffusion):
     @torch.no_grad()
     def edit_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
                              start_latents, strength, known_latents=None, latent_mask=None, noise=None, blend_noise=None, seed=None,
-                             sample_offset=0, encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None):
+                             sample_offset=0, encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None,
+                             guidance_rescale=0.0):
         """AudioDiffusion.edit_from_embeddings with the beat / chord streams of inference_from_embeddings"""
         if not hasattr(inference_scheduler, "coef_table"):
             inference_scheduler = from_diffusers(inference_scheduler)
@@ -450,7 +496,7 @@ class MusicAudioDiffusion(AudioDiffusion):
         self._need_music(encoded_beats, encoded_chords)
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, start_latents, noise,
                              seed, sample_offset, known_latents=known_latents, latent_mask=latent_mask, blend_noise=blend_noise,
-                             start=start,
+                             start=start, guidance_rescale=guidance_rescale,
                              beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
 
     @torch.no_grad()

@@ -54,10 +54,12 @@ class Predictor(BasePredictor):
                 model: str = Input(description="choose a model", choices=["tango2", "tango2-full"], default="tango2"),
                 steps: int = Input(description="inference steps", default=100),
                 guidance: float = Input(description="guidance scale", default=3),
+                negative_prompt: str = Input(description="text to steer away from (empty: none)", default=""),
                 out: str = "/tmp/output.wav") -> Path:
         """Run a single prediction (predict.py:37-67): generate -> write 16 kHz wav -> return its path."""
         if model not in self.models:
             raise KeyError("unknown model %r; loaded: %s" % (model, sorted(self.models)))
-        audio = self.models[model].generate(prompt, steps, guidance)
+        extra = {"negative_prompt": negative_prompt} if negative_prompt else {}      # unset: the call every generator has always taken
+        audio = self.models[model].generate(prompt, steps, guidance, **extra)
         write_wav(out, audio, SAMPLE_RATE)
         return Path(out)

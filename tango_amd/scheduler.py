@@ -557,3 +557,45 @@ def _init_params(cls):
             names |= {p.name for p in inspect.signature(c.__init__).parameters.values()
                       if p.kind not in (p.VAR_KEYWORD, p.VAR_POSITIONAL)}
     return names - {"self"}
+
+
+# ---- guidance as a table (include/tango_engine.h tango_guidance_args_t) ------------------------------------------------------------
+def guidance_is_table(guidance):
+    """False for a plain scalar (a Python / numpy number or a 0-dim array / tensor), True for a sequence, array or tensor"""
+    if torch.is_tensor(guidance):
+        return guidance.dim() > 0
+    return np.ndim(guidance) > 0
+
+
+def cfg_enabled(guidance):
+    """does this guidance argument run the [uncond; cond] batch?  A scalar: when > 1 (models.py:213); a table: always"""
+    return True if guidance_is_table(guidance) else float(guidance) > 1.0
+
+
+def guidance_table(guidance, num_steps, batch):
+    """The host table of a guidance argument: None for a plain scalar (the engine's scalar path, unchanged), else float32
+    [num_steps, batch] -- a [batch] row (one scale per latents row, constant over the steps) repeated for every step, or a
+    [num_steps, batch] schedule as it is.  `batch` counts latents rows (prompts x samples).  ValueError for any other shape and for
+    entries that are negative or not finite (1.0 gives the conditional output, 0.0 the unconditional one)."""
+    if not guidance_is_table(guidance):
+        return None
+    g = guidance.detach().cpu().numpy() if torch.is_tensor(guidance) else np.asarray(guidance)
+    g = g.astype(np.float32)
+    if g.shape == (batch,):
+        g = np.broadcast_to(g, (num_steps, batch))
+    elif g.shape != (num_steps, batch):
+        raise ValueError("a guidance table is [%d] (per sample) or [%d, %d] (per step and sample), got %s"
+                         % (batch, num_steps, batch, g.shape))
+    if not np.all(np.isfinite(g)) or np.any(g < 0):
+        raise ValueError("guidance table entries must be finite and >= 0")
+    return np.ascontiguousarray(g)
+
+
+def check_guidance_rescale(guidance, guidance_rescale):
+    """guidance_rescale in [0, 1], and > 0 only with classifier-free guidance on: ValueError otherwise (no device needed)"""
+    r = float(guidance_rescale)
+    if not 0.0 <= r <= 1.0:          # NaN fails both comparisons
+        raise ValueError("guidance_rescale must be in [0, 1], got %r" % (guidance_rescale,))
+    if r > 0.0 and not cfg_enabled(guidance):
+        raise ValueError("guidance_rescale needs classifier-free guidance: guidance > 1 or a guidance table, got %r" % (guidance,))
+    return r

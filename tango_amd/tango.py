@@ -6,12 +6,14 @@ on the HIP engine.  `name` may be a local directory holding the HF snapshot file
 import json
 import os
 
+import numpy as np
 import torch
 
 from .autoencoder import AutoencoderKL
 from .inpaint import clip_duration, duration_geometry, latent_mask, prepare_waveform
 from .models import AudioDiffusion
 from .scheduler import SD21_SCHEDULER_CONFIG, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+from .scheduler import cfg_enabled, check_guidance_rescale, guidance_is_table
 from .stft import wav_to_fbank
 
 _CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")
@@ -69,25 +71,59 @@ class Tango:
         for i in range(0, len(lst), n):
             yield lst[i:i + n]
 
-    def generate(self, prompt, steps=100, guidance=3, samples=1, disable_progress=True, duration=10):
+    @staticmethod
+    def _check_guidance(guidance, guidance_rescale):
+        """the guidance argument checks that need no device: guidance_rescale in [0, 1], and > 0 only with guidance on"""
+        return check_guidance_rescale(guidance, guidance_rescale)
+
+    @staticmethod
+    def _slice_per_batch(value, k, n, rows_per_prompt=1):
+        """prompts k .. k + n - 1 of a per-prompt list, or their latents rows (the last axis) of a guidance table; anything else as it is"""
+        if isinstance(value, (list, tuple)) and all(isinstance(v, str) for v in value):
+            return list(value[k:k + n])
+        if value is not None and guidance_is_table(value):
+            value = value if torch.is_tensor(value) else np.asarray(value)
+            return value[..., k * rows_per_prompt:(k + n) * rows_per_prompt]
+        return value
+
+    def generate(self, prompt, steps=100, guidance=3, samples=1, disable_progress=True, duration=10, negative_prompt=None,
+                 guidance_rescale=0.0):
         """ Generate audio for a single prompt string. (tango.py:43-49)  `duration`: seconds of audio, 2.5 .. 20 on the 2.5 s grid
-        (audioldm/pipeline.py:113-126 text_to_audio); a ValueError for anything else. """
+        (audioldm/pipeline.py:113-126 text_to_audio); a ValueError for anything else.
+
+        `negative_prompt`: text the result is steered away from (the unconditional half of the guidance batch; None: the empty
+        text, as the reference).  `guidance`: a scalar, or one scale per sample ([samples]) or per step and sample ([steps,
+        samples]).  `guidance_rescale` in [0, 1]: Lin et al. 2023, pulls the guided output back to the conditional output's
+        per-sample standard deviation (0 = off). """
+        self._check_guidance(guidance, guidance_rescale)
         with torch.no_grad():
             latents = self.model.inference([prompt], self.scheduler, steps, guidance, samples, disable_progress=disable_progress,
-                                           duration=duration)
+                                           duration=duration, negative_prompt=negative_prompt, guidance_rescale=guidance_rescale)
             mel = self.vae.decode_first_stage(latents)
             wave = self.vae.decode_to_waveform(mel)
         return wave[0]
 
-    def generate_for_batch(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, disable_progress=True, duration=10):
-        """ Generate audio for a list of prompt strings. (tango.py:51-64)  `duration`: as in generate(), one length for all. """
+    def generate_for_batch(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, disable_progress=True, duration=10,
+                           negative_prompt=None, guidance_rescale=0.0):
+        """ Generate audio for a list of prompt strings. (tango.py:51-64)  `duration`: as in generate(), one length for all.
+        `negative_prompt` (None, a str, or one str per prompt), `guidance` (a scalar, or a table over all len(prompts) * samples
+        latents rows: [rows] or [steps, rows]) and `guidance_rescale` as in generate(); a list and a table are sliced per batch
+        like the prompts. """
         duration_geometry(duration)
+        self._check_guidance(guidance, guidance_rescale)
+        if isinstance(negative_prompt, (list, tuple)) and len(negative_prompt) != len(prompts):
+            raise ValueError("negative_prompt holds %d strings for %d prompts" % (len(negative_prompt), len(prompts)))
+        if guidance_is_table(guidance) and np.shape(guidance)[-1] != len(prompts) * samples:
+            raise ValueError("a guidance table holds one entry per prompt and sample (%d), got %d"
+                             % (len(prompts) * samples, np.shape(guidance)[-1]))
         outputs = []
         for k in range(0, len(prompts), batch_size):
             batch = prompts[k: k + batch_size]
             with torch.no_grad():
-                latents = self.model.inference(batch, self.scheduler, steps, guidance, samples, disable_progress=disable_progress,
-                                               duration=duration)
+                latents = self.model.inference(batch, self.scheduler, steps, self._slice_per_batch(guidance, k, len(batch), samples),
+                                               samples, disable_progress=disable_progress, duration=duration,
+                                               negative_prompt=self._slice_per_batch(negative_prompt, k, len(batch)),
+                                               guidance_rescale=guidance_rescale)
                 mel = self.vae.decode_first_stage(latents)
                 wave = self.vae.decode_to_waveform(mel)
                 outputs += [item for item in wave]
@@ -95,18 +131,29 @@ class Tango:
             return outputs
         return list(self.chunks(outputs, samples))
 
-    def generate_for_batch_dp(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, group=None, duration=10):
+    def generate_for_batch_dp(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, group=None, duration=10,
+                              negative_prompt=None, guidance_rescale=0.0):
         """Data-parallel `generate_for_batch` over the ranks of the default (or given) torch.distributed group: one
         process per GPU, each holding a full `Tango`.  Every rank makes this call; rank 0's `prompts` are used, the text
         encoder runs on rank 0 only, embeddings travel by one RCCL broadcast per pass of `batch_size * world` prompts,
         int16 waveforms come back by one gather.  Returns the `generate_for_batch` result on rank 0, None elsewhere.
-        `duration`: as in generate(); every rank passes the same value."""
+        `duration`: as in generate(); every rank passes the same value.  `negative_prompt` (rank 0's is used: rank 0 encodes, nothing
+        new travels) and `guidance_rescale` (every rank passes the same value) as in generate_for_batch(); a guidance TABLE is
+        refused with a ValueError: sharding it over the ranks is not implemented."""
         from .parallel import generate_for_batch_dp
+        if guidance_is_table(guidance):
+            raise ValueError("generate_for_batch_dp takes a scalar guidance: a guidance table is not sharded over the ranks")
+        self._check_guidance(guidance, guidance_rescale)
+        if isinstance(negative_prompt, (list, tuple)) and prompts is not None and len(negative_prompt) != len(prompts):
+            raise ValueError("negative_prompt holds %d strings for %d prompts" % (len(negative_prompt), len(prompts)))
         latent_h, frames, _ = duration_geometry(duration)
+        done = [0]            # prompts encoded so far: passes are encoded in order, each once
 
         def encode(batch, n_per_prompt, g):
             if g > 1.0:
-                pe, pm = self.model.encode_text_classifier_free(batch, n_per_prompt)
+                neg = self._slice_per_batch(negative_prompt, done[0], len(batch))
+                done[0] += len(batch)
+                pe, pm = self.model.encode_text_classifier_free(batch, n_per_prompt, neg)
             else:
                 pe, pm = self.model.encode_text(batch)
                 pe, pm = pe.repeat_interleave(n_per_prompt, 0), pm.repeat_interleave(n_per_prompt, 0)
@@ -120,7 +167,7 @@ class Tango:
             ecfg = self.model.engine._cfg
             lat = dp_initial_latents(seed, offset, b, self.model.unet.config.in_channels, latent_h, ecfg.latent_w) * self.scheduler.init_noise_sigma
             latents = self.model.inference_from_embeddings(pe, pm, self.scheduler, steps, guidance, latents=lat, seed=seed,
-                                                           sample_offset=offset)
+                                                           sample_offset=offset, guidance_rescale=guidance_rescale)
             return self.vae.engine.vocode(self.vae.decode_first_stage(latents))      # int16 stays on the device
 
         with torch.no_grad():
@@ -128,7 +175,9 @@ class Tango:
                                          guidance=guidance, samples=samples, batch_size=batch_size, group=group)
 
     def generate_from_embeddings(self, prompt_embeds, boolean_prompt_mask, steps=100, guidance=3, duration=10, **kw):
-        """Same three calls given the text-encoder outputs (benchmarks / data-parallel workers); `duration` as in generate()."""
+        """Same three calls given the text-encoder outputs (benchmarks / data-parallel workers); `duration` as in generate().
+        `guidance` may be a table over the latents rows, and `guidance_rescale=` goes through `kw` (AudioDiffusion.inference_from_embeddings);
+        a negative prompt is the first half of `prompt_embeds`."""
         with torch.no_grad():
             latents = self.model.inference_from_embeddings(prompt_embeds, boolean_prompt_mask, self.scheduler, steps, guidance,
                                                            duration=duration, **kw)
@@ -136,7 +185,8 @@ class Tango:
             return self.vae.decode_to_waveform(mel)
 
     # ---- masked-latent inpainting (audioldm/pipeline.py:249-301 super_resolution_and_inpainting) ------------------------------
-    def inpaint(self, prompt, audio, time_range=(0.10, 0.15), freq_range=(1.0, 1.0), steps=100, guidance=3, samples=1, duration=10):
+    def inpaint(self, prompt, audio, time_range=(0.10, 0.15), freq_range=(1.0, 1.0), steps=100, guidance=3, samples=1, duration=10,
+                negative_prompt=None, guidance_rescale=0.0):
         """Regenerate the time span `time_range` and the mel band `freq_range` (fractions of the clip, ldm.py:773-777) of one 16 kHz
         clip `audio` (1-D; reading and resampling are the caller's) under the text `prompt`; the rest keeps the clip's audio.
         Returns np.int16 [samples, 163872].
@@ -144,11 +194,14 @@ class Tango:
         `duration`: seconds the clip is cut or zero-padded to (2.5 .. 20 on the 2.5 s grid; 10 -> 163872 samples, else
         duration_geometry(duration)[2]).  None: the smallest grid duration that holds the clip (tango_amd.inpaint.clip_duration; a 3 s
         clip runs as 5 s, a quarter of the latent rows of the default), 20 s for longer clips.  AudioLDM's round_up_duration
-        (pipeline.py:49-50) always adds one more 2.5 s block instead; that is not reproduced."""
+        (pipeline.py:49-50) always adds one more 2.5 s block instead; that is not reproduced.
+        `negative_prompt`, table `guidance` and `guidance_rescale`: as in generate()."""
+        self._check_guidance(guidance, guidance_rescale)
         with torch.no_grad():
             known = self.encode_audio(audio, duration)
             mask = latent_mask(1, time_range, freq_range, known.shape[2], known.shape[3])
-            latents = self.model.inpaint([prompt], known, mask, self.scheduler, steps, guidance, samples)
+            latents = self.model.inpaint([prompt], known, mask, self.scheduler, steps, guidance, samples,
+                                         negative_prompt=negative_prompt, guidance_rescale=guidance_rescale)
             mel = self.vae.decode_first_stage(latents)
             return self.vae.decode_to_waveform(mel)
 
@@ -158,7 +211,7 @@ class Tango:
         generate_from_embeddings); `kw` goes to AudioDiffusion.inpaint_from_embeddings (latents, noise, blend_noise, seed, ...)."""
         with torch.no_grad():
             known = self.encode_audio(audio, duration)
-            rows = prompt_embeds.shape[0] // 2 if guidance > 1.0 else prompt_embeds.shape[0]
+            rows = prompt_embeds.shape[0] // 2 if cfg_enabled(guidance) else prompt_embeds.shape[0]
             if rows != samples:
                 raise ValueError("prompt_embeds hold %d rows, `samples` is %d" % (rows, samples))
             mask = latent_mask(samples, time_range, freq_range, known.shape[2], known.shape[3])
@@ -169,7 +222,7 @@ class Tango:
 
     # ---- audio-to-audio editing (audioldm/pipeline.py:145-247 style_transfer) -----------------------------------------------------
     def edit(self, prompt, audio, strength=0.5, steps=100, guidance=3, samples=1, mode="noise", source_prompt="", time_range=None,
-             freq_range=None, seed=None, duration=10):
+             freq_range=None, seed=None, duration=10, negative_prompt=None, guidance_rescale=0.0):
         """Edit one 16 kHz clip `audio` (1-D; reading and resampling are the caller's) towards the text `prompt`: the clip's latents
         are moved part of the way into the noise and the last k = int(strength * steps) of `steps` denoise steps run from there.
         Returns np.int16 [samples, 163872].
@@ -186,12 +239,15 @@ class Tango:
         `duration`: seconds the clip is cut or zero-padded to, as in inpaint() (None: the smallest grid duration that holds the
         clip, without round_up_duration's extra 2.5 s block); the result has duration_geometry(duration)[2] samples.
 
+        `negative_prompt` and `guidance_rescale`: as in generate(); a `guidance` table counts the k EXECUTED steps ([k, samples]).
+
         Not reproduced from AudioLDM: the `samples[:, :, :-3, :]` crop of the decoded mel (pipeline.py:241)."""
         with torch.no_grad():
             self._check_edit(mode, steps, strength)
+            self._check_guidance(guidance, guidance_rescale)
             host = None
-            if guidance > 1.0:
-                pe, pm, host = self.model._encode_text_classifier_free([prompt], samples)
+            if cfg_enabled(guidance):
+                pe, pm, host = self.model._encode_text_classifier_free([prompt], samples, negative_prompt)
             else:
                 pe, pm = self.model.encode_text([prompt])
                 pe, pm = pe.repeat_interleave(samples, 0), pm.repeat_interleave(samples, 0)
@@ -200,7 +256,7 @@ class Tango:
                 se, sm = self.model.encode_text([source_prompt])
                 src = (se.repeat_interleave(samples, 0).float(), sm.repeat_interleave(samples, 0))
             return self._edit(pe.float(), pm, audio, strength, steps, guidance, samples, mode, src, time_range, freq_range, seed,
-                              dict(mask_host=host), duration)
+                              dict(mask_host=host, guidance_rescale=guidance_rescale), duration)
 
     def edit_from_embeddings(self, prompt_embeds, boolean_prompt_mask, audio, strength=0.5, steps=100, guidance=3, samples=1,
                              mode="noise", source_embeds=None, source_mask=None, time_range=None, freq_range=None, seed=None,
@@ -210,7 +266,7 @@ class Tango:
         (conditional rows only).  `kw` goes to AudioDiffusion.edit_from_embeddings (noise, blend_noise, sample_offset)."""
         with torch.no_grad():
             self._check_edit(mode, steps, strength)
-            rows = prompt_embeds.shape[0] // 2 if guidance > 1.0 else prompt_embeds.shape[0]
+            rows = prompt_embeds.shape[0] // 2 if cfg_enabled(guidance) else prompt_embeds.shape[0]
             if rows != samples:
                 raise ValueError("prompt_embeds hold %d rows, `samples` is %d" % (rows, samples))
             src = None
