@@ -315,6 +315,11 @@ const char* tango_debug_linear_route(int dtype, int M, int N, int K, int geglu, 
 /* the GroupNorm kernel form tango_op_groupnorm runs for this shape under the current switches: "slab", "coop" (cooperative single launch), "group" (one
    workgroup per (sample, group)), "two" (statistics + apply launches); "" = refused.  Asks the device for the cooperative kernel's occupancy. */
 const char* tango_debug_groupnorm_form(int dtype, int B, int C, int HW, int groups);
+/* host-side query, no GPU needed: the attention kernel tango_op_attention[_ex] and the engine run for this problem under the current switches, as
+ * "qb<query blocks per wave>:<form> <grid x>x<y>x<z>", e.g. "qb2:msum+kdma+vdma 32x5x32"; forms: plain, masked, posbias, msum, defer, msum+defer, msum+kdma,
+ * msum+kdma+vdma, f8, f8+msum, x8.  Arguments the launch refuses answer its message instead.  masked / pos_bias: a key-mask bias / a relative position
+ * bias is given; fp8_pv 0 | 1 | 2 and vt_perm as in tango_op_attention_ex's flags.  dtype 0 = fp32, 1 = fp16, 2 = bf16.  tests/test_attention_routes.py */
+const char* tango_debug_attention_route(int dtype, int B, int heads, int Sq, int Skv, int masked, int pos_bias, int fp8_pv, int vt_perm);
 
 /* ---- per-operator entry points (parity tests; fp32 reference-layout tensors on device) ---- */
 int tango_op_conv2d(int dtype, const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W,

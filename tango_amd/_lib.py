@@ -130,6 +130,7 @@ SYMBOLS = [
     "tango_debug_conv_transpose1d_phase",
     "tango_op_linear_ex", "tango_debug_linear_ex_check", "tango_op_conv2d_temb", "tango_op_conv2d_ups_temb",
     "tango_engine_denoise_guided", "tango_debug_denoise_guided_check", "tango_op_sched_guided",
+    "tango_debug_attention_route",
 ]
 
 _lib = None
@@ -187,6 +188,8 @@ def load():
     lib.tango_debug_linear_route.restype = C.c_char_p
     lib.tango_debug_groupnorm_form.argtypes = [ci] * 5
     lib.tango_debug_groupnorm_form.restype = C.c_char_p
+    lib.tango_debug_attention_route.argtypes = [ci] * 9
+    lib.tango_debug_attention_route.restype = C.c_char_p
     lib.tango_engine_ring_elems.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.tango_engine_plan_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(ci)]
     lib.tango_op_conv2d.argtypes = [ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]

@@ -546,90 +546,110 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_kernel(const AttnParams p)
   }
 }
 
-bool attention_vt_perm_ok(int dtype, const AttnParams& p) {
-  return dtype != DT_F32 && !p.bias && !p.pos_bias && p.Skv % 64 == 0 && p.Sq > 512 && p.fp8_pv == 0 && p.ldvt % 8 == 0;
+// ---- host: which instantiation a site runs ----
+// One pure function of (dtype, AttnParams, tuning()) chooses; attn_launch() below only spells the chosen instantiation, the engine asks
+// plan_attention_site() what its producer may write, and tango_debug_attention_route answers attn_plan_name().  The first matching rule
+// wins.  Three precedences are measured history, not design: DEFER beats KDMA, KDMA needs MSUM, a vt_perm site reads no switch.
+AttnPlan plan_attention(int dtype, const AttnParams& p) {
+  AttnPlan pl;
+  const bool h16 = dtype == DT_F16 || dtype == DT_BF16;
+  const int64_t esz = h16 ? 2 : 4;
+  const bool masked = p.bias != nullptr || (p.Skv % 64) != 0;
+  auto refuse = [&](const char* why) { pl.refusal = why; return pl; };
+  if (!h16 && dtype != DT_F32) return refuse("attention: bad dtype");
+  if ((p.ldq * esz) % 16 || (p.ldk * esz) % 16 || (p.ldvt * esz) % 16 || (p.ldo * esz) % 8) return refuse("attention: ld alignment");
+  // a permuted V^T is only understood by the LDS-DMA form of the long unmasked 16-bit sites: never read it with another kernel
+  if (p.vt_perm && !(h16 && !masked && !p.pos_bias && p.Sq > 512 && p.fp8_pv == 0 && p.ldvt % 8 == 0))
+    return refuse("attention: vt_perm needs an unmasked 16-bit site with Sq > 512, Skv % 64 == 0, no fp8 P.V");
+  if (p.fp8_pv && !h16) return refuse("attention: fp8 P.V needs a 16-bit engine (Q.K^T stays in the engine dtype)");
+  // (ADVICE r3) never fall back silently: a config-5 run must not measure the 16-bit kernel under the fp8 label
+  if (p.fp8_pv && (masked || p.pos_bias)) return refuse("attention: fp8 P.V is implemented for unmasked sites with Skv % 64 == 0 only");
+  if (p.fp8_pv == 2 && p.Skv % 128 != 0) return refuse("attention: MX fp8 P.V (128 keys per MFMA) needs Skv % 128 == 0");
+
+  const Tuning& t = tuning();
+  if (p.fp8_pv == 2) {
+    // MX P.V: 128-key tiles.  32 query rows per wave at two waves per SIMD (the 64 S^T accumulators of a 128-key tile do not fit three), or 16
+    // rows per wave at three (TANGO_ATTN_X8_QB; measured: DESIGN.md section 5, round 6)
+    pl.form = AF_X8;
+    pl.qb = t.attn_x8_qb == 2 && p.Sq % 128 == 0 ? 2 : 1;
+    pl.minw = pl.qb == 2 ? 2 : 3;
+  } else if (p.pos_bias) {
+    pl.form = AF_POSBIAS;   // text-encoder self-attention (short sequences): one query block per wave
+  } else {
+    // Sq > 512: 4 waves x 32 query rows per workgroup at 3 workgroups/CU.  Wider workgroups (6 or 8 waves sharing one K/V tile stream, i.e.
+    // 1.5-2x fewer L2->LDS bytes per flop) were measured in round 1: 8 waves 10.5 ms vs 9.2 ms per step at Sq = Skv = 4096; 48 or 64 query
+    // rows per wave at 2 waves/SIMD: 9.2 / 10.1 ms -- the kernel is VALU (softmax) co-limited, not fill-limited.
+    // Short sequences at large batch (levels 1-2 at B >= 8): 32 query rows per wave halve the K / V tile traffic and the workgroup count once
+    // there are enough workgroups to fill the chip anyway (round 4)
+    const bool many = t.attn_qb2_min_wgs > 0 && (long)((p.Sq + 127) / 128) * p.heads * p.B >= t.attn_qb2_min_wgs && p.Sq % 128 == 0;
+    pl.qb = p.Sq > 512 || many ? 2 : 1;
+    if (masked) pl.form = AF_MASKED;
+    else if (!h16) pl.form = AF_PLAIN;
+    else if (p.vt_perm) pl.form = AF_MSUM_KDMA_VDMA;
+    else if (p.fp8_pv) pl.form = t.attn_msum ? AF_F8_MSUM : AF_F8;
+    else if (t.attn_msum && t.attn_defer) pl.form = AF_MSUM_DEFER;
+    else if (t.attn_msum && t.attn_kdma && p.Sq > 512) pl.form = AF_MSUM_KDMA;
+    else if (t.attn_msum) pl.form = AF_MSUM;
+    else if (t.attn_defer) pl.form = AF_DEFER;
+    else pl.form = AF_PLAIN;
+  }
+  pl.grid[0] = (unsigned)((p.Sq + 64 * pl.qb - 1) / (64 * pl.qb)); pl.grid[1] = (unsigned)p.heads; pl.grid[2] = (unsigned)p.B;
+  return pl;
 }
+
+std::string attn_plan_name(const AttnPlan& pl) {
+  static const char* const forms[] = {"plain", "masked", "posbias", "msum", "defer", "msum+defer", "msum+kdma", "msum+kdma+vdma", "f8", "f8+msum", "x8"};
+  return "qb" + std::to_string(pl.qb) + ":" + forms[pl.form];
+}
+
+AttnSite plan_attention_site(int dtype, int B, int heads, int S, int want_fp8) {
+  AttnParams p;
+  p.q = p.k = p.vt = nullptr; p.o = nullptr; p.ldq = p.ldk = p.ldo = 0; p.ldvt = S;
+  p.bias = nullptr; p.B = B; p.heads = heads; p.Sq = S; p.Skv = S; p.scale = 0.125f;
+  AttnSite site;
+  for (p.fp8_pv = want_fp8 == 2 ? 2 : want_fp8 != 0; p.fp8_pv > 0 && plan_attention(dtype, p).refusal; --p.fp8_pv) {}   // MX -> plain fp8 -> engine dtype, as far as the site allows
+  site.fp8_pv = p.fp8_pv;
+  p.vt_perm = 1;
+  site.vt_perm_ok = plan_attention(dtype, p).refusal == nullptr;
+  return site;
+}
+
+static constexpr int attn_key(AttnForm f, int qb) { return (int)f * 2 + qb - 1; }
 
 template <typename T>
 static int attn_launch(const AttnParams& p, hipStream_t s) {
-  if ((p.ldq * (int64_t)sizeof(T)) % 16 || (p.ldk * (int64_t)sizeof(T)) % 16 || (p.ldvt * (int64_t)sizeof(T)) % 16 ||
-      (p.ldo * (int64_t)sizeof(T)) % 8)
-    TANGO_FAIL("attention: ld alignment");
-  const bool masked = p.bias != nullptr || (p.Skv % 64) != 0;
-  // a permuted V^T is only understood by the LDS-DMA form of the long unmasked 16-bit sites: never read it with another kernel
-  if (p.vt_perm && !attention_vt_perm_ok(TypeTag<T>::dt, p)) TANGO_FAIL("attention: vt_perm needs an unmasked 16-bit site with Sq > 512, Skv % 64 == 0, no fp8 P.V");
-  if (p.fp8_pv && sizeof(T) != 2) TANGO_FAIL("attention: fp8 P.V needs a 16-bit engine (Q.K^T stays in the engine dtype)");
-  // (ADVICE r3) never fall back silently: a config-5 run must not measure the 16-bit kernel under the fp8 label
-  if (p.fp8_pv && (masked || p.pos_bias)) TANGO_FAIL("attention: fp8 P.V is implemented for unmasked sites with Skv % 64 == 0 only");
-  if (p.fp8_pv == 2 && p.Skv % 128 != 0) TANGO_FAIL("attention: MX fp8 P.V (128 keys per MFMA) needs Skv % 128 == 0");
-  if constexpr (sizeof(T) == 2) {
-    if (p.fp8_pv == 2) {
-      // MX P.V (X8): 128-key tiles.  Two forms, picked by TANGO_ATTN_X8_QB (measured: DESIGN.md section 5, round 6): 32 query rows per
-      // wave at two waves per SIMD (the 64 S^T accumulators of a 128-key tile do not fit three), or 16 rows per wave at three
-      const bool qb2 = tuning().attn_x8_qb == 2 && p.Sq % 128 == 0;
-      if (qb2) {
-        dim3 grid((unsigned)(p.Sq / 128), (unsigned)p.heads, (unsigned)p.B);
-        hipLaunchKernelGGL((attn_kernel<T, 2, false, 4, 2, false, true, true, true>), grid, dim3(256), 0, s, p);
-      } else {
-        dim3 grid((unsigned)((p.Sq + 63) / 64), (unsigned)p.heads, (unsigned)p.B);
-        hipLaunchKernelGGL((attn_kernel<T, 1, false, 4, 3, false, true, true, true>), grid, dim3(256), 0, s, p);
-      }
-      TANGO_HIP(hipGetLastError());
-      return 0;
-    }
+  const AttnPlan pl = plan_attention(TypeTag<T>::dt, p);
+  if (pl.refusal) TANGO_FAIL(pl.refusal);
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+  // one line per instantiation; h16: a form the planner gives only the 16-bit types, not instantiated for fp32
+#define ATTN_CASE(h16, form, qb, ...) \
+  case attn_key(form, qb):            \
+    if constexpr (!h16 || sizeof(T) == 2) hipLaunchKernelGGL((attn_kernel<T, qb, __VA_ARGS__>), grid, dim3(256), 0, s, p); \
+    break;
+  switch (attn_key(pl.form, pl.qb)) {
+    //        h16    form               QB MASKED NW MINW PB     F8     MSUM   X8     DEFER  KDMA   VDMA
+    ATTN_CASE(false, AF_PLAIN,          1, false, 4, 3,   false, false, false, false, false, false, false)
+    ATTN_CASE(false, AF_PLAIN,          2, false, 4, 3,   false, false, false, false, false, false, false)
+    ATTN_CASE(false, AF_MASKED,         1, true,  4, 3,   false, false, false, false, false, false, false)
+    ATTN_CASE(false, AF_MASKED,         2, true,  4, 3,   false, false, false, false, false, false, false)
+    ATTN_CASE(false, AF_POSBIAS,        1, true,  4, 3,   true,  false, false, false, false, false, false)
+    ATTN_CASE(true,  AF_MSUM,           1, false, 4, 3,   false, false, true,  false, false, false, false)
+    ATTN_CASE(true,  AF_MSUM,           2, false, 4, 3,   false, false, true,  false, false, false, false)
+    ATTN_CASE(true,  AF_DEFER,          1, false, 4, 3,   false, false, false, false, true,  false, false)
+    ATTN_CASE(true,  AF_DEFER,          2, false, 4, 3,   false, false, false, false, true,  false, false)
+    ATTN_CASE(true,  AF_MSUM_DEFER,     1, false, 4, 3,   false, false, true,  false, true,  false, false)
+    ATTN_CASE(true,  AF_MSUM_DEFER,     2, false, 4, 3,   false, false, true,  false, true,  false, false)
+    ATTN_CASE(true,  AF_MSUM_KDMA,      2, false, 4, 3,   false, false, true,  false, false, true,  false)
+    ATTN_CASE(true,  AF_MSUM_KDMA_VDMA, 2, false, 4, 3,   false, false, true,  false, false, true,  true)
+    ATTN_CASE(true,  AF_F8,             1, false, 4, 3,   false, true,  false, false, false, false, false)
+    ATTN_CASE(true,  AF_F8,             2, false, 4, 3,   false, true,  false, false, false, false, false)
+    ATTN_CASE(true,  AF_F8_MSUM,        1, false, 4, 3,   false, true,  true,  false, false, false, false)
+    ATTN_CASE(true,  AF_F8_MSUM,        2, false, 4, 3,   false, true,  true,  false, false, false, false)
+    ATTN_CASE(true,  AF_X8,             1, false, 4, 3,   false, true,  true,  true,  false, false, false)
+    ATTN_CASE(true,  AF_X8,             2, false, 4, 2,   false, true,  true,  true,  false, false, false)
+    default: TANGO_FAIL("attention: the planner chose a form that has no kernel");
   }
-  if (p.pos_bias) {   // text-encoder self-attention (short sequences): one query block per wave
-    dim3 grid((unsigned)((p.Sq + 63) / 64), (unsigned)p.heads, (unsigned)p.B);
-    hipLaunchKernelGGL((attn_kernel<T, 1, true, 4, 3, true>), grid, dim3(256), 0, s, p);
-    TANGO_HIP(hipGetLastError());
-    return 0;
-  }
-  if (p.Sq > 512) {
-    // 4 waves x 32 query rows per workgroup at 3 workgroups/CU.  Wider workgroups (6 or 8 waves sharing one K/V tile
-    // stream, i.e. 1.5-2x fewer L2->LDS bytes per flop) were measured in round 1: 8 waves 10.5 ms vs 9.2 ms per step
-    // at Sq = Skv = 4096; 48 or 64 query rows per wave at 2 waves/SIMD: 9.2 / 10.1 ms -- the kernel is VALU (softmax)
-    // co-limited, not fill-limited.
-    constexpr int QB = 2;
-    dim3 grid((unsigned)((p.Sq + 64 * QB - 1) / (64 * QB)), (unsigned)p.heads, (unsigned)p.B);
-    if (masked) hipLaunchKernelGGL((attn_kernel<T, QB, true, 4, 3>), grid, dim3(256), 0, s, p);
-    else if constexpr (sizeof(T) == 2) {
-      if (p.vt_perm) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, true, false, false, true, true>), grid, dim3(256), 0, s, p);
-      else if (p.fp8_pv && tuning().attn_msum) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, true, true>), grid, dim3(256), 0, s, p);
-      else if (p.fp8_pv) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_msum && tuning().attn_defer) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, true, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_msum && tuning().attn_kdma) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, true, false, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_msum) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_defer) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, false, false, true>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3>), grid, dim3(256), 0, s, p);
-    } else hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3>), grid, dim3(256), 0, s, p);
-  } else if (tuning().attn_qb2_min_wgs > 0 &&
-             (long)((p.Sq + 127) / 128) * p.heads * p.B >= tuning().attn_qb2_min_wgs && p.Sq % 128 == 0) {
-    // short sequences at large batch (levels 1-2 at B >= 8): 32 query rows per wave halve the K / V tile traffic and the workgroup count
-    // once there are enough workgroups to fill the chip anyway (round 4)
-    constexpr int QB = 2;
-    dim3 grid((unsigned)((p.Sq + 64 * QB - 1) / (64 * QB)), (unsigned)p.heads, (unsigned)p.B);
-    if (masked) hipLaunchKernelGGL((attn_kernel<T, QB, true, 4, 3>), grid, dim3(256), 0, s, p);
-    else if constexpr (sizeof(T) == 2) {
-      if (p.fp8_pv && tuning().attn_msum) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, true, true>), grid, dim3(256), 0, s, p);
-      else if (p.fp8_pv) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_msum && tuning().attn_defer) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, true, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_msum) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_defer) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, false, false, true>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3>), grid, dim3(256), 0, s, p);
-    } else hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3>), grid, dim3(256), 0, s, p);
-  } else {
-    constexpr int QB = 1;
-    dim3 grid((unsigned)((p.Sq + 64 * QB - 1) / (64 * QB)), (unsigned)p.heads, (unsigned)p.B);
-    if (masked) hipLaunchKernelGGL((attn_kernel<T, QB, true, 4, 3>), grid, dim3(256), 0, s, p);
-    else if constexpr (sizeof(T) == 2) {
-      if (p.fp8_pv && tuning().attn_msum) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, true, true>), grid, dim3(256), 0, s, p);
-      else if (p.fp8_pv) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_msum && tuning().attn_defer) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, true, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_msum) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, true>), grid, dim3(256), 0, s, p);
-      else if (tuning().attn_defer) hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3, false, false, false, false, true>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3>), grid, dim3(256), 0, s, p);
-    } else hipLaunchKernelGGL((attn_kernel<T, QB, false, 4, 3>), grid, dim3(256), 0, s, p);
-  }
+#undef ATTN_CASE
   TANGO_HIP(hipGetLastError());
   return 0;
 }

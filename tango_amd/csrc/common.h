@@ -389,10 +389,24 @@ struct AttnParams {
                                   // fragments present them), written so by qkv_stat_kernel; the kernel then fetches BOTH tiles by LDS-DMA (attention.hip KDMA + VDMA)
   int fp8_pv = 0;                 // 16-bit engines, unmasked (self-attention) sites: P and V as e4m3 on the fp8 MFMA (attention.hip); 2 = the MX instruction (128 keys per MFMA, unit scales)
 };
+// the kernel form launch_attention() runs: a pure host function of (dtype, p, tuning()) that touches no memory (rules: attention.hip)
+enum AttnForm { AF_PLAIN, AF_MASKED, AF_POSBIAS, AF_MSUM, AF_DEFER, AF_MSUM_DEFER, AF_MSUM_KDMA, AF_MSUM_KDMA_VDMA, AF_F8, AF_F8_MSUM, AF_X8 };
+struct AttnPlan {
+  AttnForm form = AF_PLAIN;
+  int qb = 1;                     // blocks of 16 query rows per wave: 1 or 2
+  int minw = 3;                   // waves per SIMD the kernel is bounded for: 3, or 2 (x8 at qb 2)
+  unsigned grid[3] = {0, 0, 0};   // (query blocks of 64 qb rows, heads, B); the block is 256 threads
+  const char* refusal = nullptr;  // why launch_attention() refuses these arguments, or null
+};
+AttnPlan plan_attention(int dtype, const AttnParams& p);
+std::string attn_plan_name(const AttnPlan& pl);   // what tango_debug_attention_route answers: "qb2:msum+kdma+vdma", "qb1:masked", ...
+// a UNet self-attention site (Sq = Skv = ldvt = S, no bias) asked `want_fp8` (tango_config::unet_attn_fp8): the fp8 form it can run, and whether it can
+// read a vt_perm V^T (the producer may then write one) -- by the planner's own refusals
+struct AttnSite { int fp8_pv; bool vt_perm_ok; };
+AttnSite plan_attention_site(int dtype, int B, int heads, int S, int want_fp8);
 int launch_attention(int dtype, const AttnParams& p, hipStream_t s);
 // position of token s of a sequence in a vt_perm V^T: inside its block of 32, key 16 hi + 4 g + r sits at 8 g + 4 hi + r
 __host__ __device__ inline int vt_perm_pos(int s) { return (s & ~31) | ((s & 12) << 1) | ((s & 16) >> 2) | (s & 3); }
-bool attention_vt_perm_ok(int dtype, const AttnParams& p);   // this site can read a vt_perm V^T (the producer may then write one)
 
 // ---- fused cross-attention block (xattn.hip): y = x + to_out(softmax(to_q(LayerNorm(x)) K^T / 8 + bias) V) + b_out ----
 struct XAttnParams {

@@ -381,16 +381,11 @@ struct Builder {
     TView qkv = alloc(rows_p, 2 * C);               // [q | k]; v goes transposed into vt [B][C][HW]
     void* vt = A.alloc((size_t)rows_p * C * esz);
     GOpt nb; nb.use_bias = false;
-    const int attn_fp8 = (E.cfg.unet_attn_fp8 != 0 && dt != DT_F32 && HW % 64 == 0) ? ((E.cfg.unet_attn_fp8 == 2 && HW % 128 == 0) ? 2 : 1) : 0;
+    const AttnSite site = plan_attention_site(dt, Bp, w.heads, HW, E.cfg.unet_attn_fp8);
+    const int attn_fp8 = site.fp8_pv;
     // round 6: where the projection runs on the activation-stationary kernel AND the attention site can fetch by LDS-DMA, v^T is written with its
     // keys in the attention kernel's fragment order (AttnParams::vt_perm): producer and consumer agree here, in one place
-    int vperm = 0;
-    {
-      AttnParams ap;
-      ap.q = nullptr; ap.k = nullptr; ap.vt = nullptr; ap.o = nullptr; ap.ldq = ap.ldk = ap.ldo = 0; ap.ldvt = HW;
-      ap.bias = nullptr; ap.B = Bp; ap.heads = w.heads; ap.Sq = HW; ap.Skv = HW; ap.scale = 0.125f; ap.fp8_pv = attn_fp8;
-      vperm = tuning().attn_vdma && attention_vt_perm_ok(dt, ap) ? 1 : 0;
-    }
+    int vperm = tuning().attn_vdma && site.vt_perm_ok ? 1 : 0;
     if (!qkv_stat(h, rows_p, w, qkv, vt, HW, vperm)) {
       // GEMM-route producers (levels 1-2; level 0 below the activation-stationary kernel's row threshold): every EPI_VT epilogue can write the
       // permuted order as well (TANGO_ATTN_VDMA=2, the default; 1 = only qkv_stat_kernel does)

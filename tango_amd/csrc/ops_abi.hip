@@ -784,6 +784,20 @@ int tango_op_attention_ex(int dt, const float* q, const float* k, const float* v
   return 0;
 }
 
+const char* tango_debug_attention_route(int dt, int B, int heads, int Sq, int Skv, int masked, int pos_bias, int fp8_pv, int vt_perm) {
+  // the kernel tango_op_attention[_ex] (same leading dimensions) or the engine runs for this site under the current switches, and its grid; or the refusal
+  const float* const fd = (const float*)kRouteDummy;
+  AttnParams p;
+  p.q = p.k = p.vt = kRouteDummy; p.o = kRouteDummy; p.ldq = p.ldk = p.ldo = heads * 64; p.ldvt = (Skv + 7) / 8 * 8;
+  p.bias = masked ? fd : nullptr; p.pos_bias = pos_bias ? fd : nullptr; p.B = B; p.heads = heads; p.Sq = Sq; p.Skv = Skv; p.scale = 0.125f;
+  p.fp8_pv = fp8_pv; p.vt_perm = vt_perm;
+  const AttnPlan pl = plan_attention(dt, p);
+  static thread_local std::string out;
+  out = pl.refusal ? pl.refusal
+                   : attn_plan_name(pl) + " " + std::to_string(pl.grid[0]) + "x" + std::to_string(pl.grid[1]) + "x" + std::to_string(pl.grid[2]);
+  return out.c_str();
+}
+
 int tango_op_xattn_block(int dt, const float* x, const float* gamma, const float* beta, const float* wq, const float* k, const float* v,
                          const float* bias, const float* wo, const float* bo, float* out, int B, int HW, int L, float eps, void* stream) {
   // y = x + to_out(softmax(to_q(LayerNorm(x)) K^T / 8 + bias) V) + bo in the fused kernel (xattn.hip); C = 320, 5 heads.

@@ -35,11 +35,13 @@ struct Tuning {
   bool no_cfg_shared;       // TANGO_NO_CFG_SHARED=1    A/B: the CFG-shared prefix of a guidance step (conv_in ... first self-attention once for both halves) off (round 5)
   bool stream_spec;         // TANGO_STREAM_SPEC=0|1     lin_stream_kernel: compile-time GEGLU + folded-LayerNorm epilogue for the level-0 projection (default on) (round 5)
   int attn_qb2_min_wgs;     // TANGO_ATTN_QB2_MIN_WGS=n attention with Sq <= 512: 32 query rows per wave once that still leaves n workgroups (default 512: level-2 self-attention at B=32 0.319 -> 0.247 ms, profiles/r4_c14_attn_qb2_ab_b32.txt); 0 = never (round 4)
+                            //                          plan_attention (attention.hip) decides it before the form, for every dtype and for masked sites too; needs Sq % 128 == 0; pos_bias and MX fp8 sites never read it
   bool no_halo_narrow;      // TANGO_NO_HALO_NARROW=1   A/B: conv_out (N <= 32) back on the 256 x 16 tile kernel instead of the halo kernel's 256 x 32 tile (round 6)
   int gn_slab;              // TANGO_GN_SLAB=0|1        GroupNorm of <= 256-row samples with vector-aligned groups (UNet levels 2-3): one workgroup keeps a rows x 4-group slab in registers -- one launch, one read, one write (round 6)
   int gn_small_mb;          // TANGO_GN_SMALL_MB=n      GroupNorm: the one-launch (sample, group)-per-workgroup kernel up to n MiB of input (default 8)
   int wide_pers;            // TANGO_WIDE_PERS=n        256 x 320 GEMM: the persistent form (next tile's first chunk prefetched behind the epilogue) from n tiles per CU on (default 2: linears of a B = 32 step 20.0 -> 19.7 ms, bit-identical results, profiles/r4_c16_wide_pers_ab_b32.txt); 0 = never (round 4)
   bool attn_msum;           // TANGO_ATTN_MSUM=0|1      unmasked 16-bit attention: softmax row sums on the matrix pipe (attention.hip MSUM; default on: S = 4096 site 8.00 -> 7.79 ms at B = 32, profiles/r4_c17_attn_msum_ab_b32.txt) (round 4)
+                            //                          precedence in plan_attention: masked, pos_bias and fp32 sites read none of MSUM / DEFER / KDMA, MX fp8 (x8) and vt_perm sites always sum on the matrix pipe; fp8 = 1 reads this switch only
   int duo_maxk;             // TANGO_DUO_MAXK=k         gemm_duo_kernel (256 x 160, two workgroups per CU) takes linears with K <= k; 0 = out of the dispatch; unset = the measured rule in gemm_duo_ok() (round 4)
   int duo_min_tiles;        // TANGO_DUO_MIN_TILES=n    ... that have at least n tiles of 256 x 160
   int duo_mask;             // TANGO_DUO_MASK=bits      ... of these classes: 1 plain, 2 GEGLU, 4 folded LayerNorm (incl. transposed V), 8 folded LayerNorm + GEGLU
@@ -51,10 +53,14 @@ struct Tuning {
   int gn_proj_stat;         // TANGO_GN_PROJ_STAT=0|1   level-0 GroupNorm -> proj_in: statistics pass + the activation-stationary kernel normalising on its way in (round 6); 0 = GroupNorm kernel + GEMM
   bool gn_fold;             // TANGO_GN_FOLD=1          GroupNorm -> proj_in as ONE GEMM with per-sample folded weights at levels 0-1 (round 6: built, within tolerance, measured +-0.0 ms per step: off)
   int attn_kdma;            // TANGO_ATTN_KDMA=0|1      unmasked 16-bit attention with Sq > 512: the K tile by LDS-DMA instead of through VGPRs (round 6)
+                            //                          only with TANGO_ATTN_MSUM=1 (without it: no effect) and TANGO_ATTN_DEFER=0 (DEFER wins); a vt_perm site fetches K by LDS-DMA whatever this says
   int attn_vdma;            // TANGO_ATTN_VDMA=0|1|2    self-attention with Sq > 512: v^T written in fragment order by the producer, K AND V^T tiles by LDS-DMA (round 6);
                             //                          1 = only where qkv_stat_kernel produces it (level 0), 2 = the GEMM routes' transposed epilogues as well (level 1)
+                            //                          read by the engine alone, where the producer is chosen (Builder::transformer): a site handed a vt_perm V^T runs msum+kdma+vdma and reads no other switch
   int attn_defer;           // TANGO_ATTN_DEFER=0|1     unmasked 16-bit attention: move the running softmax maximum only when a tile exceeds it by more than 2^8 (round 6); 0 = exact lazy rescale
+                            //                          with TANGO_ATTN_MSUM=1 the form msum+defer, which has no LDS-DMA K tile: DEFER=1 silently drops TANGO_ATTN_KDMA; ignored at vt_perm and fp8 sites
   int attn_x8_qb;           // TANGO_ATTN_X8_QB=1|2     MX fp8 P.V attention (unet_attn_fp8 = 2): 16 query rows per wave at three waves per SIMD, or 32 at two (round 6)
+                            //                          32 rows also need Sq % 128 == 0; the only switch an MX fp8 site reads
   int conv_tall;            // TANGO_CONV_TALL=0|1      3x3 wide conv on the 512-pixel x 160-channel form of the tile where the halo fits (round 6: half the weight DMA per MFMA)
   int wide_pipe;            // TANGO_WIDE_PIPE=0|1|2    256 x 320 GEMM: in-wave software pipeline (fragments of item i+1 requested under the MFMAs of item i) instead of the ping-pong read / multiply parts; 1 = staggered halves, two barriers per item, 2 = all waves in step, one barrier per item (round 6: both slower than ping-pong on the GEMMs)
   bool ups_phases;          // TANGO_UPS_PHASES=0|1     nearest-x2 upsampler convs of the 16-bit engines as four 2x2-tap phase convolutions on the source grid (conv_wide.hip PH: 4/9 of the flops); 0 = the nine-tap gather form (A/B).  Decided when a plan is built
