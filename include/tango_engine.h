@@ -440,13 +440,23 @@ int tango_op_attention_ex(int dtype, const float* q, const float* k, const float
    k, v [B*L, 320] = to_k / to_v of the text; bias [B, L] additive or NULL */
 int tango_op_xattn_block(int dtype, const float* x, const float* gamma, const float* beta, const float* wq, const float* k, const float* v,
                          const float* bias, const float* wo, const float* bo, float* out, int B, int HW, int L, float eps, void* stream);
+/* The four tango_op_sched_* hooks below are one implementation and refuse what tango_engine_denoise refuses for the row of their step
+ * (unknown rule, coefficient width against the rule, step noise or clip with the multistep rule, table column 11 not 0 / 1, a row
+ * order the loop index does not allow, masked arguments that do not go together, rescale outside [0, 1], guidance entries that are
+ * negative or not finite), besides sizes <= 0 and missing latents / model_out_nchw / coef. */
+
+/* one fused CFG + DDPM (rule 0) / DDIM (rule 1) step on caller-owned buffers: latents [B, C, HW] fp32 in/out, model_out_nchw
+ * [B2, C, HW] fp32, noise DEVICE [B, C, HW] or NULL (Philox, seed 0), coef8 HOST [8] (the row of this step), clip / clip_range as
+ * tango_denoise_args_t.clip_sample / clip_sample_range.  Synchronises. */
 int tango_op_sched_step(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int HW,
                         int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, void* stream);
 
 /* one fused CFG + multistep DPM-Solver step (TANGO_RULE_DPM_MULTISTEP) at loop index `step` on caller-owned buffers: latents
  * [B, C, HW] fp32 in/out, model_out_nchw [B2, C, HW] fp32 (B2 = 2B, [uncond; cond], when cfg), ring DEVICE [3][B][C][HW] fp32
  * (the converted outputs of steps step - 1 and step - 2 in slots (step + 2) % 3 and (step + 1) % 3; this step's goes to
- * step % 3), coef16 HOST [step + 1][16] (the table up to this step), algo 0 DPM-Solver++ / 1 DPM-Solver.  Synchronises. */
+ * step % 3), coef16 HOST [step + 1][16] (the table up to this step), algo 0 DPM-Solver++ / 1 DPM-Solver (the argument
+ * decides, whatever column 11 of the table says; column 11 of row 0 must still be 0 or 1, and the order column exactly 1, 2 or 3).
+ * Synchronises. */
 int tango_op_sched_multistep(float* latents, const float* model_out_nchw, float* ring, const float* coef16, int step, int B, int C,
                              int HW, int cfg, float guidance, int pred_type, int algo, void* stream);
 

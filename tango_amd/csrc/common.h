@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 namespace tango {
 
@@ -437,43 +438,63 @@ int launch_rowbias_add(int dtype, const void* x, int64_t ldx, const float* cvec,
 // row softmax (in place) used by the VAE single-head 512-d attention: x[rows][cols] *= scale; softmax
 int launch_softmax_rows(int dtype, void* x, int64_t ld, int rows, int cols, float scale, hipStream_t s);
 
-// ---- elementwise / layout ----
+// ---- scheduler update: the denoise loop's own kernels (sched.hip) ----
+// The parameter block of one denoise call, in DEVICE memory (the kernels take one pointer to it: a captured step does not depend on the
+// call's pointers and scalars).  Every default is the value the kernels treat as absent: a site that builds one sets only what it has
+// something to say about.  All update kernels read lat .. pred_type and num_steps; sched_step_kernel (rules 0 / 1) rule, clip,
+// clip_range, noise (null: seed, sample_offset); sched_multistep_kernel (rule 2) ring, coef_w, algo; the masked variants and
+// inpaint_blend0 x0, mask, blend_coef, blend_noise (null: seed, sample_offset); the guided variants and the statistics kernels gtable,
+// rescale, gpart, gscale (`guidance` is then not read).
 struct SchedParams {
-  float* lat;            // [B,8,256,16] fp32 NCHW, updated in place
-  const float* eps;      // UNet output fp32 NHWC [B2, HW, C] (B2 = 2B when cfg)
-  void* xin;             // next UNet input, T, NHWC [B2, HW, Cpad]
-  int xin_ld;
-  const float* noise;    // [steps][B*C*HW] or null -> philox
-  const float* coef;     // [steps][8] device
-  const int* step_ptr;
-  int B, C, HW;
-  int cfg;               // 1: eps holds [uncond; cond]
-  float guidance;
-  int pred_type;         // 0 epsilon, 1 sample, 2 v_prediction
-  int rule;              // 0 DDPM, 1 DDIM
-  int clip; float clip_range;
-  unsigned long long seed;
-  int sample_offset;     // global sample index of local sample 0 (multi-GPU invariant noise)
+  float* lat = nullptr;            // [B,8,256,16] fp32 NCHW, updated in place
+  const float* eps = nullptr;      // UNet output fp32 NHWC [B2, HW, C] (B2 = 2B when cfg)
+  void* xin = nullptr;             // next UNet input, T, NHWC [B2, HW, Cpad]
+  int xin_ld = 0;
+  const float* noise = nullptr;    // [steps][B*C*HW] or null -> philox
+  const float* coef = nullptr;     // [steps][coef_w] device
+  const int* step_ptr = nullptr;
+  int B = 0, C = 0, HW = 0;
+  int cfg = 0;                     // 1: eps holds [uncond; cond]
+  float guidance = 0.0f;
+  int pred_type = 0;               // 0 epsilon, 1 sample, 2 v_prediction
+  int rule = 0;                    // 0 DDPM, 1 DDIM
+  int clip = 0; float clip_range = 1.0f;
+  unsigned long long seed = 0;
+  int sample_offset = 0;           // global sample index of local sample 0 (multi-GPU invariant noise)
   // multistep rule (rule 2, sched_multistep_kernel): fp32 ring of the converted model outputs of the last three steps,
   // [3][B][C][HW] NCHW, slot = step % 3; `coef` rows are `coef_w` (16) floats wide (include/tango_engine.h)
-  float* ring;
-  int coef_w;
-  int algo;              // 0 DPM-Solver++ (x0 form), 1 DPM-Solver (eps form)
+  float* ring = nullptr;
+  int coef_w = 8;
+  int algo = 0;                    // 0 DPM-Solver++ (x0 form), 1 DPM-Solver (eps form)
   // masked (inpainting) kernels only (include/tango_engine.h tango_denoise_args_t.known_latents): after the update of loop index i,
   // when i + 1 < num_steps, x = (bc[i+1][0] * x0 + bc[i+1][1] * n_{i+1}) * m + (1 - m) * x
-  const float* x0;          // [B][C][HW] known latents
-  const float* mask;        // [B][HW]
-  const float* blend_coef;  // [steps][2] device: sqrt(abar_t), sqrt(1 - abar_t)
-  const float* blend_noise; // [steps][B*C*HW] or null -> philox, step word | 0x80000000
-  int num_steps;
+  const float* x0 = nullptr;          // [B][C][HW] known latents
+  const float* mask = nullptr;        // [B][HW]
+  const float* blend_coef = nullptr;  // [steps][2] device: sqrt(abar_t), sqrt(1 - abar_t)
+  const float* blend_noise = nullptr; // [steps][B*C*HW] or null -> philox, step word | 0x80000000
+  int num_steps = 1;
   // guided kernels only (include/tango_engine.h tango_guidance_args_t): the guidance scale of sample b at loop index i is
   // gtable[i * B + b] (`guidance` above is not read), and with rescale = phi > 0 the guided output is pulled towards the conditional
   // output's per-sample standard deviation: v = phi * (cfg * gscale[b]) + (1 - phi) * cfg, gscale[b] = std(cond) / std(cfg) of this step
-  const float* gtable;      // [steps][B] device
-  float rescale;            // phi in [0, 1]; 0: no statistics are taken and gscale is not read
-  double* gpart;            // [B][ceil(HW / kGuideChunk)][4] partial sums of guidance_stats_kernel (written and read every step)
-  float* gscale;            // [B] written by guidance_scale_kernel
+  const float* gtable = nullptr;      // [steps][B] device
+  float rescale = 0.0f;               // phi in [0, 1]; 0: no statistics are taken and gscale is not read
+  double* gpart = nullptr;            // [B][ceil(HW / kGuideChunk)][4] partial sums of guidance_stats_kernel (written and read every step)
+  float* gscale = nullptr;            // [B] written by guidance_scale_kernel
 };
+static_assert(std::is_trivially_copyable<SchedParams>::value && sizeof(SchedParams) == 200,
+              "SchedParams is memcpy'd to the device and copied by value in the kernels: its layout is fixed");
+
+// The update step's arguments as the host sees them: what a denoise call (rows [0, num_rows)) and a one-step test hook (row `step` alone)
+// may pass.  Pointers are only asked whether they are null, except `coef` (HOST [num_rows][coef_w]) and `table` (HOST [table_rows][batch]).
+struct SchedArgs {
+  int rule = 0; const float* coef = nullptr; int coef_w = 8, num_rows = 0;
+  int row0 = 0, row1 = 0; bool noise = false, clip = false;   // the multistep rows whose order is checked; step noise given, clip_sample on
+  const void *known = nullptr, *mask = nullptr, *blend_coef = nullptr, *blend_noise = nullptr;
+  bool guided = false, cfg_on = false;       // the guidance part is given; the call runs the [uncond; cond] batch
+  const float* table = nullptr; int table_rows = 0, batch = 0; float rescale = 0.0f;
+};
+// the refusal without a prefix (the caller says "denoise: " or its own name), or nullptr.  Host only, no device needed.
+const char* sched_args_refusal(const SchedArgs& a);
 // `dev_params` is a DEVICE copy of SchedParams; the grid covers max_positions >= B*HW (one thread per latent position).
 // `rule` (host copy of the block's rule) picks the kernel: 0 / 1 sched_step_kernel, 2 sched_multistep_kernel; `masked` their
 // inpainting variants (the blend for the next loop index fused after the update); `guided` the variants that read the guidance
@@ -493,7 +514,7 @@ int launch_step_inc(int* step_ptr, hipStream_t s);
 // test hook: the N(0,1) draws of sched_step at loop index `step` -> out fp32 [B][C][HW] (`blend`: the masked loop's blend noise)
 int launch_philox_normal(float* out, int B, int C, int HW, int step, unsigned long long seed, int sample_offset, hipStream_t s,
                          bool blend = false);
-// fused latent encode of audio-to-audio editing (elementwise.hip latent_encode_kernel): moments fp32 [moments_batch][2C][HW] ->
+// fused latent encode of audio-to-audio editing (sched.hip latent_encode_kernel): moments fp32 [moments_batch][2C][HW] ->
 // xt (and z0 when not null) fp32 [B][C][HW]; eps / noise injected [B][C][HW] or null -> Philox.  One workgroup per sample, any HW.
 int launch_latent_encode(const float* moments, int moments_batch, float* z0, float* xt, const float* eps, const float* noise, int B,
                          int C, int HW, float scale, float clip_trigger, float clip_range, float sa, float sb, int posterior_mode,
@@ -502,6 +523,7 @@ int launch_latent_encode(const float* moments, int moments_batch, float* z0, flo
 int launch_philox_normal_encode(float* out, int B, int C, int HW, int which, unsigned long long seed, int sample_offset,
                                 hipStream_t s);
 
+// ---- elementwise / layout (elementwise.hip) ----
 // latents fp32 NCHW [B,C,HW] -> T NHWC [rep*B, HW, ld] (replicated `rep` times along batch), zero-pads C..ld? no: writes C channels
 int launch_nchw_to_nhwc(int dtype, const float* src, void* dst, int64_t ld, int B, int C, int HW, int rep, float scale, hipStream_t s);
 // T NHWC [B,HW,ld] (first C channels) -> fp32 NCHW

@@ -1464,41 +1464,25 @@ UNetMode Engine::unet_mode_for(int B2, int n_short, bool cfg_on, bool two_chains
   return cfg_on && cfg_shared_ok(B2, n_short) ? UNetMode::CfgShared : UNetMode::Whole;
 }
 
-// the argument checks of denoise(): callers read these messages
-static int check_denoise_args(const tango_denoise_args_t& a) {
-  if (a.num_steps <= 0) TANGO_FAIL("denoise: num_steps must be positive");
-  if (a.rule != TANGO_RULE_DDPM && a.rule != TANGO_RULE_DDIM && a.rule != TANGO_RULE_DPM_MULTISTEP) TANGO_FAIL("denoise: unknown rule");
-  const bool ms = a.rule == TANGO_RULE_DPM_MULTISTEP;
-  const int coef_w = a.coef_width ? a.coef_width : 8;
-  if (coef_w != (ms ? 16 : 8)) TANGO_FAIL(ms ? "denoise: the multistep rule takes 16-float coefficient rows (coef_width 16)"
-                                             : "denoise: DDPM / DDIM take 8-float coefficient rows (coef_width 0 or 8)");
-  if (ms && a.noise) TANGO_FAIL("denoise: the multistep rule is deterministic: noise must be NULL");
-  if (ms && a.clip_sample) TANGO_FAIL("denoise: clip_sample is not supported by the multistep rule");
-  if (ms && a.coef[11] != 0.0f && a.coef[11] != 1.0f) TANGO_FAIL("denoise: multistep table column 11 (algorithm) must be 0 or 1");
-  if (ms) {
-    for (int i = 0; i < a.num_steps; ++i) {          // a row never reads a history slot this loop has not written
-      const float o = a.coef[(size_t)i * 16 + 10];
-      if (!(o == 1.0f || (o == 2.0f && i >= 1) || (o == 3.0f && i >= 2))) TANGO_FAIL("denoise: multistep table row with a bad order");
-    }
-  }
-  const bool mk = a.known_latents != nullptr;
-  if (mk != (a.latent_mask != nullptr)) TANGO_FAIL("denoise: known_latents and latent_mask go together");
-  if (mk && !a.blend_coef) TANGO_FAIL("denoise: a masked call needs blend_coef [num_steps][2]");
-  if (!mk && (a.blend_coef || a.blend_noise)) TANGO_FAIL("denoise: blend_coef / blend_noise need known_latents and latent_mask");
+// the argument checks of denoise(), every row of the call's tables: callers read these messages (sched_args_refusal states them)
+static int check_denoise_args(const tango_denoise_args_t& a, const tango_guidance_args_t* g) {
+  SchedArgs c;
+  c.rule = a.rule; c.coef = a.coef; c.coef_w = a.coef_width ? a.coef_width : 8; c.num_rows = c.row1 = a.num_steps;
+  c.noise = a.noise != nullptr; c.clip = a.clip_sample != 0; c.guided = g != nullptr;
+  c.known = a.known_latents; c.mask = a.latent_mask; c.blend_coef = a.blend_coef; c.blend_noise = a.blend_noise;
+  if (g) { c.cfg_on = a.guidance_scale > 1.0f || g->table; c.rescale = g->rescale; c.table = g->table; c.table_rows = a.num_steps; c.batch = a.batch; }
+  if (const char* why = sched_args_refusal(c)) TANGO_FAIL(std::string("denoise: ") + why);
   return 0;
 }
 
-// the checks of a guided call (tango_guidance_args_t) on top of check_denoise_args(): callers read these messages too
-static int check_guidance_args(const tango_denoise_args_t& a, const tango_guidance_args_t& g) {
-  if (!(g.rescale >= 0.0f && g.rescale <= 1.0f)) TANGO_FAIL("denoise: guidance rescale must be in [0, 1]");
-  if (g.rescale > 0.0f && !g.table && !(a.guidance_scale > 1.0f))
-    TANGO_FAIL("denoise: guidance rescale needs classifier-free guidance (guidance_scale > 1 or a guidance table)");
-  if (g.table) {
-    if (a.batch <= 0) TANGO_FAIL("denoise: a guidance table needs batch > 0");
-    const size_t n = (size_t)a.num_steps * (size_t)a.batch;
-    for (size_t i = 0; i < n; ++i)
-      if (!(g.table[i] >= 0.0f) || std::isinf(g.table[i])) TANGO_FAIL("denoise: guidance table entries must be finite and >= 0");
-  }
+// grow a device buffer the engine owns beside its plans to `need` units of `unit` bytes.  Outside any capture; every earlier use of
+// the old buffer (replays in flight on any stream) completes before it is freed.
+template <typename T>
+static int grow_device_buffer(T** buf, size_t* have, size_t need, size_t unit, const char* fail) {
+  if (need <= *have) return 0;
+  if (*buf) { TANGO_HIP(hipDeviceSynchronize()); (void)hipFree(*buf); *buf = nullptr; *have = 0; }
+  if (hipMalloc((void**)buf, need * unit) != hipSuccess) { *buf = nullptr; TANGO_FAIL(fail); }
+  *have = need;
   return 0;
 }
 
@@ -1538,8 +1522,7 @@ int Engine::capture_steps(const UNetPlan& P, int rule, bool masked, bool guided,
 }
 
 int Engine::denoise(const tango_denoise_args_t& a, const tango_guidance_args_t* g, hipStream_t s) {
-  TANGO_TRY(check_denoise_args(a));
-  if (g) TANGO_TRY(check_guidance_args(a, *g));
+  TANGO_TRY(check_denoise_args(a, g));
   // a table, or a rescale, takes the guided update kernels; a null / all-default block is today's call
   const bool gd = g && (g->table || g->rescale > 0.0f);
   const bool ms = a.rule == TANGO_RULE_DPM_MULTISTEP;
@@ -1558,31 +1541,21 @@ int Engine::denoise(const tango_denoise_args_t& a, const tango_guidance_args_t* 
   const int HW = H * cfg.latent_w;
   const int C = cfg.unet_in_channels;
   const size_t ring_need = (size_t)3 * B * C * HW;    // elements: a call with fewer, taller samples may need more than an earlier one
-  if (ms && ring_need > ring_elems) {
-    // outside any capture; every earlier use of the old ring (replays in flight on any stream) completes before it is freed
-    if (d_ring) { TANGO_HIP(hipDeviceSynchronize()); (void)hipFree(d_ring); d_ring = nullptr; ring_elems = 0; }
-    if (hipMalloc(&d_ring, ring_need * 4) != hipSuccess) { d_ring = nullptr; TANGO_FAIL("denoise: hipMalloc of the multistep ring failed"); }
-    ring_elems = ring_need;
-  }
+  if (ms) TANGO_TRY(grow_device_buffer(&d_ring, &ring_elems, ring_need, 4, "denoise: hipMalloc of the multistep ring failed"));
   const size_t gt_bytes = ((size_t)a.num_steps * B * 4 + 255) & ~(size_t)255, gs_bytes = ((size_t)B * 4 + 255) & ~(size_t)255;
   const size_t guide_need = gt_bytes + gs_bytes + (size_t)B * guidance_chunks(HW) * 4 * 8;
-  if (gd && guide_need > guide_bytes) {      // like the ring: outside any capture, after every earlier use of the old buffer
-    if (d_guide) { TANGO_HIP(hipDeviceSynchronize()); (void)hipFree(d_guide); d_guide = nullptr; guide_bytes = 0; }
-    if (hipMalloc((void**)&d_guide, guide_need) != hipSuccess) { d_guide = nullptr; TANGO_FAIL("denoise: hipMalloc of the guidance workspace failed"); }
-    guide_bytes = guide_need;
-  }
-  SchedParams sp;
+  if (gd) TANGO_TRY(grow_device_buffer(&d_guide, &guide_bytes, guide_need, 1, "denoise: hipMalloc of the guidance workspace failed"));
+  SchedParams sp;      // what this call has nothing to say about keeps the block's "absent" defaults
   sp.lat = a.latents; sp.eps = P->eps; sp.xin = P->xin; sp.xin_ld = 8;
   sp.noise = a.noise; sp.coef = d_coef; sp.step_ptr = d_step;
   sp.B = B; sp.C = C; sp.HW = HW; sp.cfg = cfg_on ? 1 : 0; sp.guidance = a.guidance_scale;
   sp.pred_type = a.prediction_type; sp.rule = a.rule; sp.clip = a.clip_sample; sp.clip_range = a.clip_sample_range;
-  sp.seed = a.seed; sp.sample_offset = a.sample_offset;
-  sp.ring = ms ? d_ring : nullptr; sp.coef_w = coef_w; sp.algo = ms ? (int)a.coef[11] : 0;
-  sp.x0 = a.known_latents; sp.mask = a.latent_mask; sp.blend_coef = mk ? d_bcoef : nullptr; sp.blend_noise = mk ? a.blend_noise : nullptr;
-  sp.num_steps = a.num_steps;
-  sp.gtable = gd ? (const float*)d_guide : nullptr; sp.rescale = gd ? g->rescale : 0.0f;
-  sp.gscale = gd ? (float*)(d_guide + gt_bytes) : nullptr; sp.gpart = gd ? (double*)(d_guide + gt_bytes + gs_bytes) : nullptr;
+  sp.seed = a.seed; sp.sample_offset = a.sample_offset; sp.num_steps = a.num_steps;
+  if (ms) { sp.ring = d_ring; sp.coef_w = coef_w; sp.algo = (int)a.coef[11]; }
+  if (mk) { sp.x0 = a.known_latents; sp.mask = a.latent_mask; sp.blend_coef = d_bcoef; sp.blend_noise = a.blend_noise; }
   if (gd) {
+    sp.gtable = (const float*)d_guide; sp.rescale = g->rescale;
+    sp.gscale = (float*)(d_guide + gt_bytes); sp.gpart = (double*)(d_guide + gt_bytes + gs_bytes);
     // a rescale without a table: the scalar in every entry (the guided kernels read the table only)
     std::vector<float> flat;
     if (!g->table) flat.assign((size_t)a.num_steps * B, a.guidance_scale);
@@ -2199,7 +2172,7 @@ const char* tango_debug_denoise_guided_check(const tango_denoise_args_t* a, cons
   static thread_local std::string msg;
   msg.clear();
   if (!a) return "denoise: null args";
-  if (tango::check_denoise_args(*a) != 0 || (g && tango::check_guidance_args(*a, *g) != 0)) msg = tango_last_error();
+  if (tango::check_denoise_args(*a, g) != 0) msg = tango_last_error();
   return msg.c_str();
 }
 int tango_engine_unet_forward_h(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,

@@ -832,62 +832,122 @@ int tango_op_xattn_block(int dt, const float* x, const float* gamma, const float
   return 0;
 }
 
-int tango_op_sched_step(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int HW,
-                        int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  Scratch sc;
-  const int B2 = cfg ? 2 * B : B;
+// One update step at loop index `step` on caller-owned fp32 buffers: the body of the four tango_op_sched_* hooks, each of which sets
+// what differs from these defaults.  Pointers as in include/tango_engine.h (coef / blend_coef / guidance_row / scale_out HOST).
+struct SchedOp {
+  const char* who = "op_sched";
+  float* latents = nullptr; const float* model_out_nchw = nullptr; const float* noise = nullptr; float* ring = nullptr;
+  const float* coef = nullptr; int coef_width = 8, step = 0, num_steps = 1;      // [num_steps][coef_width]
+  int algo = -1;                    // multistep rule: the algorithm; -1 reads it from column 11 of the table, as the engine does
+  bool need_mask = false;           // the masked arguments are required, not optional
+  const float *known_latents = nullptr, *latent_mask = nullptr, *blend_coef = nullptr, *blend_noise = nullptr;
+  uint64_t seed = 0; int sample_offset = 0;
+  int B = 0, C = 0, HW = 0, cfg = 0, pred_type = 0, rule = 0, clip = 0; float guidance = 0.0f, clip_range = 1.0f;
+  bool guided = false;              // the guided kernels, with guidance_row / rescale / scale_out as tango_op_sched_guided says
+  const float* guidance_row = nullptr; float rescale = 0.0f; float* scale_out = nullptr; void* stream = nullptr;
+};
+
+static int op_sched(const SchedOp& o) {
+  const std::string w(o.who);
+  const int B = o.B, C = o.C, HW = o.HW, step = o.step;
+  if (B <= 0 || C <= 0 || HW <= 0 || o.num_steps <= 0 || step < 0 || step >= o.num_steps) TANGO_FAIL(w + ": bad sizes");
+  if (!o.latents || !o.model_out_nchw || !o.coef) TANGO_FAIL(w + ": latents, model_out_nchw and coef are required");
+  if (o.need_mask && !(o.known_latents && o.latent_mask && o.blend_coef)) TANGO_FAIL(w + ": known_latents, latent_mask and blend_coef are required");
+  if (o.guided && (!o.cfg || !o.guidance_row)) TANGO_FAIL(w + ": the guided kernels need cfg = 1 and a guidance row");
+  const bool ms = o.rule == TANGO_RULE_DPM_MULTISTEP;
+  if (ms && !o.ring) TANGO_FAIL(w + ": the multistep rule takes a ring");
+  SchedArgs c;                      // the engine's own rules, on the row of this step
+  c.rule = o.rule; c.coef = o.coef; c.coef_w = o.coef_width; c.num_rows = o.num_steps; c.row0 = step; c.row1 = step + 1;
+  c.noise = o.noise != nullptr; c.clip = o.clip != 0;
+  c.known = o.known_latents; c.mask = o.latent_mask; c.blend_coef = o.blend_coef; c.blend_noise = o.blend_noise;
+  c.guided = o.guided; c.cfg_on = o.cfg != 0; c.table = o.guidance_row; c.table_rows = 1; c.batch = B; c.rescale = o.rescale;
+  if (const char* why = sched_args_refusal(c)) TANGO_FAIL(w + ": " + why);
+  const bool mk = o.known_latents != nullptr; const int B2 = o.cfg ? 2 * B : B;
+  hipStream_t s = (hipStream_t)o.stream; Scratch sc;
   float* eps = (float*)sc.get((size_t)B2 * HW * C * 4);
-  float* xin = (float*)sc.get((size_t)B2 * HW * 8 * 4);
-  float* dcoef = (float*)sc.get(8 * 4);
+  float* xin = (float*)sc.get((size_t)B2 * HW * C * 4);
+  float* dcoef = (float*)sc.get((size_t)o.num_steps * o.coef_width * 4);
   int* dstep = (int*)sc.get(256);
-  if (!eps || !xin || !dcoef || !dstep) TANGO_FAIL("op_sched_step: alloc");
-  TANGO_TRY(launch_nchw_to_nhwc(DT_F32, model_out_nchw, eps, C, B2, C, HW, 1, 1.0f, s));
-  TANGO_HIP(hipMemcpyAsync(dcoef, coef8, 32, hipMemcpyHostToDevice, s));
-  TANGO_HIP(hipMemsetAsync(dstep, 0, 4, s));
-  SchedParams p;
-  p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = 8; p.noise = noise; p.coef = dcoef; p.step_ptr = dstep;
-  p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = rule; p.clip = clip;
-  p.clip_range = clip_range; p.seed = 0; p.sample_offset = 0; p.ring = nullptr; p.coef_w = 8; p.algo = 0;
-  p.x0 = nullptr; p.mask = nullptr; p.blend_coef = nullptr; p.blend_noise = nullptr; p.num_steps = 1;
-  p.gtable = nullptr; p.rescale = 0.0f; p.gpart = nullptr; p.gscale = nullptr;
   SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
-  if (!dp) TANGO_FAIL("op_sched_step: alloc");
+  if (!eps || !xin || !dcoef || !dstep || !dp) TANGO_FAIL(w + ": alloc");
+  TANGO_TRY(launch_nchw_to_nhwc(DT_F32, o.model_out_nchw, eps, C, B2, C, HW, 1, 1.0f, s));
+  TANGO_HIP(hipMemcpyAsync(dcoef, o.coef, (size_t)o.num_steps * o.coef_width * 4, hipMemcpyHostToDevice, s));
+  TANGO_HIP(hipMemcpyAsync(dstep, &step, 4, hipMemcpyHostToDevice, s));
+  SchedParams p;
+  p.lat = o.latents; p.eps = eps; p.xin = xin; p.xin_ld = C; p.noise = o.noise; p.coef = dcoef; p.step_ptr = dstep;
+  p.B = B; p.C = C; p.HW = HW; p.cfg = o.cfg; p.guidance = o.guidance; p.pred_type = o.pred_type; p.rule = o.rule;
+  p.clip = o.clip; p.clip_range = o.clip_range; p.seed = o.seed; p.sample_offset = o.sample_offset; p.num_steps = o.num_steps;
+  if (ms) { p.ring = o.ring; p.coef_w = o.coef_width; p.algo = o.algo != -1 ? o.algo : (int)o.coef[11]; }
+  if (mk) {
+    float* dbc = (float*)sc.get((size_t)o.num_steps * 2 * 4);
+    if (!dbc) TANGO_FAIL(w + ": alloc");
+    TANGO_HIP(hipMemcpyAsync(dbc, o.blend_coef, (size_t)o.num_steps * 2 * 4, hipMemcpyHostToDevice, s));
+    p.x0 = o.known_latents; p.mask = o.latent_mask; p.blend_coef = dbc; p.blend_noise = o.blend_noise;
+  }
+  if (o.guided) {
+    float* dgt = (float*)sc.get((size_t)o.num_steps * B * 4);
+    float* dgs = (float*)sc.get((size_t)B * 4);
+    double* dgp = (double*)sc.get((size_t)B * guidance_chunks(HW) * 4 * 8);
+    if (!dgt || !dgs || !dgp) TANGO_FAIL(w + ": alloc");
+    TANGO_HIP(hipMemcpyAsync(dgt + (size_t)step * B, o.guidance_row, (size_t)B * 4, hipMemcpyHostToDevice, s));   // gtable[step * B + b]
+    p.gtable = dgt; p.rescale = o.rescale; p.gpart = dgp; p.gscale = dgs;
+  }
   TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
-  TANGO_TRY(launch_sched_step(DT_F32, dp, B * HW, s));
+  if (mk && step == 0) TANGO_TRY(launch_inpaint_blend0(DT_F32, dp, B * HW, s));
+  if (o.guided) TANGO_TRY(launch_guidance_stats(dp, B, HW, s));
+  TANGO_TRY(launch_sched_step(DT_F32, dp, B * HW, s, o.rule, mk, o.guided));
+  if (o.scale_out) {
+    if (o.rescale > 0.0f) TANGO_HIP(hipMemcpyAsync(o.scale_out, p.gscale, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    else for (int b = 0; b < B; ++b) o.scale_out[b] = 1.0f;
+  }
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
 }
 
+int tango_op_sched_step(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int HW,
+                        int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, void* stream) {
+  SchedOp o;                        // the single 8-float row is row 0 of a one-step loop
+  o.who = "op_sched_step"; o.latents = latents; o.model_out_nchw = model_out_nchw; o.noise = noise; o.coef = coef8;
+  o.B = B; o.C = C; o.HW = HW; o.cfg = cfg; o.guidance = guidance; o.pred_type = pred_type; o.rule = rule;
+  o.clip = clip; o.clip_range = clip_range; o.stream = stream;
+  return op_sched(o);
+}
+
 int tango_op_sched_multistep(float* latents, const float* model_out_nchw, float* ring, const float* coef16, int step, int B, int C,
                              int HW, int cfg, float guidance, int pred_type, int algo, void* stream) {
-  if (step < 0 || B <= 0 || C <= 0 || HW <= 0) TANGO_FAIL("op_sched_multistep: bad sizes");
   if (algo != 0 && algo != 1) TANGO_FAIL("op_sched_multistep: algo must be 0 (DPM-Solver++) or 1 (DPM-Solver)");
-  const int order = (int)coef16[(size_t)step * 16 + 10];
-  if (order < 1 || order > 3 || order > step + 1) TANGO_FAIL("op_sched_multistep: row order must be in [1, min(3, step + 1)]");
-  hipStream_t s = (hipStream_t)stream;
-  Scratch sc;
-  const int B2 = cfg ? 2 * B : B;
-  float* eps = (float*)sc.get((size_t)B2 * HW * C * 4);
-  float* xin = (float*)sc.get((size_t)B2 * HW * C * 4);
-  float* dcoef = (float*)sc.get((size_t)(step + 1) * 16 * 4);
-  int* dstep = (int*)sc.get(256);
-  if (!eps || !xin || !dcoef || !dstep) TANGO_FAIL("op_sched_multistep: alloc");
-  TANGO_TRY(launch_nchw_to_nhwc(DT_F32, model_out_nchw, eps, C, B2, C, HW, 1, 1.0f, s));
-  TANGO_HIP(hipMemcpyAsync(dcoef, coef16, (size_t)(step + 1) * 16 * 4, hipMemcpyHostToDevice, s));
-  TANGO_HIP(hipMemcpyAsync(dstep, &step, 4, hipMemcpyHostToDevice, s));
-  SchedParams p;
-  p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = C; p.noise = nullptr; p.coef = dcoef; p.step_ptr = dstep;
-  p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = TANGO_RULE_DPM_MULTISTEP;
-  p.clip = 0; p.clip_range = 1.0f; p.seed = 0; p.sample_offset = 0; p.ring = ring; p.coef_w = 16; p.algo = algo;
-  p.x0 = nullptr; p.mask = nullptr; p.blend_coef = nullptr; p.blend_noise = nullptr; p.num_steps = step + 1;
-  p.gtable = nullptr; p.rescale = 0.0f; p.gpart = nullptr; p.gscale = nullptr;
-  SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
-  if (!dp) TANGO_FAIL("op_sched_multistep: alloc");
-  TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
-  TANGO_TRY(launch_sched_step(DT_F32, dp, B * HW, s, TANGO_RULE_DPM_MULTISTEP));
-  TANGO_HIP(hipStreamSynchronize(s));
-  return 0;
+  SchedOp o;                        // the table up to this step; the algorithm is the argument, whatever column 11 says
+  o.who = "op_sched_multistep"; o.latents = latents; o.model_out_nchw = model_out_nchw; o.ring = ring; o.coef = coef16;
+  o.coef_width = 16; o.step = step; o.num_steps = step + 1; o.algo = algo;
+  o.B = B; o.C = C; o.HW = HW; o.cfg = cfg; o.guidance = guidance; o.pred_type = pred_type; o.rule = TANGO_RULE_DPM_MULTISTEP; o.stream = stream;
+  return op_sched(o);
+}
+
+int tango_op_sched_masked(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
+                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
+                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
+                          int pred_type, int rule, void* stream) {
+  SchedOp o;                        // a loop step of any rule; the masked arguments are required
+  o.who = "op_sched_masked"; o.need_mask = true;
+  o.latents = latents; o.model_out_nchw = model_out_nchw; o.noise = noise; o.ring = ring; o.coef = coef;
+  o.coef_width = coef_width; o.step = step; o.num_steps = num_steps; o.seed = seed; o.sample_offset = sample_offset;
+  o.known_latents = known_latents; o.latent_mask = latent_mask; o.blend_coef = blend_coef; o.blend_noise = blend_noise;
+  o.B = B; o.C = C; o.HW = HW; o.cfg = cfg; o.guidance = guidance; o.pred_type = pred_type; o.rule = rule; o.stream = stream;
+  return op_sched(o);
+}
+
+int tango_op_sched_guided(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
+                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
+                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
+                          int pred_type, int rule, const float* guidance_row, float rescale, float* scale_out, void* stream) {
+  SchedOp o;                        // a loop step of any rule, masked or not, through the guided kernels
+  o.who = "op_sched_guided";
+  o.latents = latents; o.model_out_nchw = model_out_nchw; o.noise = noise; o.ring = ring; o.coef = coef;
+  o.coef_width = coef_width; o.step = step; o.num_steps = num_steps; o.seed = seed; o.sample_offset = sample_offset;
+  o.known_latents = known_latents; o.latent_mask = latent_mask; o.blend_coef = blend_coef; o.blend_noise = blend_noise;
+  o.B = B; o.C = C; o.HW = HW; o.cfg = cfg; o.guidance = guidance; o.pred_type = pred_type; o.rule = rule; o.stream = stream;
+  o.guided = true; o.guidance_row = guidance_row; o.rescale = rescale; o.scale_out = scale_out;
+  return op_sched(o);
 }
 
 int tango_op_philox_normal(float* out, int B, int C, int HW, int step, uint64_t seed, int sample_offset, void* stream) {
@@ -902,91 +962,6 @@ int tango_op_philox_normal_blend(float* out, int B, int C, int HW, int step, uin
   TANGO_TRY(launch_philox_normal(out, B, C, HW, step, seed, sample_offset, s, true));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
-}
-
-// tango_op_sched_masked and tango_op_sched_guided: one step on caller-owned buffers.  guided: guidance_row / rescale / scale_out as the header says
-static int op_sched_any(const char* who, bool guided, float* latents, const float* model_out_nchw, const float* noise, float* ring,
-                        const float* coef, int coef_width, int step, int num_steps, const float* known_latents, const float* latent_mask,
-                        const float* blend_coef, const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg,
-                        float guidance, int pred_type, int rule, const float* guidance_row, float rescale, float* scale_out, void* stream) {
-  const std::string w(who);
-  if (B <= 0 || C <= 0 || HW <= 0 || num_steps <= 0 || step < 0 || step >= num_steps) TANGO_FAIL(w + ": bad sizes");
-  const bool mk = known_latents || latent_mask || blend_coef || blend_noise;
-  if (!guided || mk) {
-    if (!known_latents || !latent_mask || !blend_coef) TANGO_FAIL(w + ": known_latents, latent_mask and blend_coef are required");
-  }
-  if (guided) {
-    if (!cfg || !guidance_row) TANGO_FAIL(w + ": the guided kernels need cfg = 1 and a guidance row");
-    if (!(rescale >= 0.0f && rescale <= 1.0f)) TANGO_FAIL(w + ": rescale must be in [0, 1]");
-    for (int b = 0; b < B; ++b)
-      if (!(guidance_row[b] >= 0.0f) || std::isinf(guidance_row[b])) TANGO_FAIL(w + ": guidance entries must be finite and >= 0");
-  }
-  const bool ms = rule == TANGO_RULE_DPM_MULTISTEP;
-  if (rule != TANGO_RULE_DDPM && rule != TANGO_RULE_DDIM && !ms) TANGO_FAIL(w + ": unknown rule");
-  if (coef_width != (ms ? 16 : 8)) TANGO_FAIL(w + ": coef_width must be 16 for the multistep rule, else 8");
-  int algo = 0;
-  if (ms) {
-    if (noise || !ring) TANGO_FAIL(w + ": the multistep rule takes a ring and no step noise");
-    const int order = (int)coef[(size_t)step * 16 + 10];
-    if (order < 1 || order > 3 || order > step + 1) TANGO_FAIL(w + ": row order must be in [1, min(3, step + 1)]");
-    algo = (int)coef[11];
-    if (algo != 0 && algo != 1) TANGO_FAIL(w + ": table column 11 (algorithm) must be 0 or 1");
-  }
-  hipStream_t s = (hipStream_t)stream;
-  Scratch sc;
-  const int B2 = cfg ? 2 * B : B;
-  const int chunks = guidance_chunks(HW);
-  float* eps = (float*)sc.get((size_t)B2 * HW * C * 4);
-  float* xin = (float*)sc.get((size_t)B2 * HW * C * 4);
-  float* dcoef = (float*)sc.get((size_t)num_steps * coef_width * 4);
-  float* dbc = (float*)sc.get((size_t)num_steps * 2 * 4);
-  int* dstep = (int*)sc.get(256);
-  SchedParams* dp = (SchedParams*)sc.get(sizeof(SchedParams));
-  float* dgt = (float*)sc.get((size_t)num_steps * B * 4);
-  float* dgs = (float*)sc.get((size_t)B * 4);
-  double* dgp = (double*)sc.get((size_t)B * chunks * 4 * 8);
-  if (!eps || !xin || !dcoef || !dbc || !dstep || !dp || !dgt || !dgs || !dgp) TANGO_FAIL(w + ": alloc");
-  TANGO_TRY(launch_nchw_to_nhwc(DT_F32, model_out_nchw, eps, C, B2, C, HW, 1, 1.0f, s));
-  TANGO_HIP(hipMemcpyAsync(dcoef, coef, (size_t)num_steps * coef_width * 4, hipMemcpyHostToDevice, s));
-  if (mk) TANGO_HIP(hipMemcpyAsync(dbc, blend_coef, (size_t)num_steps * 2 * 4, hipMemcpyHostToDevice, s));
-  TANGO_HIP(hipMemcpyAsync(dstep, &step, 4, hipMemcpyHostToDevice, s));
-  // the row of THIS step: the kernels read gtable[step * B + b]
-  if (guided) TANGO_HIP(hipMemcpyAsync(dgt + (size_t)step * B, guidance_row, (size_t)B * 4, hipMemcpyHostToDevice, s));
-  SchedParams p;
-  p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = C; p.noise = noise; p.coef = dcoef; p.step_ptr = dstep;
-  p.B = B; p.C = C; p.HW = HW; p.cfg = cfg; p.guidance = guidance; p.pred_type = pred_type; p.rule = rule;
-  p.clip = 0; p.clip_range = 1.0f; p.seed = seed; p.sample_offset = sample_offset; p.ring = ms ? ring : nullptr; p.coef_w = coef_width;
-  p.algo = algo;
-  p.x0 = known_latents; p.mask = latent_mask; p.blend_coef = mk ? dbc : nullptr; p.blend_noise = blend_noise; p.num_steps = num_steps;
-  p.gtable = guided ? dgt : nullptr; p.rescale = guided ? rescale : 0.0f; p.gpart = guided ? dgp : nullptr; p.gscale = guided ? dgs : nullptr;
-  TANGO_HIP(hipMemcpyAsync(dp, &p, sizeof(SchedParams), hipMemcpyHostToDevice, s));
-  if (mk && step == 0) TANGO_TRY(launch_inpaint_blend0(DT_F32, dp, B * HW, s));
-  if (guided) TANGO_TRY(launch_guidance_stats(dp, B, HW, s));
-  TANGO_TRY(launch_sched_step(DT_F32, dp, B * HW, s, rule, mk, guided));
-  if (scale_out) {
-    if (rescale > 0.0f) TANGO_HIP(hipMemcpyAsync(scale_out, dgs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    else for (int b = 0; b < B; ++b) scale_out[b] = 1.0f;
-  }
-  TANGO_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-int tango_op_sched_masked(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
-                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
-                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
-                          int pred_type, int rule, void* stream) {
-  return op_sched_any("op_sched_masked", false, latents, model_out_nchw, noise, ring, coef, coef_width, step, num_steps, known_latents,
-                      latent_mask, blend_coef, blend_noise, seed, sample_offset, B, C, HW, cfg, guidance, pred_type, rule, nullptr, 0.0f,
-                      nullptr, stream);
-}
-
-int tango_op_sched_guided(float* latents, const float* model_out_nchw, const float* noise, float* ring, const float* coef, int coef_width,
-                          int step, int num_steps, const float* known_latents, const float* latent_mask, const float* blend_coef,
-                          const float* blend_noise, uint64_t seed, int sample_offset, int B, int C, int HW, int cfg, float guidance,
-                          int pred_type, int rule, const float* guidance_row, float rescale, float* scale_out, void* stream) {
-  return op_sched_any("op_sched_guided", true, latents, model_out_nchw, noise, ring, coef, coef_width, step, num_steps, known_latents,
-                      latent_mask, blend_coef, blend_noise, seed, sample_offset, B, C, HW, cfg, guidance, pred_type, rule, guidance_row,
-                      rescale, scale_out, stream);
 }
 
 int tango_op_latent_encode(const float* moments, int moments_batch, float* z0_out, float* xt_out, const float* eps, const float* noise,

@@ -341,3 +341,45 @@ def test_sched_step_bit_exact(lib, pred):
         check(lib, lib.tango_op_sched_step(ptr(lat_d), ptr(dev(mo)), ptr(dev(nz)), coef.ctypes.data_as(C.c_void_p), B, Cc, HW, 1, 3.0,
                                            {"epsilon": 0, "v_prediction": 2}[pred], 0, 0, 1.0, None))
         assert torch.equal(lat_d.cpu(), ref), "t=%d max diff %g" % (t, (lat_d.cpu() - ref).abs().max())
+
+
+@pytest.mark.parametrize("rule", ["ddpm", "ddim"])
+@pytest.mark.parametrize("pred", ["v_prediction", "epsilon"])
+def test_sched_step_clip_bit_exact(lib, pred, rule):
+    """clip_sample through tango_op_sched_step == the oracle's DDPM / DDIM step with clip_sample=True, bit for bit, with and without
+    CFG, at an early and a late timestep.  HW = 300: two workgroups per sample pair, the last one partly empty.  The range is 1.0
+    except for epsilon at t = 995, where x0 = (x - sqrt(1 - abar) v) / sqrt(abar) with sqrt(abar) = 0.068 has a spread of about 15
+    (55 with CFG) and a range of 1.0 would clip nearly everything: 16.0 there.  Each case first shows on the oracle alone that the
+    clip changes between 10 % and 90 % of the result."""
+    from oracle import tango_oracle as O
+    from tango_amd.scheduler import DDIMScheduler
+    B, Cc, HW, N = 2, 8, 300, 200
+    base = dict(O.SD21_SCHEDULER, prediction_type=pred)
+    cls = O.DDPMOracle if rule == "ddpm" else O.DDIMOracle
+    ddim_rows = None
+    if rule == "ddim":
+        host = DDIMScheduler(**{k: v for k, v in base.items() if k != "variance_type"})
+        host.set_timesteps(N)
+        ddim_rows = dict(zip(host.timesteps.tolist(), host.coef_table()))
+    g = torch.Generator().manual_seed(17)
+    for cfg_on in (True, False):
+        for t in (995, 5):
+            rng = 16.0 if (pred == "epsilon" and t == 995) else 1.0
+            sch, plain = cls(**dict(base, clip_sample=True, clip_sample_range=rng)), cls(**dict(base, clip_sample=False))
+            sch.set_timesteps(N)
+            plain.set_timesteps(N)
+            lat = torch.randn(B, Cc, HW, generator=g)
+            mo = torch.randn(2 * B if cfg_on else B, Cc, HW, generator=g)
+            nz = torch.randn(B, Cc, HW, generator=g)
+            model = mo.chunk(2)[0] + 3.0 * (mo.chunk(2)[1] - mo.chunk(2)[0]) if cfg_on else mo
+            ref, unclipped = sch.step(model, t, lat, noise=nz), plain.step(model, t, lat, noise=nz)
+            changed = (ref != unclipped).float().mean().item()
+            assert 0.1 <= changed <= 0.9, "cfg %s t=%d: the clip changes %.0f %% of the reference" % (cfg_on, t, 100 * changed)
+            row = np.asarray(sch.coefficients(t) + [0, 0, 0], dtype=np.float32) if rule == "ddpm" else np.ascontiguousarray(ddim_rows[t])
+            lat_d = dev(lat)
+            check(lib, lib.tango_op_sched_step(ptr(lat_d), ptr(dev(mo)), ptr(dev(nz)), row.ctypes.data_as(C.c_void_p), B, Cc, HW,
+                                               1 if cfg_on else 0, 3.0, {"epsilon": 0, "v_prediction": 2}[pred],
+                                               0 if rule == "ddpm" else 1, 1, rng, None))
+            got = lat_d.cpu()
+            assert torch.equal(got, ref), "cfg %s t=%d max diff %g" % (cfg_on, t, (got - ref).abs().max())
+            assert not torch.equal(got, unclipped)

@@ -160,7 +160,7 @@ def _philox(lib, B, C_, HW, step, seed, offset):
 
 
 def test_philox_noise_statistics(lib):
-    """Box-Muller over Philox4x32-10 (elementwise.hip): N(0,1) moments of 1.05e6 draws, independence across steps / seeds /
+    """Box-Muller over Philox4x32-10 (sched.hip): N(0,1) moments of 1.05e6 draws, independence across steps / seeds /
     samples, and offset invariance of the counter layout."""
     x = _philox(lib, 4, 8, 32768, 3, 1234, 0).double().flatten()      # 1 048 576 draws
     n = x.numel()

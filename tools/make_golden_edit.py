@@ -96,7 +96,7 @@ def add_noise_inputs(seed):
 
 
 def table_step(row, rule, pred, v, x, nz=None):
-    """one update of the fused one-step kernel (tango_amd/csrc/elementwise.hip sched_step_kernel) from a table row, in its expression
+    """one update of the fused one-step kernel (tango_amd/csrc/sched.hip sched_step_kernel) from a table row, in its expression
     order, in torch fp32: rule "ddpm" or "ddim" (the inverse table runs as "ddim")"""
     sa, sb, c0, c1, sig, sap, dirc = (torch.tensor(float(r), dtype=torch.float32) for r in row[:7])
     if pred == "epsilon":
