@@ -320,6 +320,11 @@ const char* tango_debug_groupnorm_form(int dtype, int B, int C, int HW, int grou
  * msum+kdma+vdma, f8, f8+msum, x8.  Arguments the launch refuses answer its message instead.  masked / pos_bias: a key-mask bias / a relative position
  * bias is given; fp8_pv 0 | 1 | 2 and vt_perm as in tango_op_attention_ex's flags.  dtype 0 = fp32, 1 = fp16, 2 = bf16.  tests/test_attention_routes.py */
 const char* tango_debug_attention_route(int dtype, int B, int heads, int Sq, int Skv, int masked, int pos_bias, int fp8_pv, int vt_perm);
+/* the same for buffers with the given pitches in elements (tango_debug_attention_route asks ldq = ldk = ldo = heads * 64, ldvt = round8(Skv)): the
+ * engine's self-attention reads q | k from one buffer of pitch 2 * heads * 64, its cross-attention q from that buffer and k at pitch heads * 64.  The
+ * answer depends on the pitches only through the ld-alignment refusal (16-byte q / k / v^T rows, 8-byte output rows) */
+const char* tango_debug_attention_route_ld(int dtype, int B, int heads, int Sq, int Skv, int masked, int pos_bias, int fp8_pv, int vt_perm, int ldq,
+                                           int ldk, int ldvt, int ldo);
 
 /* ---- per-operator entry points (parity tests; fp32 reference-layout tensors on device) ---- */
 int tango_op_conv2d(int dtype, const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W,
@@ -435,6 +440,18 @@ int tango_op_attention(int dtype, const float* q, const float* k, const float* v
  * and both tiles travel by LDS-DMA (unmasked 16-bit problems with Sq > 512, Skv % 64 == 0; refused otherwise) */
 int tango_op_attention_ex(int dtype, const float* q, const float* k, const float* v, const float* bias, float* out, int B, int heads,
                           int Sq, int Skv, float scale, int flags, void* stream);
+/* as tango_op_attention_ex on the memory layouts the engine hands the kernel instead of the dense one.  pos_bias: fp32 [heads][Sq][Skv] on the
+ * device or NULL, passed as it is (the text encoder's relative position bias; not with an fp8 flag).  k_col0 >= 0 (needs Sq == Skv and
+ * ldk == ldq): q and k are staged into ONE [B*S][ldq] buffer, q in columns [0, C) and k in [k_col0, k_col0 + C), C = heads * 64, as
+ * Builder::transformer and build_t5 slice their projection; k_col0 = -1: two buffers of pitches ldq and ldk.  ldvt >= round8(Skv) is the
+ * pitch of the staged V^T; the output buffer is [B*Sq][ldo] with the result in columns [o_col0, o_col0 + C).  pad_value (finite), rounded
+ * to the dtype, fills every staged element that is not payload -- the pitch columns of q and k, the V^T columns >= Skv and the whole output
+ * buffer before the launch -- and out, fp32 [B*Sq][ldo], receives the whole pitched output buffer, pads included.  Refused before any launch:
+ * a non-finite pad_value, a pitch below C (ldvt below round8(Skv)) or beyond 65536, a column range outside its row, q / k / v^T bases that are
+ * not 16-byte or an output base that is not 8-byte aligned (the column offsets are in elements), pos_bias with an fp8 flag. */
+int tango_op_attention_view(int dtype, const float* q, const float* k, const float* v, const float* bias, const float* pos_bias, float* out,
+                            int B, int heads, int Sq, int Skv, float scale, int flags, int ldq, int ldk, int k_col0, int ldvt, int ldo,
+                            int o_col0, float pad_value, void* stream);
 /* fused cross-attention block of BasicTransformerBlock (diffusers attention.py:312-323: attn2(norm2(x), text, mask) + x) as the engine
    runs it at level 0 (C = 320, 5 heads, 64 text tokens): x [B*HW, 320]; wq / wo [320, 320] Linear weights (to_q has no bias);
    k, v [B*L, 320] = to_k / to_v of the text; bias [B, L] additive or NULL */

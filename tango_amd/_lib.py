@@ -130,7 +130,7 @@ SYMBOLS = [
     "tango_debug_conv_transpose1d_phase",
     "tango_op_linear_ex", "tango_debug_linear_ex_check", "tango_op_conv2d_temb", "tango_op_conv2d_ups_temb",
     "tango_engine_denoise_guided", "tango_debug_denoise_guided_check", "tango_op_sched_guided",
-    "tango_debug_attention_route",
+    "tango_debug_attention_route", "tango_debug_attention_route_ld", "tango_op_attention_view",
 ]
 
 _lib = None
@@ -190,6 +190,8 @@ def load():
     lib.tango_debug_groupnorm_form.restype = C.c_char_p
     lib.tango_debug_attention_route.argtypes = [ci] * 9
     lib.tango_debug_attention_route.restype = C.c_char_p
+    lib.tango_debug_attention_route_ld.argtypes = [ci] * 13
+    lib.tango_debug_attention_route_ld.restype = C.c_char_p
     lib.tango_engine_ring_elems.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.tango_engine_plan_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(ci)]
     lib.tango_op_conv2d.argtypes = [ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
@@ -207,6 +209,7 @@ def load():
     lib.tango_op_layernorm.argtypes = [ci, vp, vp, vp, vp, ci, ci, cf, vp]
     lib.tango_op_attention.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]
     lib.tango_op_attention_ex.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, vp]
+    lib.tango_op_attention_view.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, ci, ci, ci, ci, ci, ci, cf, vp]
     lib.tango_op_xattn_block.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, vp]
     lib.tango_op_sched_step.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, ci, ci, cf, vp]
     lib.tango_op_sched_multistep.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp]

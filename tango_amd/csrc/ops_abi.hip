@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/tango_engine.h"
+#include "attn_view_check.h"
 #include "common.h"
 #include "tuning.h"
 
@@ -784,11 +785,75 @@ int tango_op_attention_ex(int dt, const float* q, const float* k, const float* v
   return 0;
 }
 
+// tango_op_attention_ex on the layouts the engine hands the kernel (include/tango_engine.h): q | k slices of one wide buffer, pitched V^T and
+// output rows, a position bias.  Every staged element that is not payload holds pad_value; no kernel of its own (cast_rows and transpose_v
+// take the pitches), and attn_view_refusal() answers before the first launch.
+int tango_op_attention_view(int dt, const float* q, const float* k, const float* v, const float* bias, const float* pos_bias, float* out,
+                            int B, int heads, int Sq, int Skv, float scale, int flags, int ldq, int ldk, int k_col0, int ldvt, int ldo,
+                            int o_col0, float pad_value, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!q || !k || !v || !out) TANGO_FAIL("op_attention_view: q, k, v and out are required");
+  AttnViewArgs a;
+  a.dtype = dt; a.B = B; a.heads = heads; a.Sq = Sq; a.Skv = Skv; a.flags = flags; a.bias = bias != nullptr; a.pos_bias = pos_bias != nullptr;
+  a.ldq = ldq; a.ldk = ldk; a.k_col0 = k_col0; a.ldvt = ldvt; a.ldo = ldo; a.o_col0 = o_col0; a.pad_value = pad_value;
+  const size_t esz = dtype_size(dt);
+  // first with the column offsets as bases (allocations are 256-byte aligned): every refusal precedes the first HIP call, and the sizes
+  // of the allocations below are products of checked arguments
+  if (k_col0 > 0) a.k_base = (uintptr_t)k_col0 * esz;
+  if (o_col0 > 0) a.o_base = (uintptr_t)o_col0 * esz;
+  if (const char* why = attn_view_refusal(a)) TANGO_FAIL(why);
+  const int C = heads * 64;
+  const bool one = k_col0 >= 0;                                      // q | k in one buffer
+  const size_t nq = (size_t)B * Sq * ldq, nk = (size_t)B * Skv * ldk, nvt = (size_t)B * C * ldvt, no = (size_t)B * Sq * ldo;
+  size_t npad = nq > nvt ? nq : nvt;
+  if (nk > npad) npad = nk;
+  if (no > npad) npad = no;
+  Scratch sc;
+  char* qt = (char*)sc.get(nq * esz);
+  char* kt = one ? qt + (size_t)k_col0 * esz : (char*)sc.get(nk * esz);
+  void* vt = sc.get((size_t)B * Skv * C * esz);
+  char* vtt = (char*)sc.get(nvt * esz);
+  char* ot = (char*)sc.get(no * esz);
+  float* pad = (float*)sc.get(npad * 4);
+  if (!qt || !kt || !vt || !vtt || !ot || !pad) TANGO_FAIL("op_attention_view: alloc");
+  a.q_base = (uintptr_t)qt; a.k_base = (uintptr_t)kt; a.vt_base = (uintptr_t)vtt; a.o_base = (uintptr_t)(ot + (size_t)o_col0 * esz);
+  if (const char* why = attn_view_refusal(a)) TANGO_FAIL(why);       // ... and again with the bases the kernel will see
+  {
+    const std::vector<float> hpad(npad, pad_value);
+    TANGO_HIP(hipMemcpyAsync(pad, hpad.data(), npad * 4, hipMemcpyHostToDevice, s));
+    TANGO_HIP(hipStreamSynchronize(s));     // hpad is this block's
+  }
+  // pad_value everywhere (rows of width ld), then the payload over it
+  TANGO_TRY(launch_cast_rows(dt, pad, qt, ldq, B * Sq, ldq, s));
+  if (!one) TANGO_TRY(launch_cast_rows(dt, pad, kt, ldk, B * Skv, ldk, s));
+  TANGO_TRY(launch_cast_rows(dt, pad, vtt, ldvt, B * C, ldvt, s));
+  TANGO_TRY(launch_cast_rows(dt, pad, ot, ldo, B * Sq, ldo, s));
+  TANGO_TRY(launch_cast_rows(dt, q, qt, ldq, B * Sq, C, s));
+  TANGO_TRY(launch_cast_rows(dt, k, kt, ldk, B * Skv, C, s));
+  TANGO_TRY(launch_cast_rows(dt, v, vt, C, B * Skv, C, s));
+  TANGO_TRY(transpose_v(dt, vt, vtt, B, Skv, C, ldvt, s));
+  AttnParams p;
+  p.q = qt; p.ldq = ldq; p.k = kt; p.ldk = ldk; p.vt = vtt; p.ldvt = ldvt; p.o = ot + (size_t)o_col0 * esz; p.ldo = ldo;
+  p.bias = bias; p.pos_bias = pos_bias; p.B = B; p.heads = heads; p.Sq = Sq; p.Skv = Skv; p.scale = scale;
+  if (flags & 1) p.fp8_pv = flags & 2 ? 2 : 1;
+  if (flags & 4) p.vt_perm = 1;
+  TANGO_TRY(launch_attention(dt, p, s));
+  TANGO_TRY(to_f32(dt, ot, ldo, out, (int64_t)B * Sq, ldo, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 const char* tango_debug_attention_route(int dt, int B, int heads, int Sq, int Skv, int masked, int pos_bias, int fp8_pv, int vt_perm) {
-  // the kernel tango_op_attention[_ex] (same leading dimensions) or the engine runs for this site under the current switches, and its grid; or the refusal
+  // the kernel tango_op_attention[_ex] (same leading dimensions) runs for this site under the current switches, and its grid; or the refusal
+  return tango_debug_attention_route_ld(dt, B, heads, Sq, Skv, masked, pos_bias, fp8_pv, vt_perm, heads * 64, heads * 64, (Skv + 7) / 8 * 8, heads * 64);
+}
+
+const char* tango_debug_attention_route_ld(int dt, int B, int heads, int Sq, int Skv, int masked, int pos_bias, int fp8_pv, int vt_perm, int ldq,
+                                           int ldk, int ldvt, int ldo) {
+  // ... with the pitches of the caller's buffers: what the engine (q | k slices, pitch 2C) or tango_op_attention_view runs
   const float* const fd = (const float*)kRouteDummy;
   AttnParams p;
-  p.q = p.k = p.vt = kRouteDummy; p.o = kRouteDummy; p.ldq = p.ldk = p.ldo = heads * 64; p.ldvt = (Skv + 7) / 8 * 8;
+  p.q = p.k = p.vt = kRouteDummy; p.o = kRouteDummy; p.ldq = ldq; p.ldk = ldk; p.ldo = ldo; p.ldvt = ldvt;
   p.bias = masked ? fd : nullptr; p.pos_bias = pos_bias ? fd : nullptr; p.B = B; p.heads = heads; p.Sq = Sq; p.Skv = Skv; p.scale = 0.125f;
   p.fp8_pv = fp8_pv; p.vt_perm = vt_perm;
   const AttnPlan pl = plan_attention(dt, p);

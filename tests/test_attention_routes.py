@@ -99,6 +99,98 @@ REFUSALS = [
 
 @pytest.mark.parametrize("kw,why", REFUSALS)
 def test_attention_refusal(route, kw, why):
-    """what launch_attention refuses, with the message it fails with (the ld-alignment refusal cannot be asked: the query builds the op
-    wrapper's dense, aligned rows)"""
+    """what launch_attention refuses, with the message it fails with (the ld-alignment refusal is asked through
+    tango_debug_attention_route_ld below: this query builds the op wrapper's dense, aligned rows)"""
     assert route(2, 5, **kw) == why
+
+
+def dense_ld(heads, Skv):
+    C_ = heads * 64
+    return dict(ldq=C_, ldk=C_, ldvt=(Skv + 7) // 8 * 8, ldo=C_)
+
+
+@pytest.fixture()
+def route_ld(route):
+    """tango_debug_attention_route_ld under the `route` fixture's clean switches: pitches by keyword, dense where not given"""
+    lib = _lib.load()
+
+    def ask(B, heads, Sq, Skv, masked=0, pos_bias=0, fp8=0, vt_perm=0, dtype=F16, ldq=None, ldk=None, ldvt=None, ldo=None, **env):
+        d = dense_ld(heads, Skv)
+        ld = [d[n] if v is None else v for n, v in (("ldq", ldq), ("ldk", ldk), ("ldvt", ldvt), ("ldo", ldo))]
+        os.environ.update({k: str(v) for k, v in env.items()})
+        lib.tango_tuning_reload()
+        try:
+            return lib.tango_debug_attention_route_ld(dtype, B, heads, Sq, Skv, masked, pos_bias, fp8, vt_perm, *ld).decode()
+        finally:
+            for k in env:
+                del os.environ[k]
+            lib.tango_tuning_reload()
+
+    return ask
+
+
+# q, k and v^T rows are read in 16-byte pieces, output rows stored in 8-byte ones: the smallest step off the dense pitch that breaks that,
+# and next to each the smallest one that keeps it (which must plan like the dense rows)
+LD_REFUSED = [
+    (F16, dict(ldq=321)), (F16, dict(ldq=324)), (F16, dict(ldk=321)), (F16, dict(ldk=324)), (F16, dict(ldvt=260)), (F16, dict(ldo=321)), (F16, dict(ldo=322)),
+    (BF16, dict(ldq=321)), (BF16, dict(ldk=324)), (BF16, dict(ldvt=257)), (BF16, dict(ldo=322)),
+    (F32, dict(ldq=321)), (F32, dict(ldq=322)), (F32, dict(ldk=322)), (F32, dict(ldvt=258)), (F32, dict(ldo=321)),
+]
+LD_ACCEPTED = [
+    (F16, dict(ldq=328)), (F16, dict(ldk=328)), (F16, dict(ldvt=264)), (F16, dict(ldo=324)), (BF16, dict(ldo=324)), (BF16, dict(ldvt=264)),
+    (F32, dict(ldq=324)), (F32, dict(ldk=324)), (F32, dict(ldvt=260)), (F32, dict(ldo=322)),
+]
+
+
+@pytest.mark.parametrize("dtype,ld", LD_REFUSED)
+def test_attention_ld_alignment_refusal(route_ld, dtype, ld):
+    assert route_ld(2, 5, 256, 256, dtype=dtype, **ld) == "attention: ld alignment"
+    assert route_ld(2, 5, 256, 72, masked=1, dtype=dtype, **dict(ld, ldvt=ld.get("ldvt", 72))) == "attention: ld alignment"
+
+
+@pytest.mark.parametrize("dtype,ld", LD_ACCEPTED)
+def test_attention_ld_alignment_accepted(route, route_ld, dtype, ld):
+    assert route_ld(2, 5, 256, 256, dtype=dtype, **ld) == route(2, 5, 256, 256, dtype=dtype)
+
+
+def test_attention_vt_perm_with_odd_ldvt(route_ld):
+    """a fragment-order V^T whose pitch is no multiple of 8 is never planned.  The planner's vt_perm rule names ldvt % 8 itself; for the
+    16-bit types, the only ones that read a vt_perm V^T, the 16-byte rule for rows says the same thing first"""
+    perm = "attention: vt_perm needs an unmasked 16-bit site with Sq > 512, Skv % 64 == 0, no fp8 P.V"
+    assert route_ld(2, 5, 4096, 4096, vt_perm=1, dtype=F32, ldvt=4100) == perm      # 16-byte rows in fp32, 4100 % 8 != 0
+    for dtype in (F16, BF16):
+        assert route_ld(2, 5, 4096, 4096, vt_perm=1, dtype=dtype, ldvt=4100) == "attention: ld alignment"
+        assert route_ld(2, 5, 4096, 4096, vt_perm=1, dtype=dtype, ldvt=4104) == "qb2:msum+kdma+vdma 32x5x2"
+
+
+@pytest.mark.parametrize("args,want", SITES + ARMS)
+def test_attention_route_with_engine_pitches(route, route_ld, args, want):
+    """the engine hands the kernel q | k slices of one buffer of pitch 2C (self-attention, text encoder) or q from that buffer and the hoisted
+    k at pitch C (cross-attention): the same kernel and grid as on dense rows -- the planner reads pitches for alignment only"""
+    B, heads, Sq, Skv, kw = args
+    C_ = heads * 64
+    cross = Sq != Skv
+    dtypes = (F16, BF16) if kw.get("dtype", F16) == F16 else (kw["dtype"],)
+    for dtype in dtypes:
+        k = dict(kw, dtype=dtype)
+        dense = route(B, heads, Sq, Skv, **k)
+        assert dense == want
+        assert route_ld(B, heads, Sq, Skv, ldq=2 * C_, ldk=C_ if cross else 2 * C_, **k) == dense
+        assert route_ld(B, heads, Sq, Skv, ldq=2 * C_, ldk=C_ if cross else 2 * C_, ldvt=(Skv + 7) // 8 * 8 + 8, ldo=C_ + 8, **k) == dense
+        assert route_ld(B, heads, Sq, Skv, **k) == dense                             # dense pitches spelled out
+
+
+def test_attention_view_hook_refuses_before_any_gpu_call():
+    """tango_op_attention_view answers each of its refusals (the rows of tests/test_attention_layouts_gpu.py) from its host checker before it
+    allocates or launches anything: the same messages on a machine without a GPU, from pointers that are never dereferenced"""
+    import ctypes as C
+
+    from test_attention_layouts_gpu import call_refused, view_refusals
+    lib = _lib.load()
+    B, heads, S = 1, 2, 64
+    ptrs = tuple(C.c_void_p(0x10000 * (i + 1)) for i in range(6))
+    rows = view_refusals(heads * 64, S)
+    assert len(rows) >= 25
+    for dtype, over, part in rows:
+        rc, msg = call_refused(lib, dtype, over, ptrs, B, heads, S)
+        assert rc != 0 and part in msg, (dtype, over, msg)
