@@ -8,7 +8,9 @@
  *                               + DDPMScheduler.step                       mustango/diffusers/src/diffusers/schedulers/scheduling_ddpm.py:254-349
  *                               (+ DDIMScheduler.step                      .../scheduling_ddim.py:238-360)
  *                               (+ DPMSolverMultistepScheduler.step        .../scheduling_dpmsolver_multistep.py:429-495)
- *   tango_engine_unet_forward   UNet2DConditionModel.forward               mustango/diffusers/src/diffusers/models/unet_2d_condition.py:520-707
+ *   tango_engine_denoise_windows  StableDiffusionPanoramaPipeline's loop    mustango/diffusers/src/diffusers/pipelines/stable_diffusion/pipeline_stable_diffusion_panorama.py:614-652
+ *   tango_engine_vae_decode_tiled_h  AutoencoderKL.tiled_decode             mustango/diffusers/src/diffusers/models/autoencoder_kl.py:255-296
+ *   tango_engine_unet_forward   UNet2DConditionModel.forward             mustango/diffusers/src/diffusers/models/unet_2d_condition.py:520-707
  *   tango_engine_unet_forward_music  UNet2DConditionModelMusic.forward      mustango/diffusers/src/diffusers/models/unet_2d_condition_music.py:536-757
  *   tango_engine_vae_decode     AutoencoderKL.decode_first_stage           audioldm/variational_autoencoder/autoencoder.py:116-124,60-64
  *   tango_engine_vae_encode     AutoencoderKL.encode (encode_first_stage)  audioldm/variational_autoencoder/autoencoder.py:52-58,112-113
@@ -226,6 +228,35 @@ int tango_engine_denoise_guided(tango_engine_t* h, const tango_denoise_args_t* a
  * [0, 1] or NaN, rescale > 0 without guidance, a table entry negative or not finite, and every refusal of tango_engine_denoise's own
  * checks (rule, coef_width, multistep table rows, masking pointers).  Reads args->coef (multistep rule) and guide->table. */
 const char* tango_debug_denoise_guided_check(const tango_denoise_args_t* args, const tango_guidance_args_t* guide);
+
+/* Clips longer than the UNet's trained length: MultiDiffusion (Bar-Tal et al. 2023) windows in time, the fork's panorama pipeline
+ * (mustango/diffusers/src/diffusers/pipelines/stable_diffusion/pipeline_stable_diffusion_panorama.py:442-456 get_views, :614-652 the per-step
+ * loop) fused into the engine's step (tango_denoise_args_t itself is frozen).
+ * Geometry: the canvas is args->latents [B, C_lat, H, latent_w] with H = args->latent_h (> 0; noise is [N][B, C_lat, H, latent_w]); window_h = Hw
+ * is a UNet height, 1 <= stride = s <= Hw, and (H - Hw) % s == 0 -- the views cover the canvas exactly (get_views floors and leaves a tail
+ * no view covers; here that is refused).  V = (H - Hw) / s + 1 <= 32 views, view v covers canvas rows [v s, v s + Hw).  The UNet runs
+ * (cfg ? 2 : 1) * B * V rows of height Hw per step, row half * B * V + b * V + v for window v of sample b, unconditional half first:
+ * prompt_embeds / prompt_mask (/ prompt_mask_host) hold that many rows in that order (repeat each sample's rows V times).
+ * Per step and canvas element, over the views that cover its row in ascending order: d_v = the rule's `prev` of the plain update before
+ * its noise term, from view v's guided output at the element's position in that window; r = (0 + d_.. + d_..) / count (fp32, IEEE division);
+ * r += sigma * n when sigma > 0.  n is ONE draw per canvas element (noise[step][b, c, h, w], or Philox with the canvas position in the
+ * counter) -- the fork's loop would average V independent draws and shrink the step noise; with sigma == 0 the update is the fork's.
+ * V = 1 (H == Hw) computes tango_engine_denoise's bits.
+ * Refused: TANGO_RULE_DPM_MULTISTEP (a per-view history has no reference behaviour), known_latents, a geometry that is no exact cover,
+ * V > 32, a window_h that is no UNet height, and whatever tango_engine_denoise refuses.  There is no guidance table or rescale here. */
+typedef struct tango_window_args {
+  int32_t window_h;            /* Hw */
+  int32_t stride;              /* s  */
+} tango_window_args_t;
+int tango_engine_denoise_windows(tango_engine_t* h, const tango_denoise_args_t* args, const tango_window_args_t* win, void* stream);
+/* host-side query, no GPU needed: "" when tango_engine_denoise_windows accepts these arguments as far as its argument checks go (window_h
+ * is only asked to be a multiple of 8: the heights of a configuration are checked by the call itself), else the message it fails with */
+const char* tango_debug_denoise_windows_check(const tango_denoise_args_t* args, const tango_window_args_t* win);
+/* latents [B, embed_dim, canvas_h, latent_w] -> mel [B, 1, 4 canvas_h, 64] (three VAE levels): the V = (canvas_h - window_h) / stride + 1 latent
+ * windows of every sample go through the decoder at batch B * V and height window_h (a VAE height) in one run, and the decoded tiles are
+ * cross-faded as tango_op_mel_tile_blend says.  All V tiles are decoded, overlaps included.  The same geometry rules as above. */
+int tango_engine_vae_decode_tiled_h(tango_engine_t* h, const float* latents, float* mel, int batch, int canvas_h, int window_h, int stride,
+                                    void* stream);
 
 /* one UNet call: sample [B2,C,H,W] fp32 NCHW, timestep, embeds [B2,L,d], mask [B2,L] -> out [B2,C,H,W] fp32 */
 int tango_engine_unet_forward(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
@@ -467,6 +498,20 @@ int tango_op_xattn_block(int dtype, const float* x, const float* gamma, const fl
  * tango_denoise_args_t.clip_sample / clip_sample_range.  Synchronises. */
 int tango_op_sched_step(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int HW,
                         int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, void* stream);
+
+/* one windowed update (tango_engine_denoise_windows) at loop index `step` on caller-owned fp32 buffers: latents [B, C, H, W] the canvas,
+ * in/out; model_out_nchw [B2 * V, C, Hw, W] the UNet output of the window batch (B2 = 2B, [uncond; cond], when cfg; row b * V + v of a
+ * half); noise DEVICE [B, C, H, W], this step's canvas noise, or NULL (Philox: seed, sample_offset, `step` and the canvas position); coef8
+ * HOST [8], the row of this step.  Refuses what tango_engine_denoise_windows refuses.  Synchronises. */
+int tango_op_sched_windows(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H, int W,
+                           int Hw, int s, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
+                           int sample_offset, int step, void* stream);
+/* cross-fade of decoded tiles (the fork's tiled VAE decode, mustango/diffusers/src/diffusers/models/autoencoder_kl.py:198-201, 255-296): tiles
+ * DEVICE fp32 [B * V, 1, Hw4, F], tile t holding output rows [t s4, t s4 + Hw4) -> out DEVICE fp32 [B, 1, (V - 1) s4 + Hw4, F].  With
+ * E = Hw4 - s4 the weight of tile t at its local row y is min(1, (y + 0.5) / E) if t > 0, times min(1, (Hw4 - y - 0.5) / E) if t < V - 1
+ * (both 1 when E == 0); out[r] = (sum_t w_t tile_t) / (sum_t w_t) over the covering tiles in ascending order, fp32.  For s4 >= Hw4 / 2 two
+ * overlapping weights sum to 1: blend_v's ramp at half-pixel centres.  1 <= s4 <= Hw4, V <= 32.  Synchronises. */
+int tango_op_mel_tile_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream);
 
 /* one fused CFG + multistep DPM-Solver step (TANGO_RULE_DPM_MULTISTEP) at loop index `step` on caller-owned buffers: latents
  * [B, C, HW] fp32 in/out, model_out_nchw [B2, C, HW] fp32 (B2 = 2B, [uncond; cond], when cfg), ring DEVICE [3][B][C][HW] fp32

@@ -111,6 +111,14 @@ class GuidanceArgs(C.Structure):
     ]
 
 
+class WindowArgs(C.Structure):
+    """tango_window_args_t: the window height and stride of tango_engine_denoise_windows (rows of the latent canvas)"""
+    _fields_ = [
+        ("window_h", C.c_int32),
+        ("stride", C.c_int32),
+    ]
+
+
 #: every symbol include/tango_engine.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "tango_last_error", "tango_version", "tango_tuning_reload", "tango_debug_linear_route", "tango_debug_groupnorm_form", "tango_engine_create", "tango_engine_destroy",
@@ -131,6 +139,8 @@ SYMBOLS = [
     "tango_op_linear_ex", "tango_debug_linear_ex_check", "tango_op_conv2d_temb", "tango_op_conv2d_ups_temb",
     "tango_engine_denoise_guided", "tango_debug_denoise_guided_check", "tango_op_sched_guided",
     "tango_debug_attention_route", "tango_debug_attention_route_ld", "tango_op_attention_view",
+    "tango_engine_denoise_windows", "tango_debug_denoise_windows_check", "tango_engine_vae_decode_tiled_h",
+    "tango_op_sched_windows", "tango_op_mel_tile_blend",
 ]
 
 _lib = None
@@ -162,6 +172,12 @@ def load():
     lib.tango_engine_denoise_guided.argtypes = [vp, C.POINTER(DenoiseArgs), C.POINTER(GuidanceArgs), vp]
     lib.tango_debug_denoise_guided_check.argtypes = [C.POINTER(DenoiseArgs), C.POINTER(GuidanceArgs)]
     lib.tango_debug_denoise_guided_check.restype = C.c_char_p
+    lib.tango_engine_denoise_windows.argtypes = [vp, C.POINTER(DenoiseArgs), C.POINTER(WindowArgs), vp]
+    lib.tango_debug_denoise_windows_check.argtypes = [C.POINTER(DenoiseArgs), C.POINTER(WindowArgs)]
+    lib.tango_debug_denoise_windows_check.restype = C.c_char_p
+    lib.tango_engine_vae_decode_tiled_h.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
+    lib.tango_op_sched_windows.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci, cf, C.c_uint64, ci, ci, vp]
+    lib.tango_op_mel_tile_blend.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
     lib.tango_engine_unet_forward.argtypes = [vp, vp, i64, vp, vp, vp, ci, ci, vp]
     lib.tango_engine_unet_forward_music.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.tango_engine_vae_decode.argtypes = [vp, vp, vp, ci, vp]

@@ -484,6 +484,38 @@ struct SchedParams {
 static_assert(std::is_trivially_copyable<SchedParams>::value && sizeof(SchedParams) == 200,
               "SchedParams is memcpy'd to the device and copied by value in the kernels: its layout is fixed");
 
+// ---- long clips: MultiDiffusion windows in time (sched.hip; include/tango_engine.h tango_window_args_t) ----
+// The canvas is lat [B, C, H, W]; view v of V = (H - Hw) / s + 1 covers canvas rows [v s, v s + Hw); the UNet batch row of window v of
+// sample b is half * B * V + b * V + v (unconditional half first).  One definition of the geometry for every layer:
+struct WindowGeom { int H = 0, Hw = 0, s = 0, V = 0; };
+constexpr int kMaxWindows = 32;
+// why (canvas_h, window_h, stride) is no exact cover of at most kMaxWindows views (nullptr: it is; *g is then filled in).  Host only.
+const char* window_geom_refusal(int canvas_h, int window_h, int stride, WindowGeom* g);
+// the views that cover canvas row h, ascending: [lo, hi]
+__host__ __device__ inline void window_cover(const WindowGeom& g, int h, int* lo, int* hi) {
+  *lo = h >= g.Hw ? (h - g.Hw) / g.s + 1 : 0;
+  const int top = h / g.s;
+  *hi = top < g.V - 1 ? top : g.V - 1;
+}
+// The parameter block of a windowed call: the SchedParams of the canvas (B, HW = H * W, lat, noise: the canvas's; eps, xin: the window
+// batch's, B2 * V rows of Hw * W positions) beside the geometry.  A block of its own in device memory: SchedParams keeps its layout, and
+// a captured windowed step reads this block while a captured plain step reads the engine's SchedParams block.
+struct SchedWindowParams {
+  SchedParams p;
+  WindowGeom g;
+  int W = 0;
+  int noise_row0 = 0;                // loop index of the first entry of p.noise (the one-step hook passes the row of its step alone)
+};
+static_assert(std::is_trivially_copyable<SchedWindowParams>::value, "SchedWindowParams is memcpy'd to the device");
+// sched_window_kernel (rules 0 / 1): one thread per canvas position; the grid covers max_positions >= B * H * W
+int launch_sched_windows(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s);
+// canvas fp32 NCHW [B, C, H, W] -> T NHWC [rep * B * V, Hw * W, ld]: the windowed form of launch_nchw_to_nhwc (before step 0)
+int launch_window_gather(int dtype, const float* lat, void* xin, int64_t ld, int B, int C, int W, const WindowGeom& g, int rep, hipStream_t s);
+// canvas fp32 NCHW [B, C, H, W] -> fp32 NCHW [B * V, C, Hw, W] (the tiled VAE decode's input)
+int launch_window_gather_nchw(const float* lat, float* dst, int B, int C, int W, const WindowGeom& g, hipStream_t s);
+// tiles fp32 [B * V, g.Hw, F] (tile t at output rows t * g.s ...) -> out fp32 [B, g.H, F], cross-faded over the overlaps (g in mel rows)
+int launch_mel_tile_blend(const float* tiles, float* out, int B, int F, const WindowGeom& g, hipStream_t s);
+
 // The update step's arguments as the host sees them: what a denoise call (rows [0, num_rows)) and a one-step test hook (row `step` alone)
 // may pass.  Pointers are only asked whether they are null, except `coef` (HOST [num_rows][coef_w]) and `table` (HOST [table_rows][batch]).
 struct SchedArgs {
@@ -495,6 +527,9 @@ struct SchedArgs {
 };
 // the refusal without a prefix (the caller says "denoise: " or its own name), or nullptr.  Host only, no device needed.
 const char* sched_args_refusal(const SchedArgs& a);
+// the same for a windowed update (tango_engine_denoise_windows, tango_op_sched_windows): sched_args_refusal, then the multistep rule,
+// known latents, a guidance table or rescale, and a geometry that is no exact cover (*g is filled in when the answer is nullptr)
+const char* window_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, WindowGeom* g);
 // `dev_params` is a DEVICE copy of SchedParams; the grid covers max_positions >= B*HW (one thread per latent position).
 // `rule` (host copy of the block's rule) picks the kernel: 0 / 1 sched_step_kernel, 2 sched_multistep_kernel; `masked` their
 // inpainting variants (the blend for the next loop index fused after the update); `guided` the variants that read the guidance

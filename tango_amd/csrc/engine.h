@@ -169,6 +169,9 @@ struct UNetPlan : Plan {
   // cannot replay a loop that needs another; everything else is shared.  [guided]: the table / rescale variants, with the two
   // statistics launches in front of the update (a default call replays the [.][.][0] graphs: today's kernel sequence)
   StepGraphs graphs[2][2][2];
+  // a windowed call (Engine::denoise_windows) runs this plan's step program with sched_window_kernel as its update: graphs of its own,
+  // so that a plain call and a windowed call of one shape share the plan and each replays the graph that holds its own update kernel
+  StepGraphs wgraphs;
   // Two independent chains (round 5; Engine::denoise): a "dual" plan owns only the UNet input / output buffers of the whole batch; its
   // two children run the first and the second half of the samples (no op of the UNet crosses samples) as two branches of the captured
   // graph, so that one branch's dispatch gaps and kernel tails are filled by the other's kernels.  A child takes xin / eps from its
@@ -218,6 +221,9 @@ class Engine {
   int set_weight(const char* name, const float* dev, const int64_t* shape, int ndim);
   int finalize_weights();
   int denoise(const tango_denoise_args_t& a, const tango_guidance_args_t* g, hipStream_t s);   // g may be null: scalar guidance, no rescale
+  // long clips: a.latent_h is the canvas height, the UNet runs (cfg ? 2 : 1) * a.batch * V windows of height w.window_h per step
+  int denoise_windows(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s);
+  int vae_decode_tiled(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s);
   struct Cond { const float* emb = nullptr; const uint8_t* mask = nullptr; int len = 0; const uint8_t* mask_host = nullptr; };
   // latent_h: the latent height of the call, 0 = cfg.latent_h (the width is always cfg.latent_w)
   int unet_forward(const float* sample, int64_t t, const Cond (&c)[3], float* out, int B2, int latent_h, hipStream_t s);
@@ -326,6 +332,7 @@ class Engine {
   int* d_step = nullptr;
   unsigned* d_sync = nullptr;   // barrier words of the cooperative kernels (common.h: coop_sync_words()), zeroed once at init
   SchedParams* d_sched = nullptr;   // device copy of the current call's scheduler parameter block
+  SchedWindowParams* d_wsched = nullptr;   // ... of the current windowed call's block (captured windowed steps read this one)
   int64_t* d_ts = nullptr;       // [max_steps]
   float* d_coef = nullptr;       // [max_steps][16] (DDPM / DDIM rows use the first 8 floats of a packed [N][8] table)
   float* d_bcoef = nullptr;      // [max_steps][2] add_noise scalars of the masked loop's blend (tango_denoise_args_t.blend_coef)
@@ -400,8 +407,12 @@ class Engine {
   bool cfg_shared_ok(int B2, int n_short) const;
   // how a guidance / plain batch of B2 UNet rows runs; profile_unet() asks with two_chains_ok = false
   UNetMode unet_mode_for(int B2, int n_short, bool cfg_on, bool two_chains_ok) const;
-  int run_step(const UNetPlan& P, int rule, bool masked, bool guided, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
-  int capture_steps(const UNetPlan& P, int rule, bool masked, bool guided, int n, hipGraph_t* g_out, hipGraphExec_t* x_out);
+  // which update closes a step: the kernel is fixed when a step is captured
+  struct StepKind { int rule = 0; bool masked = false, guided = false, windowed = false; };
+  int run_step(const UNetPlan& P, const StepKind& k, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
+  int capture_steps(const UNetPlan& P, const StepKind& k, int n, hipGraph_t* g_out, hipGraphExec_t* x_out);
+  // the loop of a denoise call once its blocks, conditions and first UNet input are in place: captures what G lacks, replays or runs eagerly
+  int run_loop(UNetPlan& P, StepGraphs& G, const StepKind& k, int num_steps, bool use_graph, hipStream_t s);
   int single_key_prefix(const uint8_t* mask_dev, const uint8_t* mask_host, int B2, int L, std::vector<int>& key0, hipStream_t s);
   int build_unet(UNetPlan& P, Arena& A, bool record);
   int get_vae_plan(int B, int H, VaePlan** out);

@@ -545,15 +545,17 @@ void Engine::free_plan(Plan& P) {
     //  a replay of this plan may still be in flight -- denoise() no longer waits for its stream, and destroying an
     // executing graph is not safe on HIP: drain the device first (hipFree would do so anyway, but only AFTER the destroy)
     (void)hipDeviceSynchronize();
+    auto drop = [](StepGraphs& g) {
+      if (g.exec) (void)hipGraphExecDestroy(g.exec);
+      if (g.graph) (void)hipGraphDestroy(g.graph);
+      if (g.exec_k) (void)hipGraphExecDestroy(g.exec_k);
+      if (g.graph_k) (void)hipGraphDestroy(g.graph_k);
+      g = StepGraphs();
+    };
     for (auto& plane : U.graphs)
       for (auto& row : plane)
-        for (StepGraphs& g : row) {
-          if (g.exec) (void)hipGraphExecDestroy(g.exec);
-          if (g.graph) (void)hipGraphDestroy(g.graph);
-          if (g.exec_k) (void)hipGraphExecDestroy(g.exec_k);
-          if (g.graph_k) (void)hipGraphDestroy(g.graph_k);
-          g = StepGraphs();
-        }
+        for (StepGraphs& g : row) drop(g);
+    drop(U.wgraphs);
     for (auto& c : U.child) if (c) { free_plan(*c); c.reset(); }
   }
   // a slab may still be read by work queued on a stream: hipFree synchronises the device before it releases memory
@@ -1001,6 +1003,7 @@ int Engine::init() {
     const int temb = cfg.unet_channels[0] * 4;
     d_step = (int*)dmalloc(256);
     d_sched = (SchedParams*)dmalloc(sizeof(SchedParams));
+    d_wsched = (SchedWindowParams*)dmalloc(sizeof(SchedWindowParams));
     d_ts = (int64_t*)dmalloc((size_t)max_steps * 8);
     d_coef = (float*)dmalloc((size_t)max_steps * 16 * 4);
     d_bcoef = (float*)dmalloc((size_t)max_steps * 2 * 4);
@@ -1488,7 +1491,9 @@ static int grow_device_buffer(T** buf, size_t* have, size_t need, size_t unit, c
 
 // one denoise step = UNet forward, fused CFG combine + scheduler update (writes the next UNet input), step counter++
 // (two chains: fork after the previous step's update, join before this step's); guided: the statistics of the rescale in between
-int Engine::run_step(const UNetPlan& P, int rule, bool masked, bool guided, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join) {
+// windowed: the update is sched_window_kernel on the engine's windowed block (one thread per canvas position, never more than the window
+// batch has positions, so one grid serves every (batch, views, stride) split of the plan's rows)
+int Engine::run_step(const UNetPlan& P, const StepKind& k, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join) {
   if (P.mode != UNetMode::TwoChains) {
     TANGO_TRY(P.step.run(st));
   } else {
@@ -1499,19 +1504,23 @@ int Engine::run_step(const UNetPlan& P, int rule, bool masked, bool guided, hipS
     TANGO_HIP(hipEventRecord(join, st2));
     TANGO_HIP(hipStreamWaitEvent(st, join, 0));
   }
-  if (guided) TANGO_TRY(launch_guidance_stats(d_sched, P.B2 / 2, P.H * cfg.latent_w, st));
-  TANGO_TRY(launch_sched_step(dt, d_sched, P.B2 * P.H * cfg.latent_w, st, rule, masked, guided));
+  if (k.windowed) {
+    TANGO_TRY(launch_sched_windows(dt, d_wsched, P.B2 * P.H * cfg.latent_w, st));
+    return launch_step_inc(d_step, st);
+  }
+  if (k.guided) TANGO_TRY(launch_guidance_stats(d_sched, P.B2 / 2, P.H * cfg.latent_w, st));
+  TANGO_TRY(launch_sched_step(dt, d_sched, P.B2 * P.H * cfg.latent_w, st, k.rule, k.masked, k.guided));
   return launch_step_inc(d_step, st);
 }
 
 // capture `n` steps; every per-step quantity is read through d_step / d_sched
 // (captured on an engine-owned stream: the caller's stream may be the legacy null stream,
 // which cannot be captured; the instantiated graph is then launched on the caller's stream)
-int Engine::capture_steps(const UNetPlan& P, int rule, bool masked, bool guided, int n, hipGraph_t* g_out, hipGraphExec_t* x_out) {
+int Engine::capture_steps(const UNetPlan& P, const StepKind& k, int n, hipGraph_t* g_out, hipGraphExec_t* x_out) {
   if (!cap_stream) TANGO_HIP(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
   TANGO_HIP(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeRelaxed));
   int rc = 0;
-  for (int i = 0; i < n && rc == 0; ++i) rc = run_step(P, rule, masked, guided, cap_stream, cap_stream2, ev_fork, ev_join);
+  for (int i = 0; i < n && rc == 0; ++i) rc = run_step(P, k, cap_stream, cap_stream2, ev_fork, ev_join);
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(cap_stream, &g);
   if (rc != 0) return rc;
@@ -1580,42 +1589,99 @@ int Engine::denoise(const tango_denoise_args_t& a, const tango_guidance_args_t* 
   // the blend of loop index 0 on the initial latents (ddim.py:210-217 runs it before every UNet call, the first one included); the
   // later ones are fused into the captured update kernel
   if (mk) TANGO_TRY(launch_inpaint_blend0(dt, d_sched, B * HW, s));
+  // the update kernel is fixed at capture: each (masked, multistep, guided) triple replays graphs of its own, captured once per plan
+  StepKind k;
+  k.rule = a.rule; k.masked = mk; k.guided = gd;
+  return run_loop(*P, P->graphs[mk][ms][gd], k, a.num_steps, a.use_graph != 0, s);
+}
 
-  if (mode == UNetMode::TwoChains && !ev_fork) {
+int Engine::run_loop(UNetPlan& P, StepGraphs& G, const StepKind& k, int num_steps, bool use_graph, hipStream_t s) {
+  if (P.mode == UNetMode::TwoChains && !ev_fork) {
     TANGO_HIP(hipStreamCreateWithFlags(&cap_stream2, hipStreamNonBlocking));
     TANGO_HIP(hipStreamCreateWithFlags(&aux_stream, hipStreamNonBlocking));
     for (hipEvent_t* e : {&ev_fork, &ev_join, &ev_fork_e, &ev_join_e}) TANGO_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
-  // the update kernel is fixed at capture: each (masked, multistep, guided) triple replays graphs of its own, captured once per plan
-  StepGraphs& G = P->graphs[mk][ms][gd];
-  if (a.use_graph && !G.exec) TANGO_TRY(capture_steps(*P, a.rule, mk, gd, 1, &G.graph, &G.exec));
+  if (use_graph && !G.exec) TANGO_TRY(capture_steps(P, k, 1, &G.graph, &G.exec));
   // k steps per replay (round 5; north_star: "the 100-200 denoise steps captured as a hipGraph"): the same kernel sequence captured k
   // times back to back -- every per-step quantity is read through the device-side step counter, so a k-step graph is just k copies.
   // What it removes is the host-side launch of every replay and the gap between two replays, which only shows at small batches
   // (B = 1: a 7-ms step); the remainder of num_steps / k runs on the one-step graph.
-  int kk = tuning().graph_steps > 0 ? tuning().graph_steps : graph_steps_default(B2);
-  if (kk > a.num_steps) kk = a.num_steps;
-  if (a.use_graph && kk > 1 && (!G.exec_k || G.k_steps != kk)) {
+  int kk = tuning().graph_steps > 0 ? tuning().graph_steps : graph_steps_default(P.B2);
+  if (kk > num_steps) kk = num_steps;
+  if (use_graph && kk > 1 && (!G.exec_k || G.k_steps != kk)) {
     if (G.exec_k) { TANGO_HIP(hipStreamSynchronize(s)); (void)hipGraphExecDestroy(G.exec_k); (void)hipGraphDestroy(G.graph_k); G.exec_k = nullptr; G.graph_k = nullptr; }
-    TANGO_TRY(capture_steps(*P, a.rule, mk, gd, kk, &G.graph_k, &G.exec_k));
+    TANGO_TRY(capture_steps(P, k, kk, &G.graph_k, &G.exec_k));
     G.k_steps = kk;
   }
   TANGO_HIP(hipEventRecord(ev0, s));
   {
     int i = 0;
-    if (a.use_graph && kk > 1)
-      for (; i + kk <= a.num_steps; i += kk) TANGO_HIP(hipGraphLaunch(G.exec_k, s));
-    for (; i < a.num_steps; ++i) {
-      if (a.use_graph) TANGO_HIP(hipGraphLaunch(G.exec, s));
-      else TANGO_TRY(run_step(*P, a.rule, mk, gd, s, aux_stream, ev_fork_e, ev_join_e));
+    if (use_graph && kk > 1)
+      for (; i + kk <= num_steps; i += kk) TANGO_HIP(hipGraphLaunch(G.exec_k, s));
+    for (; i < num_steps; ++i) {
+      if (use_graph) TANGO_HIP(hipGraphLaunch(G.exec, s));
+      else TANGO_TRY(run_step(P, k, s, aux_stream, ev_fork_e, ev_join_e));
     }
   }
   TANGO_HIP(hipEventRecord(ev1, s));
-  last_steps = a.num_steps;
+  last_steps = num_steps;
   last_step_gflop = 0.0;
-  for (const UNetPlan* q : {(const UNetPlan*)P, (const UNetPlan*)P->child[0].get(), (const UNetPlan*)P->child[1].get()})
+  for (const UNetPlan* q : {(const UNetPlan*)&P, (const UNetPlan*)P.child[0].get(), (const UNetPlan*)P.child[1].get()})
     if (q) for (double f : q->step.flops) last_step_gflop += f / 1e9;
   return 0;
+}
+
+// Long clips (MultiDiffusion windows in time; sched.hip sched_window_kernel): the V windows of every sample are rows of the ordinary UNet
+// plan of (B2 * V, L, ..., window_h), whose step program runs unchanged; the update averages the views on the canvas and writes the next
+// input of every window.  prompt_embeds / prompt_mask hold B2 * V rows in the window batch's order (row half * B * V + b * V + v), so the
+// single-key prefix and the condition binding are those of a plain call of that batch.
+static int check_window_args(const tango_denoise_args_t& a, const tango_window_args_t& w, WindowGeom* g) {
+  SchedArgs c;
+  c.rule = a.rule; c.coef = a.coef; c.coef_w = a.coef_width ? a.coef_width : 8; c.num_rows = c.row1 = a.num_steps;
+  c.noise = a.noise != nullptr; c.clip = a.clip_sample != 0;
+  c.known = a.known_latents; c.mask = a.latent_mask; c.blend_coef = a.blend_coef; c.blend_noise = a.blend_noise;
+  if (const char* why = window_args_refusal(c, a.latent_h, w.window_h, w.stride, g)) TANGO_FAIL(std::string("denoise_windows: ") + why);
+  return 0;
+}
+
+int Engine::denoise_windows(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) {
+  WindowGeom g;
+  TANGO_TRY(check_window_args(a, w, &g));
+  if (a.batch <= 0) TANGO_FAIL("denoise_windows: batch must be positive");
+  int Hw;
+  TANGO_TRY(resolve_h(w.window_h, true, &Hw));       // window_h is a UNet height of this configuration
+  const bool cfg_on = a.guidance_scale > 1.0f;
+  const int B = a.batch, rows = (cfg_on ? 2 : 1) * B * g.V;
+  UNetPlan* P;
+  std::vector<int> key0;
+  const int ns = single_key_prefix(a.prompt_mask, a.prompt_mask_host, rows, a.text_len, key0, s);
+  const UNetMode mode = unet_mode_for(rows, ns, cfg_on, true);
+  TANGO_TRY(get_unet_plan(rows, a.text_len, a.beat_len, a.chord_len, ns, Hw, &P, mode));
+  TANGO_TRY(ensure_temb(a.timesteps, a.num_steps, s));
+  const int W = cfg.latent_w, C = cfg.unet_in_channels;
+  SchedWindowParams wp;
+  SchedParams& sp = wp.p;
+  sp.lat = a.latents; sp.eps = P->eps; sp.xin = P->xin; sp.xin_ld = 8;
+  sp.noise = a.noise; sp.coef = d_coef; sp.step_ptr = d_step;
+  sp.B = B; sp.C = C; sp.HW = g.H * W; sp.cfg = cfg_on ? 1 : 0; sp.guidance = a.guidance_scale;
+  sp.pred_type = a.prediction_type; sp.rule = a.rule; sp.clip = a.clip_sample; sp.clip_range = a.clip_sample_range;
+  sp.seed = a.seed; sp.sample_offset = a.sample_offset; sp.num_steps = a.num_steps;
+  wp.g = g; wp.W = W;
+  TANGO_TRY(stage_h2d(d_coef, a.coef, (size_t)a.num_steps * 8 * 4, s));
+  TANGO_TRY(stage_h2d(d_wsched, &wp, sizeof(SchedWindowParams), s));
+  TANGO_HIP(hipMemsetAsync(d_step, 0, 4, s));
+  {
+    Cond c[3];
+    c[0].emb = a.prompt_embeds; c[0].mask = a.prompt_mask; c[0].len = a.text_len;
+    c[1].emb = a.beat_embeds; c[1].mask = a.beat_mask; c[1].len = a.beat_len;
+    c[2].emb = a.chord_embeds; c[2].mask = a.chord_mask; c[2].len = a.chord_len;
+    TANGO_TRY(bind_conditions(*P, c, key0, s));
+  }
+  TANGO_TRY(launch_fill_zero(P->xin, (size_t)rows * Hw * W * 8 * esz, s));
+  TANGO_TRY(launch_window_gather(dt, a.latents, P->xin, 8, B, C, W, g, cfg_on ? 2 : 1, s));
+  StepKind k;
+  k.rule = a.rule; k.windowed = true;
+  return run_loop(*P, P->wgraphs, k, a.num_steps, a.use_graph != 0, s);
 }
 
 int Program::run_profiled(hipStream_t s, std::string& report) const {
@@ -1911,6 +1977,28 @@ int Engine::vae_decode(const float* lat, float* mel, int B, int latent_h, hipStr
   return 0;
 }
 
+// Tiled decode of a long clip (the fork's AutoencoderKL.tiled_decode, mustango/diffusers/src/diffusers/models/autoencoder_kl.py:255-296): the V
+// latent windows of every sample go through the ordinary decoder plan of (B * V, window_h) in one run, then one blend kernel cross-fades
+// the decoded tiles into mel [B, 1, canvas_h << (levels - 1), F].  All V views are decoded, overlaps included: the decoder is about 1 %
+// of a pass, and its mid-block attention stays at the window's size whatever the clip length.
+int Engine::vae_decode_tiled(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s) {
+  if (cfg.vae_levels <= 0) TANGO_FAIL("engine: VAE not configured");
+  if (cfg.vae_out_ch != 1) TANGO_FAIL("engine: VAE out_ch must be 1 (NHWC == NCHW at the boundary)");
+  if (B <= 0) TANGO_FAIL("vae_decode_tiled: batch must be positive");
+  WindowGeom g;
+  if (const char* why = window_geom_refusal(canvas_h, window_h, stride, &g)) TANGO_FAIL(std::string("vae_decode_tiled: ") + why);
+  int Hw;
+  TANGO_TRY(resolve_h(window_h, false, &Hw));
+  VaePlan* P;
+  TANGO_TRY(get_vae_plan(B * g.V, Hw, &P));
+  TANGO_TRY(launch_window_gather_nchw(lat, (float*)P->in, B, cfg.vae_embed_dim, cfg.latent_w, g, s));
+  TANGO_TRY(P->prog.run(s));
+  const int up = cfg.vae_levels - 1;
+  WindowGeom gm;                                   // the same geometry in mel rows
+  gm.H = g.H << up; gm.Hw = g.Hw << up; gm.s = g.s << up; gm.V = g.V;
+  return launch_mel_tile_blend((const float*)P->out, mel, B, cfg.latent_w << up, gm, s);
+}
+
 // ================================================================================================
 // mel-VAE encoder plan (autoencoder.py:52-58 -> modules.py:519-543 Encoder.forward -> quant_conv): mel [B, 1, 4H, 4W] fp32 ->
 // moments [B, 2 * embed_dim, H, W] fp32 NCHW.  Same operators as the decoder; the Downsample convs are stride-2 gathers with the
@@ -2174,6 +2262,23 @@ const char* tango_debug_denoise_guided_check(const tango_denoise_args_t* a, cons
   if (!a) return "denoise: null args";
   if (tango::check_denoise_args(*a, g) != 0) msg = tango_last_error();
   return msg.c_str();
+}
+int tango_engine_denoise_windows(tango_engine_t* h, const tango_denoise_args_t* a, const tango_window_args_t* w, void* stream) {
+  if (!h || !a || !w) { tango::set_error("denoise_windows: null args"); return -1; }
+  return h->e->denoise_windows(*a, *w, (hipStream_t)stream);
+}
+const char* tango_debug_denoise_windows_check(const tango_denoise_args_t* a, const tango_window_args_t* w) {
+  static thread_local std::string msg;
+  msg.clear();
+  if (!a || !w) return "denoise_windows: null args";
+  tango::WindowGeom g;
+  if (tango::check_window_args(*a, *w, &g) != 0) msg = tango_last_error();
+  return msg.c_str();
+}
+int tango_engine_vae_decode_tiled_h(tango_engine_t* h, const float* latents, float* mel, int batch, int canvas_h, int window_h, int stride,
+                                    void* stream) {
+  if (!h || !latents || !mel) { tango::set_error("vae_decode_tiled: null argument"); return -1; }
+  return h->e->vae_decode_tiled(latents, mel, batch, canvas_h, window_h, stride, (hipStream_t)stream);
 }
 int tango_engine_unet_forward_h(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
                                 const uint8_t* prompt_mask, float* out, int batch2, int text_len, int latent_h, void* stream) {

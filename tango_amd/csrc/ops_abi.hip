@@ -1015,6 +1015,53 @@ int tango_op_sched_guided(float* latents, const float* model_out_nchw, const flo
   return op_sched(o);
 }
 
+int tango_op_sched_windows(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H, int W,
+                           int Hw, int sw, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
+                           int sample_offset, int step, void* stream) {
+  const std::string w("op_sched_windows");
+  if (B <= 0 || C <= 0 || W <= 0 || step < 0 || sample_offset < 0) TANGO_FAIL(w + ": bad sizes");
+  if (!latents || !model_out_nchw || !coef8) TANGO_FAIL(w + ": latents, model_out_nchw and coef8 are required");
+  SchedArgs c;                      // the engine's own rules; the single row is the row of this step
+  c.rule = rule; c.coef = coef8; c.coef_w = 8; c.num_rows = 1; c.row0 = 0; c.row1 = 1; c.noise = noise != nullptr; c.clip = clip != 0;
+  WindowGeom g;
+  if (const char* why = window_args_refusal(c, H, Hw, sw, &g)) TANGO_FAIL(w + ": " + why);
+  if (!noise && C % 4 != 0) TANGO_FAIL(w + ": the Philox stream draws four channels at a time: C must be a multiple of 4");
+  const int B2 = cfg ? 2 * B : B, rows = B2 * g.V, win = Hw * W;
+  if ((int64_t)rows * win * C >= ((int64_t)1 << 31)) TANGO_FAIL(w + ": B2 * V * Hw * W * C must stay below 2^31");
+  hipStream_t s = (hipStream_t)stream; Scratch sc;
+  float* eps = (float*)sc.get((size_t)rows * win * C * 4);
+  float* xin = (float*)sc.get((size_t)rows * win * C * 4);
+  float* dcoef = (float*)sc.get((size_t)(step + 1) * 8 * 4);
+  int* dstep = (int*)sc.get(256);
+  SchedWindowParams* dp = (SchedWindowParams*)sc.get(sizeof(SchedWindowParams));
+  if (!eps || !xin || !dcoef || !dstep || !dp) TANGO_FAIL(w + ": alloc");
+  TANGO_TRY(launch_nchw_to_nhwc(DT_F32, model_out_nchw, eps, C, rows, C, win, 1, 1.0f, s));
+  TANGO_HIP(hipMemcpyAsync(dcoef + (size_t)step * 8, coef8, 8 * 4, hipMemcpyHostToDevice, s));
+  TANGO_HIP(hipMemcpyAsync(dstep, &step, 4, hipMemcpyHostToDevice, s));
+  SchedWindowParams wp;
+  SchedParams& p = wp.p;
+  p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = C; p.noise = noise; p.coef = dcoef; p.step_ptr = dstep;
+  p.B = B; p.C = C; p.HW = H * W; p.cfg = cfg ? 1 : 0; p.guidance = guidance; p.pred_type = pred_type; p.rule = rule;
+  p.clip = clip; p.clip_range = clip_range; p.seed = seed; p.sample_offset = sample_offset; p.num_steps = step + 1;
+  wp.g = g; wp.W = W; wp.noise_row0 = step;
+  TANGO_HIP(hipMemcpyAsync(dp, &wp, sizeof(SchedWindowParams), hipMemcpyHostToDevice, s));
+  TANGO_TRY(launch_sched_windows(DT_F32, dp, B * H * W, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_mel_tile_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream) {
+  if (B <= 0 || V <= 0 || F <= 0 || !tiles || !out) TANGO_FAIL("op_mel_tile_blend: bad arguments");
+  if ((int64_t)V * Hw4 > ((int64_t)1 << 24)) TANGO_FAIL("op_mel_tile_blend: V * Hw4 too large");
+  WindowGeom g;
+  if (Hw4 <= 0 || s4 < 1 || s4 > Hw4) TANGO_FAIL("op_mel_tile_blend: 1 <= s4 <= Hw4 is required");
+  if (const char* why = window_geom_refusal((V - 1) * s4 + Hw4, Hw4, s4, &g)) TANGO_FAIL(std::string("op_mel_tile_blend: ") + why);
+  hipStream_t s = (hipStream_t)stream;
+  TANGO_TRY(launch_mel_tile_blend(tiles, out, B, F, g, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 int tango_op_philox_normal(float* out, int B, int C, int HW, int step, uint64_t seed, int sample_offset, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   TANGO_TRY(launch_philox_normal(out, B, C, HW, step, seed, sample_offset, s));

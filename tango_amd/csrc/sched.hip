@@ -1,5 +1,6 @@
 // The denoise loop's own kernels (fused CFG combine + scheduler update for DDPM / DDIM and multistep DPM-Solver with its masked and guided
-// variants, guidance statistics, inpainting blend, step counter, Philox, fused latent encode), their launchers and their argument checker.
+// variants, guidance statistics, inpainting blend, step counter, Philox, fused latent encode, the windowed update of long clips with its
+// gathers and the mel tile blend), their launchers and their argument checkers.
 #include <cmath>
 #include "common.h"
 #include "tango_engine.h"
@@ -222,6 +223,196 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __re
   }
   // the last workgroup to get here could bump the step counter, but every block of THIS launch and of the next UNet
   // launch reads it: the increment stays a separate 1-thread launch (captured in the same hipGraph, engine.hip)
+}
+
+// ------------------------------------------------------------------------------------------
+// Long clips: MultiDiffusion (Bar-Tal et al. 2023) windows in time, fused into the update.  The fork's panorama pipeline
+// (mustango/diffusers/src/diffusers/pipelines/stable_diffusion/pipeline_stable_diffusion_panorama.py:442-456 get_views, :614-652 the
+// per-step loop value += step(view); count += 1; latents = value / count) steps every view on its own and averages.  Here the views
+// of a clip are rows of one UNet batch (common.h WindowGeom) and this kernel closes the step: one thread per CANVAS position
+// (b, h, w), per channel
+//   d_v = sched_step_kernel's `prev` before its sig * nz term, from rows (b, v) of eps at window position (h - v s, w)   v in cover(h), ascending
+//   acc = 0; acc = acc + d_v;   r = acc / |cover(h)|   (IEEE division);   if sig > 0: r = r + sig * nz
+// with the same fp32 operations in the same order (no FMA contraction).  r goes to the canvas and, as T, to every window row of the
+// next UNet input that covers h, in both CFG halves.  V = 1: (0 + d) / 1 is exact, the step is sched_step_kernel's bit for bit.
+// Two deliberate deviations from the fork: (1) the views must cover the canvas exactly ((H - Hw) % s == 0 is the caller's to meet; get_views
+// floors and leaves a tail of rows with count == 0); (2) nz is ONE draw per canvas element -- injected noise[step][b, c, h, w] or Philox with
+// the canvas position as the counter's hw -- where the fork's loop would average V independent draws and shrink the variance of a
+// stochastic sampler's step noise by |cover(h)|.  With sig == 0 (DDIM eta = 0, the last DDPM step) it is the fork's loop.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowParams* __restrict__ pp) {
+#pragma clang fp contract(off)
+  const SchedParams p = pp->p;
+  const WindowGeom g = pp->g;
+  const int W = pp->W, noise_row0 = pp->noise_row0;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.B * p.HW) return;
+  const int b = idx / p.HW, hw = idx - b * p.HW;
+  const int h = hw / W, w = hw - h * W;
+  int v_lo, v_hi;
+  window_cover(g, h, &v_lo, &v_hi);
+  const float cnt = (float)(v_hi - v_lo + 1);
+  const int step = *p.step_ptr;
+  const float* cf = p.coef + step * 8;
+  const float sa = cf[0], sb = cf[1], c0 = cf[2], c1 = cf[3], sig = cf[4], sap = cf[5], dirc = cf[6];
+  const int C = p.C;
+  const int64_t win = (int64_t)g.Hw * W;            // positions of one window
+  const int64_t half = (int64_t)p.B * g.V * win;    // positions of one CFG half of the window batch
+  float nrm[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int c = 0; c < C; ++c) {
+    float* lp = p.lat + ((int64_t)b * C + c) * p.HW + hw;
+    const float x = *lp;
+    float acc = 0.0f;
+    for (int v = v_lo; v <= v_hi; ++v) {
+      const int64_t pos = ((int64_t)b * g.V + v) * win + (int64_t)(h - v * g.s) * W + w;
+      float o = p.eps[pos * C + c];
+      if (p.cfg) { const float dlt = p.eps[(half + pos) * C + c] - o; const float gd = p.guidance * dlt; o = o + gd; }   // models.py:246
+      float x0;
+      if (p.pred_type == 0) { const float m0 = sb * o; const float d0 = x - m0; x0 = d0 / sa; }   // epsilon
+      else if (p.pred_type == 1) x0 = o;                                                          // sample
+      else { const float m0 = sa * x; const float m1 = sb * o; x0 = m0 - m1; }                    // v_prediction
+      if (p.clip) x0 = fminf(fmaxf(x0, -p.clip_range), p.clip_range);
+      float d;
+      if (p.rule == 0) {
+        const float m0 = c0 * x0; const float m1 = c1 * x; d = m0 + m1;
+      } else {
+        float e;
+        if (p.pred_type == 0) e = o;
+        else if (p.pred_type == 1) { const float m0 = sa * x0; const float d0 = x - m0; e = d0 / sb; }
+        else { const float m0 = sa * o; const float m1 = sb * x; e = m0 + m1; }
+        const float m0 = sap * x0; const float m1 = dirc * e; d = m0 + m1;
+      }
+      acc = acc + d;
+    }
+    float r = acc / cnt;
+    if (sig > 0.f) {
+      float nz;
+      if (p.noise) {
+        nz = p.noise[(int64_t)(step - noise_row0) * p.B * C * p.HW + ((int64_t)b * C + c) * p.HW + hw];
+      } else {
+        if ((c & 3) == 0) philox_normal4(hw, c >> 2, p.sample_offset + b, step, p.seed, nrm);   // one draw per 4 channels
+        nz = nrm[c & 3];
+      }
+      const float m2 = sig * nz; r = r + m2;
+    }
+    *lp = r;
+    const T tv = from_f<T>(r);
+    for (int v = v_lo; v <= v_hi; ++v) {
+      const int64_t pos = ((int64_t)b * g.V + v) * win + (int64_t)(h - v * g.s) * W + w;
+      ((T*)p.xin)[pos * p.xin_ld + c] = tv;
+      if (p.cfg) ((T*)p.xin)[(half + pos) * p.xin_ld + c] = tv;
+    }
+  }
+}
+
+// canvas fp32 NCHW -> the window batch T NHWC before step 0: the windowed form of nchw_to_nhwc_kernel with rep CFG halves.  One
+// thread per (window row, position); a canvas element that V' views cover is read V' times.
+template <typename T>
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ lat, T* __restrict__ xin, int64_t ld, int B, int C, int W,
+                                                            WindowGeom g, int rep) {
+  const int64_t win = (int64_t)g.Hw * W;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * g.V * win) return;
+  const int row = (int)(idx / win), pos = (int)(idx - (int64_t)row * win);
+  const int b = row / g.V, v = row - b * g.V;
+  const int64_t HW = (int64_t)g.H * W;
+  const int64_t src = (int64_t)v * g.s * W + pos;       // window position (y, w) is canvas position (v s + y, w)
+  for (int c = 0; c < C; ++c) {
+    const T t = from_f<T>(lat[((int64_t)b * C + c) * HW + src]);
+    for (int r = 0; r < rep; ++r) xin[((int64_t)r * B * g.V * win + idx) * ld + c] = t;
+  }
+}
+
+// the same gather fp32 NCHW -> fp32 NCHW [B * V, C, Hw, W] (the input of the tiled VAE decode): one thread per output element
+__global__ __launch_bounds__(256) void window_gather_nchw_kernel(const float* __restrict__ lat, float* __restrict__ dst, int B, int C, int W,
+                                                                 WindowGeom g) {
+  const int64_t win = (int64_t)g.Hw * W;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * g.V * C * win) return;
+  const int64_t rc = idx / win;                          // (b V + v) C + c
+  const int pos = (int)(idx - rc * win);
+  const int c = (int)(rc % C), row = (int)(rc / C);
+  const int b = row / g.V, v = row - b * g.V;
+  dst[idx] = lat[((int64_t)b * C + c) * g.H * W + (int64_t)v * g.s * W + pos];
+}
+
+// Cross-fade of the V decoded tiles of a clip (the fork's tiled VAE decode, mustango/diffusers/src/diffusers/models/autoencoder_kl.py
+// :198-201 blend_v, :255-296).  g counts mel rows: tile t holds output rows [t s, t s + Hw), E = Hw - s rows overlap.  The weight of
+// tile t at its local row y is min(1, (y + 0.5) / E) if t > 0, times min(1, (Hw - y - 0.5) / E) if t < V - 1 (both 1 when E == 0), and
+//   out[r] = (sum_t w_t tile_t) / (sum_t w_t)   over the covering tiles, ascending, each sum from 0, in fp32 without FMA contraction.
+// For s >= Hw / 2 two overlapping weights sum to 1: blend_v's linear ramp sampled at half-pixel centres; deeper overlaps use the same formula.
+__global__ __launch_bounds__(256) void mel_tile_blend_kernel(const float* __restrict__ tiles, float* __restrict__ out, int B, int F, WindowGeom g) {
+#pragma clang fp contract(off)
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * g.H * F) return;
+  const int f = (int)(idx % F);
+  const int64_t br = idx / F;
+  const int r = (int)(br % g.H), b = (int)(br / g.H);
+  int t_lo, t_hi;
+  window_cover(g, r, &t_lo, &t_hi);
+  const int E = g.Hw - g.s;
+  float num = 0.0f, den = 0.0f;
+  for (int t = t_lo; t <= t_hi; ++t) {
+    const int y = r - t * g.s;
+    float wt = 1.0f;
+    if (E > 0 && t > 0) { const float a = (float)y + 0.5f; wt = fminf(1.0f, a / (float)E); }
+    if (E > 0 && t < g.V - 1) { const float a = (float)(g.Hw - y) - 0.5f; const float u = fminf(1.0f, a / (float)E); wt = wt * u; }
+    const float m = wt * tiles[(((int64_t)b * g.V + t) * g.Hw + y) * F + f];
+    num = num + m;
+    den = den + wt;
+  }
+  out[idx] = num / den;
+}
+
+int launch_sched_windows(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
+  const dim3 grid((unsigned)((max_positions + 255) / 256));
+  switch (dtype) {
+    case DT_F32: hipLaunchKernelGGL(sched_window_kernel<float>, grid, dim3(256), 0, s, dev_params); break;
+    case DT_F16: hipLaunchKernelGGL(sched_window_kernel<f16>, grid, dim3(256), 0, s, dev_params); break;
+    case DT_BF16: hipLaunchKernelGGL(sched_window_kernel<bf16>, grid, dim3(256), 0, s, dev_params); break;
+    default: TANGO_FAIL("sched_windows: bad dtype");
+  }
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_window_gather(int dtype, const float* lat, void* xin, int64_t ld, int B, int C, int W, const WindowGeom& g, int rep, hipStream_t s) {
+  const dim3 grid((unsigned)(((int64_t)B * g.V * g.Hw * W + 255) / 256));
+  switch (dtype) {
+    case DT_F32: hipLaunchKernelGGL(window_gather_kernel<float>, grid, dim3(256), 0, s, lat, (float*)xin, ld, B, C, W, g, rep); break;
+    case DT_F16: hipLaunchKernelGGL(window_gather_kernel<f16>, grid, dim3(256), 0, s, lat, (f16*)xin, ld, B, C, W, g, rep); break;
+    case DT_BF16: hipLaunchKernelGGL(window_gather_kernel<bf16>, grid, dim3(256), 0, s, lat, (bf16*)xin, ld, B, C, W, g, rep); break;
+    default: TANGO_FAIL("window_gather: bad dtype");
+  }
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_window_gather_nchw(const float* lat, float* dst, int B, int C, int W, const WindowGeom& g, hipStream_t s) {
+  const dim3 grid((unsigned)(((int64_t)B * g.V * C * g.Hw * W + 255) / 256));
+  hipLaunchKernelGGL(window_gather_nchw_kernel, grid, dim3(256), 0, s, lat, dst, B, C, W, g);
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_mel_tile_blend(const float* tiles, float* out, int B, int F, const WindowGeom& g, hipStream_t s) {
+  const dim3 grid((unsigned)(((int64_t)B * g.H * F + 255) / 256));
+  hipLaunchKernelGGL(mel_tile_blend_kernel, grid, dim3(256), 0, s, tiles, out, B, F, g);
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+const char* window_geom_refusal(int canvas_h, int window_h, int stride, WindowGeom* g) {
+  if (window_h <= 0) return "window_h must be positive";
+  if (stride < 1 || stride > window_h) return "stride must be in [1, window_h]";
+  if (canvas_h < window_h) return "the canvas height must be at least window_h";
+  if ((canvas_h - window_h) % stride != 0)
+    return "the windows must cover the canvas exactly: (canvas height - window_h) must be a multiple of stride";
+  const int V = (canvas_h - window_h) / stride + 1;
+  if (V > kMaxWindows) return "at most 32 windows per clip";
+  if (g) { g->H = canvas_h; g->Hw = window_h; g->s = stride; g->V = V; }
+  return nullptr;
 }
 
 // test hook: the N(0,1) draws sched_step_kernel makes at loop index `step` for samples [sample_offset, sample_offset + B)
@@ -532,6 +723,19 @@ const char* sched_args_refusal(const SchedArgs& a) {
     for (size_t i = 0; i < n; ++i)
       if (!(a.table[i] >= 0.0f) || std::isinf(a.table[i])) return "guidance table entries must be finite and >= 0";
   }
+  return nullptr;
+}
+
+// Why the windowed update refuses these arguments: the multistep rule, what the plain update refuses, what else windows leave out, the geometry.
+const char* window_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, WindowGeom* g) {
+  if (a.rule == TANGO_RULE_DPM_MULTISTEP)           // first: whatever its table looks like
+    return "the multistep rule is not supported with windows (a per-view history has no reference behaviour): use DDPM or DDIM";
+  if (const char* why = sched_args_refusal(a)) return why;
+  if (a.known) return "known_latents (masked-latent inpainting) is not supported with windows";
+  if (a.guided && (a.table || a.rescale > 0.0f)) return "a guidance table or rescale is not supported with windows";
+  if (canvas_h <= 0) return "a windowed call states its canvas height (latent_h > 0)";
+  if (const char* why = window_geom_refusal(canvas_h, window_h, stride, g)) return why;
+  if (window_h % 8 != 0) return "window_h is not a UNet height";
   return nullptr;
 }
 

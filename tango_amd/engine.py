@@ -371,6 +371,104 @@ class Engine:
                 _lib.check(self.lib.tango_engine_denoise_guided(self._h, C.byref(a), C.byref(g), _stream_ptr()), "denoise")
         return latents
 
+    def _check_canvas(self, what, x, channels, window_h, stride):
+        """a long clip's canvas [B, channels, H, latent_w] against its windows, as _check_latents checks a plain call: `window_h` a
+        height of the duration grid, 1 <= stride <= window_h, and the V = (H - window_h) / stride + 1 <= 32 views cover the H rows
+        exactly.  Returns (H, window_h, stride, V)."""
+        hw = check_latent_h(window_h)
+        if int(stride) != stride or not 1 <= stride <= hw:
+            raise ValueError("stride %r must be an integer in [1, window_h = %d]" % (stride, hw))
+        stride = int(stride)
+        if x.dim() != 4 or tuple(x.shape[1::2]) != (channels, self._cfg.latent_w):
+            raise ValueError("%s must be [B, %d, H, %d], got %s" % (what, channels, self._cfg.latent_w, tuple(x.shape)))
+        H = x.shape[2]
+        if H < hw or (H - hw) % stride:
+            raise ValueError("%s of height %d is not covered exactly by windows of %d rows every %d rows: (H - window_h) must be a "
+                             "multiple of stride" % (what, H, hw, stride))
+        V = (H - hw) // stride + 1
+        if V > 32:
+            raise ValueError("%s of height %d needs %d windows: at most 32" % (what, H, V))
+        return H, hw, stride, V
+
+    def denoise_windows(self, latents, prompt_embeds, prompt_mask, timesteps, coef, guidance_scale, *, window_h, stride,
+                        prediction_type="v_prediction", rule="ddpm", clip_sample=False, clip_sample_range=1.0, noise=None, seed=0,
+                        sample_offset=0, use_graph=True, prompt_mask_host=None, known_latents=None, guidance_table=None,
+                        guidance_rescale=0.0):
+        """In-place denoise of a long clip's canvas `latents` [B, 8, H, 16] (fp32 cuda) as V = (H - window_h) / stride + 1 overlapping
+        windows of `window_h` rows (a height of the duration grid) every `stride` rows: MultiDiffusion in time (include/tango_engine.h
+        tango_window_args_t).  Each step runs the UNet on the (2 if guidance_scale > 1 else 1) * B * V windows as one batch and averages
+        the per-view updates on the canvas.  `prompt_embeds` / `prompt_mask` hold one row per WINDOW, row half * B * V + b * V + v
+        (`repeat_interleave(V, 0)` of each half of a plain call's rows); `noise` [N, B, 8, H, 16] is canvas-shaped, one draw per canvas
+        element.  `rule`: "ddpm" or "ddim"; the multistep rule, `known_latents`, a guidance table and a rescale are refused.  The
+        other arguments are Engine.denoise's.  With H == window_h the result is Engine.denoise's, bit for bit."""
+        assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
+        if rule == "dpmsolver":
+            raise ValueError("the multistep DPM-Solver rule is not supported with windows (a per-view history has no reference "
+                             "behaviour): use DDPM or DDIM")
+        if known_latents is not None:
+            raise ValueError("known_latents (masked-latent inpainting) is not supported with windows")
+        if guidance_table is not None or float(guidance_rescale) != 0.0:
+            raise ValueError("a guidance table or rescale is not supported with windows")
+        if self.unet_cfg.get("music"):
+            raise ValueError("denoise_windows serves the plain UNet: the Music UNet's conditions are not windowed")
+        H, hw, stride, V = self._check_canvas("latents", latents, self.unet_cfg["in_channels"], window_h, stride)
+        enc = self._f32(prompt_embeds)
+        mask = self._u8(prompt_mask)
+        mask_host = prompt_mask.to(torch.uint8).contiguous() if prompt_mask is not None and not prompt_mask.is_cuda else None
+        if mask_host is None and prompt_mask_host is not None and prompt_mask is not None:
+            if prompt_mask_host.is_cuda or tuple(prompt_mask_host.shape) != tuple(prompt_mask.shape):
+                raise ValueError("prompt_mask_host must be a CPU tensor of prompt_mask's shape %s" % (tuple(prompt_mask.shape),))
+            mask_host = prompt_mask_host.to(torch.uint8).contiguous()
+            mask = mask_host.to(self.device, non_blocking=True)      # one source of truth, as in denoise()
+        B = latents.shape[0]
+        rows = (2 if guidance_scale > 1.0 else 1) * B * V
+        self._check_cond("prompt_embeds (one row per window)", enc, mask, rows)
+        ts = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int64))
+        cf = np.ascontiguousarray(np.asarray(coef, dtype=np.float32))
+        if cf.shape != (len(ts), 8):
+            raise ValueError("rule %r takes a coefficient table [%d, 8], got %s" % (rule, len(ts), cf.shape))
+        if noise is not None:
+            noise = self._f32(noise)
+            if tuple(noise.shape) != (len(ts),) + tuple(latents.shape):
+                raise ValueError("noise must be [num_steps, %s], got %s" % (", ".join(map(str, latents.shape)), tuple(noise.shape)))
+        a = _lib.DenoiseArgs()
+        a.latents = latents.data_ptr()
+        a.prompt_embeds = enc.data_ptr()
+        a.prompt_mask = mask.data_ptr() if mask is not None else None
+        a.prompt_mask_host = mask_host.data_ptr() if mask_host is not None else None
+        a.batch, a.text_len, a.num_steps = B, enc.shape[1], len(ts)
+        a.timesteps, a.coef, a.coef_width = ts.ctypes.data, cf.ctypes.data, 8
+        a.guidance_scale = float(guidance_scale)
+        a.prediction_type = _lib.PRED[prediction_type]
+        a.rule = _lib.RULE[rule]
+        a.clip_sample = 1 if clip_sample else 0
+        a.clip_sample_range = float(clip_sample_range)
+        a.noise = noise.data_ptr() if noise is not None else None
+        a.seed, a.sample_offset = int(seed), int(sample_offset)
+        a.use_graph = 1 if use_graph else 0
+        a.latent_h = H
+        w = _lib.WindowArgs(window_h=hw, stride=stride)
+        why = self.lib.tango_debug_denoise_windows_check(C.byref(a), C.byref(w))
+        if why:
+            raise ValueError(why.decode())
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.tango_engine_denoise_windows(self._h, C.byref(a), C.byref(w), _stream_ptr()), "denoise_windows")
+        return latents
+
+    def vae_decode_tiled(self, latents, window_h, stride):
+        """a long clip's latents [B, embed_dim, H, 16] -> mel [B, 1, 4H, 64]: the V = (H - window_h) / stride + 1 windows are decoded as
+        one batch of B * V latents of height `window_h` and the decoded tiles cross-faded over their overlaps (include/tango_engine.h
+        tango_op_mel_tile_blend).  The same geometry rules as denoise_windows."""
+        z = self._f32(latents)
+        H, hw, stride, _ = self._check_canvas("vae_decode_tiled: latents", z, self.vae_cfg.get("embed_dim", 8), window_h, stride)
+        nl = len(self.vae_cfg["ch_mult"])
+        B = z.shape[0]
+        mel = torch.empty((B, self.vae_cfg["out_ch"], H << (nl - 1), z.shape[3] << (nl - 1)), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.tango_engine_vae_decode_tiled_h(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(mel.data_ptr()), B, H, hw,
+                                                                stride, _stream_ptr()), "vae_decode_tiled")
+        return mel
+
     def _check_inpaint(self, latents, n, known_latents, latent_mask, blend_coef, blend_noise):
         """host-side validation of denoise()'s masking arguments: None when the call is not masked, else the device / host copies the
         engine reads (known, mask, blend table, blend noise)"""

@@ -55,6 +55,45 @@ def check_latent_h(h):
     return int(h)
 
 
+#: latent rows per second (duration_to_latent_t_size, pipeline.py:94-95) and the most windows one long clip is cut into (the engine's limit)
+LATENT_ROWS_PER_SECOND, MAX_WINDOWS = 25.6, 32
+
+
+def long_geometry(duration, window=10.0, hop=5.0):
+    """A clip longer than `window` seconds as overlapping windows in time (MultiDiffusion; the fork's panorama get_views,
+    pipeline_stable_diffusion_panorama.py:442-456): `duration` s -> (H, Hw, s, V) in latent rows, the canvas height
+    H = int(duration * 25.6), the window height Hw = duration_geometry(window)[0], the stride s = hop * 25.6 -- an integer multiple
+    of 8 no larger than Hw -- and V = (H - Hw) / s + 1 <= 32 views.  The views must cover the canvas exactly, (H - Hw) % s == 0 (the
+    fork floors and leaves a tail no view covers): otherwise a ValueError names the nearest valid durations on both sides."""
+    try:
+        d, hp = float(duration), float(hop)
+    except (TypeError, ValueError):
+        raise ValueError("duration and hop must be numbers of seconds, got %r and %r" % (duration, hop))
+    hw = duration_geometry(window)[0]
+    s = hp * LATENT_ROWS_PER_SECOND
+    if not (s == int(s) and int(s) >= 8 and int(s) % 8 == 0):       # (NaN compares false)
+        raise ValueError("hop %r s is %r latent rows: the stride must be an integer multiple of 8 rows (0.3125 s)" % (hop, s))
+    s = int(s)
+    if s > hw:
+        raise ValueError("hop %r s exceeds the window of %r s: the windows would leave gaps" % (hop, window))
+    if not d > float(window):
+        raise ValueError("duration %r s does not exceed the window of %r s: generate() serves it" % (duration, window))
+    if not d * LATENT_ROWS_PER_SECOND < 2 ** 31:                    # (NaN and inf end here)
+        raise ValueError("duration %r s is not a clip length" % (duration,))
+    h = int(d * LATENT_ROWS_PER_SECOND + 1e-6)                      # (25.6 is no binary fraction: 1e-6 rows absorb the product's rounding)
+    k = (h - hw) // s
+    if (h - hw) % s or abs(d * LATENT_ROWS_PER_SECOND - h) > 1e-6:  # a fraction of a row is not rounded away silently
+        kk = min(max(k, 1), MAX_WINDOWS - 2)                         # at either end of the range: the two durations next to it
+        lo, hi = (hw + kk * s) / LATENT_ROWS_PER_SECOND, (hw + (kk + 1) * s) / LATENT_ROWS_PER_SECOND
+        raise ValueError("duration %r s is not window + k * hop (%r s + k * %r s): the neighbouring durations are %g and %g"
+                         % (duration, window, hop, lo, hi))
+    v = k + 1
+    if v > MAX_WINDOWS:
+        raise ValueError("duration %r s needs %d windows of %r s every %r s: at most %d (%g s)"
+                         % (duration, v, window, hop, MAX_WINDOWS, (hw + (MAX_WINDOWS - 1) * s) / LATENT_ROWS_PER_SECOND))
+    return h, hw, s, v
+
+
 def clip_duration(n_samples):
     """the smallest grid duration whose mel frames hold a 16 kHz clip of `n_samples` samples; 20 s for anything longer (the clip is
     then cut).  Unlike the reference's round_up_duration (pipeline.py:49-50), which always adds one more 2.5 s block -- a 5 s clip

@@ -14,7 +14,7 @@ from typing import List, Optional
 import torch
 
 from .engine import Engine, normalize_unet_config
-from .inpaint import check_latent_h, duration_geometry
+from .inpaint import check_latent_h, duration_geometry, long_geometry
 from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler  # noqa: F401  (re-exported like `from models import DDPMScheduler`)
 from .scheduler import DDIMInverseScheduler, cfg_enabled, check_guidance_rescale, from_diffusers, guidance_table
 
@@ -225,10 +225,16 @@ class AudioDiffusion:
         return torch.cat([halves[0][0], halves[1][0]]), host.to(dev), host
 
     # ---- latents -----------------------------------------------------------------------------
-    def prepare_latents(self, batch_size, inference_scheduler, num_channels_latents, dtype, device, latent_h=256):
+    def prepare_latents(self, batch_size, inference_scheduler, num_channels_latents, dtype, device, latent_h=256, long_h=None):
         """models.py:259-264 (global torch generator on `device`, like the reference).  `latent_h`: the latent height of the clip
-        length, tango_amd.inpaint.duration_geometry(duration)[0] (256 = 10 s)."""
-        shape = (batch_size, num_channels_latents, check_latent_h(latent_h), 16)
+        length, tango_amd.inpaint.duration_geometry(duration)[0] (256 = 10 s).  `long_h`: the canvas height of a long clip
+        (tango_amd.inpaint.long_geometry(duration)[0]) instead, which is not on that grid; `latent_h` is then not read."""
+        if long_h is not None:
+            if int(long_h) != long_h or long_h < 1:
+                raise ValueError("long_h must be a positive number of latent rows, got %r" % (long_h,))
+            shape = (batch_size, num_channels_latents, int(long_h), 16)
+        else:
+            shape = (batch_size, num_channels_latents, check_latent_h(latent_h), 16)
         latents = torch.randn(shape, device=device, dtype=dtype)
         return latents * inference_scheduler.init_noise_sigma
 
@@ -335,6 +341,65 @@ class AudioDiffusion:
             pm = pm.repeat_interleave(num_samples_per_prompt, 0)
         return self.inference_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, mask_host=host,
                                               duration=duration, guidance_rescale=guidance_rescale)
+
+    # ---- clips longer than 20 s: MultiDiffusion windows in time (the fork's pipeline_stable_diffusion_panorama.py:442-456, 614-652) ----
+    @torch.no_grad()
+    def inference_long_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3,
+                                       duration=30, window=10, hop=5, latents=None, noise=None, seed=None, sample_offset=0,
+                                       mask_host=None):
+        """inference_from_embeddings for a clip of `duration` > `window` seconds: the canvas [B, 8, H, 16] (H = int(duration * 25.6))
+        is denoised as V overlapping windows of `window` seconds every `hop` seconds (tango_amd.inpaint.long_geometry), every window
+        under its sample's text, the per-view updates averaged on the canvas at every step (Engine.denoise_windows).
+        `prompt_embeds` / `boolean_prompt_mask` as in inference_from_embeddings ([uncond; cond] with guidance): their rows are repeated
+        per window here.  `noise` [N, B, 8, H, 16] is canvas-shaped.  DDPM and DDIM schedulers; a DPM-Solver scheduler, a guidance
+        table and a rescale are refused."""
+        H, hw, stride, V = long_geometry(duration, window, hop)
+        if not isinstance(guidance_scale, (int, float)):
+            raise ValueError("a guidance table is not supported with windows: guidance_scale must be a scalar")
+        if not hasattr(inference_scheduler, "coef_table"):
+            inference_scheduler = from_diffusers(inference_scheduler)
+        if inference_scheduler.rule == "dpmsolver":
+            raise ValueError("the multistep DPM-Solver rule is not supported with windows (a per-view history has no reference "
+                             "behaviour): use DDPM or DDIM")
+        cfg_on = guidance_scale > 1.0
+        B = prompt_embeds.shape[0] // 2 if cfg_on else prompt_embeds.shape[0]
+        inference_scheduler.set_timesteps(num_steps, device=self.device)
+        if latents is None:
+            latents = self.prepare_latents(B, inference_scheduler, self.unet.config.in_channels, torch.float32, self.device, long_h=H)
+        latents = latents.to(self.device, torch.float32).contiguous().clone()
+        if latents.dim() != 4 or latents.shape[0] != B or latents.shape[2] != H:
+            raise ValueError("latents must be [%d, C, %d, W] for %r s, got %s" % (B, H, duration, tuple(latents.shape)))
+        if boolean_prompt_mask is None:
+            boolean_prompt_mask = torch.ones(prompt_embeds.shape[:2], dtype=torch.bool, device=prompt_embeds.device)
+        pe, pm, mask_host = self._pad_text(prompt_embeds.to(self.device), boolean_prompt_mask, mask_host)
+        # one row per window, row half * B * V + b * V + v: each half's rows repeated V times in place
+        pe, pm = pe.repeat_interleave(V, 0), pm.repeat_interleave(V, 0)
+        mask_host = mask_host.repeat_interleave(V, 0) if mask_host is not None else None
+        c = inference_scheduler.config
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.seed is None else (int(self.seed) << 20) + self._calls
+        self._calls += 1
+        self.engine.denoise_windows(latents, pe, pm, inference_scheduler.timesteps.cpu().numpy(), inference_scheduler.coef_table(),
+                                    guidance_scale, window_h=hw, stride=stride, prediction_type=c.prediction_type,
+                                    rule=inference_scheduler.rule, clip_sample=c.clip_sample,
+                                    clip_sample_range=getattr(c, "clip_sample_range", 1.0), noise=noise, seed=seed,
+                                    sample_offset=sample_offset, use_graph=self.use_graph, prompt_mask_host=mask_host)
+        return latents
+
+    @torch.no_grad()
+    def inference_long(self, prompt, inference_scheduler, num_steps=20, guidance_scale=3, num_samples_per_prompt=1, duration=30,
+                       window=10, hop=5, negative_prompt=None, seed=None, sample_offset=0):
+        """inference() for a clip longer than `window` seconds (inference_long_from_embeddings): latents [B*S, 8, int(duration * 25.6), 16]"""
+        long_geometry(duration, window, hop)
+        host = None
+        if cfg_enabled(guidance_scale):
+            pe, pm, host = self._encode_text_classifier_free(prompt, num_samples_per_prompt, negative_prompt)
+        else:
+            pe, pm = self.encode_text(prompt)
+            pe = pe.repeat_interleave(num_samples_per_prompt, 0)
+            pm = pm.repeat_interleave(num_samples_per_prompt, 0)
+        return self.inference_long_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, duration, window, hop,
+                                                   seed=seed, sample_offset=sample_offset, mask_host=host)
 
     # ---- masked-latent inpainting (audioldm/pipeline.py:249-301, ldm.py:724-818, ddim.py:207-233) ------------------------------
     @torch.no_grad()

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from .autoencoder import AutoencoderKL
-from .inpaint import clip_duration, duration_geometry, latent_mask, prepare_waveform
+from .inpaint import clip_duration, duration_geometry, latent_mask, long_geometry, prepare_waveform
 from .models import AudioDiffusion
 from .scheduler import SD21_SCHEDULER_CONFIG, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 from .scheduler import cfg_enabled, check_guidance_rescale, guidance_is_table
@@ -102,6 +102,37 @@ class Tango:
             mel = self.vae.decode_first_stage(latents)
             wave = self.vae.decode_to_waveform(mel)
         return wave[0]
+
+    #: UNet rows of one engine call of generate_long: the benchmarked batch, which is known to fit
+    LONG_MAX_ROWS = 64
+
+    def generate_long(self, prompt, duration, steps=100, guidance=3, samples=1, window=10, hop=5, negative_prompt=None, seed=None):
+        """ Generate `duration` > `window` seconds of audio for a single prompt string: MultiDiffusion in time.  The clip is denoised as
+        V overlapping windows of `window` seconds (a length of generate()'s grid) every `hop` seconds, averaged on one latent canvas at
+        every step (AudioDiffusion.inference_long), decoded window by window with a cross-fade of the overlaps
+        (Engine.vae_decode_tiled) and vocoded in one piece.  `duration` must be window + k * hop (tango_amd.inpaint.long_geometry names
+        the neighbours otherwise), at most 32 windows.  Works with the configured DDPM or a DDIM scheduler; a DPM-Solver scheduler is
+        refused.  `seed`: the Philox key of the step noise (None: from torch's generator); the canvas noise comes from torch's
+        generator, like generate()'s.  Samples are chunked so that one engine call runs at most 64 UNet rows.
+        Returns np.int16 [samples, vocoder_samples(4 * H)]. """
+        H, hw, stride, V = long_geometry(duration, window, hop)
+        if not isinstance(guidance, (int, float)):
+            raise ValueError("a guidance table is not supported with windows: guidance must be a scalar")
+        if getattr(self.scheduler, "rule", None) == "dpmsolver":
+            raise ValueError("the multistep DPM-Solver rule is not supported with windows (a per-view history has no reference "
+                             "behaviour): use DDPM or DDIM")
+        per_call = max(1, self.LONG_MAX_ROWS // ((2 if cfg_enabled(guidance) else 1) * V))
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        waves = []
+        with torch.no_grad():
+            for k in range(0, samples, per_call):
+                n = min(per_call, samples - k)
+                latents = self.model.inference_long([prompt], self.scheduler, steps, guidance, n, duration, window, hop,
+                                                    negative_prompt=negative_prompt, seed=seed, sample_offset=k)
+                mel = self.vae.engine.vae_decode_tiled(latents, hw, stride)
+                waves.append(self.vae.decode_to_waveform(mel))
+        return np.concatenate(waves)
 
     def generate_for_batch(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, disable_progress=True, duration=10,
                            negative_prompt=None, guidance_rescale=0.0):
