@@ -258,6 +258,33 @@ const char* tango_debug_denoise_windows_check(const tango_denoise_args_t* args, 
 int tango_engine_vae_decode_tiled_h(tango_engine_t* h, const float* latents, float* mel, int batch, int canvas_h, int window_h, int stride,
                                     void* stream);
 
+/* Seamless loops: the same windows on a RING in time.  The canvas args->latents [B, C_lat, H, latent_w] (H = args->latent_h > 0) is a ring
+ * of H rows; V = H / s views, view v covers canvas rows (v s + y) mod H for y in [0, Hw).  1 <= s <= Hw <= H (a window never meets itself),
+ * H % s == 0, V <= 32, Hw a UNet height.  H == Hw is a good call: V = Hw / s rotated views of the whole ring; H == Hw == s is one view
+ * that does not wrap and computes tango_engine_denoise's bits.  The UNet batch, the row order of prompt_embeds / prompt_mask and the plan
+ * are tango_engine_denoise_windows'.  Per step and canvas element of row h, with r = h % s: the n = ceil((Hw - r) / s) covering views are
+ * v_k = (h / s - k) mod V, k = 0 .. n - 1, the element at local row y_k = r + k s of view v_k; they are accumulated in DESCENDING k (the view
+ * that starts farthest below h first: for a row no view wraps over, the linear call's ascending order), acc = 0 + d_.. + d_..; acc / n;
+ * + sigma * one draw per canvas element, exactly as above.  The order is relative to h, so the update commutes with a rotation of the ring
+ * by a multiple of s: no row is special, the wrap point included.
+ * Refused, each with a message of its own, in this order: TANGO_RULE_DPM_MULTISTEP, whatever tango_engine_denoise refuses, known_latents,
+ * (a guidance table or rescale: there is none here), latent_h <= 0, H < Hw, H % s != 0, s outside [1, Hw], V > 32, no UNet height. */
+int tango_engine_denoise_ring(tango_engine_t* h, const tango_denoise_args_t* args, const tango_window_args_t* win, void* stream);
+/* host-side query, no GPU needed: "" when tango_engine_denoise_ring accepts these arguments as far as its argument checks go (window_h is
+ * only asked to be a multiple of 8), else the message it fails with */
+const char* tango_debug_denoise_ring_check(const tango_denoise_args_t* args, const tango_window_args_t* win);
+/* ring latents [B, embed_dim, canvas_h, latent_w] -> mel [B, 1, 4 canvas_h, 64] on the same ring: the V = canvas_h / stride wrapping windows
+ * go through the decoder at batch B * V and height window_h, and the tiles are cross-faded as tango_op_mel_ring_blend says. */
+int tango_engine_vae_decode_ring_h(tango_engine_t* h, const float* latents, float* mel, int batch, int canvas_h, int window_h, int stride,
+                                   void* stream);
+/* mel [B, 1, T, num_mels] fp32 on a ring of T = mel_frames frames -> wav int16 [B, hop * T] (hop = the product of the upsample rates, 160):
+ * the mel is padded circularly by Cx = tango_engine_vocoder_ring_context() frames on each side, the ordinary vocoder runs at T + 2 Cx
+ * frames, and samples [hop Cx + 16, hop Cx + 16 + hop T) of each item (16 = half the 32 samples the vocoder makes beyond hop per frame) are
+ * copied out.  The last sample joins the first as any two neighbours join. */
+int tango_engine_vocode_ring(tango_engine_t* h, const float* mel, int16_t* wav, int batch, int mel_frames, int* n_samples, void* stream);
+/* Cx: the vocoder's receptive field in mel frames on one side, from its configuration (kernels, dilations, rates), rounded up to a multiple of 4 */
+int tango_engine_vocoder_ring_context(tango_engine_t* h);
+
 /* one UNet call: sample [B2,C,H,W] fp32 NCHW, timestep, embeds [B2,L,d], mask [B2,L] -> out [B2,C,H,W] fp32 */
 int tango_engine_unet_forward(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
                               const uint8_t* prompt_mask, float* out, int batch2, int text_len, void* stream);
@@ -512,6 +539,18 @@ int tango_op_sched_windows(float* latents, const float* model_out_nchw, const fl
  * (both 1 when E == 0); out[r] = (sum_t w_t tile_t) / (sum_t w_t) over the covering tiles in ascending order, fp32.  For s4 >= Hw4 / 2 two
  * overlapping weights sum to 1: blend_v's ramp at half-pixel centres.  1 <= s4 <= Hw4, V <= 32.  Synchronises. */
 int tango_op_mel_tile_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream);
+/* tango_op_sched_windows on a ring (tango_engine_denoise_ring): latents [B, C, H, W] the ring, model_out_nchw [B2 * (H / s), C, Hw, W].
+ * Refuses what tango_engine_denoise_ring refuses.  Synchronises. */
+int tango_op_sched_ring(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H, int W,
+                        int Hw, int s, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
+                        int sample_offset, int step, void* stream);
+/* cross-fade of decoded tiles on a ring: tiles DEVICE fp32 [B * V, 1, Hw4, F], tile t holding ring rows (t s4 + y) mod (V s4) -> out DEVICE
+ * fp32 [B, 1, V s4, F].  Every tile has a predecessor and a successor: with E = Hw4 - s4 the weight at local row y is
+ * min(1, (y + 0.5) / E) * min(1, (Hw4 - y - 0.5) / E) (1 when E == 0); out[r] = (sum w tile) / (sum w) over the covering tiles in the ring
+ * update's order, fp32.  1 <= s4 <= Hw4 <= V s4, V <= 32.  Synchronises. */
+int tango_op_mel_ring_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream);
+/* circular padding: mel DEVICE fp32 [B, T, F] -> out DEVICE fp32 [B, T + 2 ctx, F], out frame j = mel frame (j - ctx) mod T.  Synchronises. */
+int tango_op_mel_ring_pad(const float* mel, float* out, int B, int T, int F, int ctx, void* stream);
 
 /* one fused CFG + multistep DPM-Solver step (TANGO_RULE_DPM_MULTISTEP) at loop index `step` on caller-owned buffers: latents
  * [B, C, HW] fp32 in/out, model_out_nchw [B2, C, HW] fp32 (B2 = 2B, [uncond; cond], when cfg), ring DEVICE [3][B][C][HW] fp32

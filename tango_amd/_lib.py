@@ -141,6 +141,8 @@ SYMBOLS = [
     "tango_debug_attention_route", "tango_debug_attention_route_ld", "tango_op_attention_view",
     "tango_engine_denoise_windows", "tango_debug_denoise_windows_check", "tango_engine_vae_decode_tiled_h",
     "tango_op_sched_windows", "tango_op_mel_tile_blend",
+    "tango_engine_denoise_ring", "tango_debug_denoise_ring_check", "tango_engine_vae_decode_ring_h", "tango_engine_vocode_ring",
+    "tango_engine_vocoder_ring_context", "tango_op_sched_ring", "tango_op_mel_ring_blend", "tango_op_mel_ring_pad",
 ]
 
 _lib = None
@@ -178,6 +180,15 @@ def load():
     lib.tango_engine_vae_decode_tiled_h.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
     lib.tango_op_sched_windows.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci, cf, C.c_uint64, ci, ci, vp]
     lib.tango_op_mel_tile_blend.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
+    lib.tango_engine_denoise_ring.argtypes = [vp, C.POINTER(DenoiseArgs), C.POINTER(WindowArgs), vp]
+    lib.tango_debug_denoise_ring_check.argtypes = [C.POINTER(DenoiseArgs), C.POINTER(WindowArgs)]
+    lib.tango_debug_denoise_ring_check.restype = C.c_char_p
+    lib.tango_engine_vae_decode_ring_h.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
+    lib.tango_engine_vocode_ring.argtypes = [vp, vp, vp, ci, ci, C.POINTER(ci), vp]
+    lib.tango_engine_vocoder_ring_context.argtypes = [vp]
+    lib.tango_op_sched_ring.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci, cf, C.c_uint64, ci, ci, vp]
+    lib.tango_op_mel_ring_blend.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
+    lib.tango_op_mel_ring_pad.argtypes = [vp, vp, ci, ci, ci, ci, vp]
     lib.tango_engine_unet_forward.argtypes = [vp, vp, i64, vp, vp, vp, ci, ci, vp]
     lib.tango_engine_unet_forward_music.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.tango_engine_vae_decode.argtypes = [vp, vp, vp, ci, vp]

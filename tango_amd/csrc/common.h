@@ -516,6 +516,32 @@ int launch_window_gather_nchw(const float* lat, float* dst, int B, int C, int W,
 // tiles fp32 [B * V, g.Hw, F] (tile t at output rows t * g.s ...) -> out fp32 [B, g.H, F], cross-faded over the overlaps (g in mel rows)
 int launch_mel_tile_blend(const float* tiles, float* out, int B, int F, const WindowGeom& g, hipStream_t s);
 
+// ---- loops: the same windows on a ring in time (sched.hip; tango_engine_denoise_ring) ----
+// The canvas rows are a ring of H rows: V = H / s views, view v covers canvas rows (v s + y) mod H for y in [0, Hw), with
+// 1 <= s <= Hw <= H (a window never meets itself), H % s == 0 and V <= kMaxWindows.  The window batch's row order is the linear one.
+// why (canvas_h, window_h, stride) is no such ring (nullptr: it is; *g is then filled in).  Host only.
+const char* ring_geom_refusal(int canvas_h, int window_h, int stride, WindowGeom* g);
+// The n = ceil((Hw - h % s) / s) views that cover ring row h, in accumulation order: the view that starts farthest below h first.  The j-th
+// is view (*v0 + j) mod V at its local row *y0 - j s (k = n - 1 - j of v_k = (h / s - k) mod V, y_k = h % s + k s).  The order is relative
+// to h, so the update commutes with a rotation of the ring by a multiple of s; for a row no covering view wraps over it is window_cover's.
+__host__ __device__ inline int ring_cover(const WindowGeom& g, int h, int* v0, int* y0) {
+  const int q = h / g.s, r = h - q * g.s;
+  const int n = (g.Hw - r + g.s - 1) / g.s;          // n <= ceil(Hw / s) <= V
+  const int v = q - (n - 1);
+  *v0 = v < 0 ? v + g.V : v;
+  *y0 = r + (n - 1) * g.s;
+  return n;
+}
+// sched_window_kernel's ring form (rules 0 / 1) on a SchedWindowParams block whose g is a ring; the grid covers max_positions >= B * H * W
+int launch_sched_ring(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s);
+// the two gathers with source row (v s + y) mod H
+int launch_ring_gather(int dtype, const float* lat, void* xin, int64_t ld, int B, int C, int W, const WindowGeom& g, int rep, hipStream_t s);
+int launch_ring_gather_nchw(const float* lat, float* dst, int B, int C, int W, const WindowGeom& g, hipStream_t s);
+// tiles fp32 [B * V, g.Hw, F] (tile t at ring rows (t g.s + y) mod g.H) -> out fp32 [B, g.H, F]: every tile fades in and out (g in mel rows)
+int launch_mel_ring_blend(const float* tiles, float* out, int B, int F, const WindowGeom& g, hipStream_t s);
+// mel fp32 [B, T, F] on a ring -> dst fp32 [B, T + 2 ctx, F], dst frame j = mel frame (j - ctx) mod T
+int launch_mel_ring_pad(const float* mel, float* dst, int B, int T, int F, int ctx, hipStream_t s);
+
 // The update step's arguments as the host sees them: what a denoise call (rows [0, num_rows)) and a one-step test hook (row `step` alone)
 // may pass.  Pointers are only asked whether they are null, except `coef` (HOST [num_rows][coef_w]) and `table` (HOST [table_rows][batch]).
 struct SchedArgs {
@@ -530,6 +556,9 @@ const char* sched_args_refusal(const SchedArgs& a);
 // the same for a windowed update (tango_engine_denoise_windows, tango_op_sched_windows): sched_args_refusal, then the multistep rule,
 // known latents, a guidance table or rescale, and a geometry that is no exact cover (*g is filled in when the answer is nullptr)
 const char* window_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, WindowGeom* g);
+// the same for an update on a ring (tango_engine_denoise_ring, tango_op_sched_ring): the multistep rule, sched_args_refusal, known latents,
+// a guidance table or rescale, a missing canvas height, then ring_geom_refusal and a window_h that is no multiple of 8
+const char* ring_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, WindowGeom* g);
 // `dev_params` is a DEVICE copy of SchedParams; the grid covers max_positions >= B*HW (one thread per latent position).
 // `rule` (host copy of the block's rule) picks the kernel: 0 / 1 sched_step_kernel, 2 sched_multistep_kernel; `masked` their
 // inpainting variants (the blend for the next loop index fused after the update); `guided` the variants that read the guidance

@@ -172,6 +172,8 @@ struct UNetPlan : Plan {
   // a windowed call (Engine::denoise_windows) runs this plan's step program with sched_window_kernel as its update: graphs of its own,
   // so that a plain call and a windowed call of one shape share the plan and each replays the graph that holds its own update kernel
   StepGraphs wgraphs;
+  // ... and a call on a ring (Engine::denoise_ring) the ring form of that kernel: plain, windowed and ring calls of one shape share the plan
+  StepGraphs rgraphs;
   // Two independent chains (round 5; Engine::denoise): a "dual" plan owns only the UNet input / output buffers of the whole batch; its
   // two children run the first and the second half of the samples (no op of the UNet crosses samples) as two branches of the captured
   // graph, so that one branch's dispatch gaps and kernel tails are filled by the other's kernels.  A child takes xin / eps from its
@@ -224,6 +226,11 @@ class Engine {
   // long clips: a.latent_h is the canvas height, the UNet runs (cfg ? 2 : 1) * a.batch * V windows of height w.window_h per step
   int denoise_windows(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s);
   int vae_decode_tiled(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s);
+  // loops: the same with the canvas rows on a ring (V = a.latent_h / w.stride views that wrap), and the vocoder on a ring of mel frames
+  int denoise_ring(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s);
+  int vae_decode_ring(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s);
+  int vocode_ring(const float* mel, int16_t* wav, int B, int frames, int* n_samples, hipStream_t s);
+  int vocoder_ring_context() const;     // mel frames of context vocode_ring pads each side with: the vocoder's receptive field
   struct Cond { const float* emb = nullptr; const uint8_t* mask = nullptr; int len = 0; const uint8_t* mask_host = nullptr; };
   // latent_h: the latent height of the call, 0 = cfg.latent_h (the width is always cfg.latent_w)
   int unet_forward(const float* sample, int64_t t, const Cond (&c)[3], float* out, int B2, int latent_h, hipStream_t s);
@@ -408,7 +415,9 @@ class Engine {
   // how a guidance / plain batch of B2 UNet rows runs; profile_unet() asks with two_chains_ok = false
   UNetMode unet_mode_for(int B2, int n_short, bool cfg_on, bool two_chains_ok) const;
   // which update closes a step: the kernel is fixed when a step is captured
-  struct StepKind { int rule = 0; bool masked = false, guided = false, windowed = false; };
+  struct StepKind { int rule = 0; bool masked = false, guided = false, windowed = false, ring = false; };   // ring: a windowed step on a ring
+  int denoise_windowed(const tango_denoise_args_t& a, const tango_window_args_t& w, bool ring, hipStream_t s);
+  int vae_decode_windowed(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, bool ring, hipStream_t s);
   int run_step(const UNetPlan& P, const StepKind& k, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
   int capture_steps(const UNetPlan& P, const StepKind& k, int n, hipGraph_t* g_out, hipGraphExec_t* x_out);
   // the loop of a denoise call once its blocks, conditions and first UNet input are in place: captures what G lacks, replays or runs eagerly

@@ -556,6 +556,7 @@ void Engine::free_plan(Plan& P) {
       for (auto& row : plane)
         for (StepGraphs& g : row) drop(g);
     drop(U.wgraphs);
+    drop(U.rgraphs);
     for (auto& c : U.child) if (c) { free_plan(*c); c.reset(); }
   }
   // a slab may still be read by work queued on a stream: hipFree synchronises the device before it releases memory
@@ -1505,7 +1506,9 @@ int Engine::run_step(const UNetPlan& P, const StepKind& k, hipStream_t st, hipSt
     TANGO_HIP(hipStreamWaitEvent(st, join, 0));
   }
   if (k.windowed) {
-    TANGO_TRY(launch_sched_windows(dt, d_wsched, P.B2 * P.H * cfg.latent_w, st));
+    // (a ring of H = V s <= V Hw rows has no more positions than its window batch either)
+    if (k.ring) TANGO_TRY(launch_sched_ring(dt, d_wsched, P.B2 * P.H * cfg.latent_w, st));
+    else TANGO_TRY(launch_sched_windows(dt, d_wsched, P.B2 * P.H * cfg.latent_w, st));
     return launch_step_inc(d_step, st);
   }
   if (k.guided) TANGO_TRY(launch_guidance_stats(d_sched, P.B2 / 2, P.H * cfg.latent_w, st));
@@ -1635,19 +1638,28 @@ int Engine::run_loop(UNetPlan& P, StepGraphs& G, const StepKind& k, int num_step
 // plan of (B2 * V, L, ..., window_h), whose step program runs unchanged; the update averages the views on the canvas and writes the next
 // input of every window.  prompt_embeds / prompt_mask hold B2 * V rows in the window batch's order (row half * B * V + b * V + v), so the
 // single-key prefix and the condition binding are those of a plain call of that batch.
-static int check_window_args(const tango_denoise_args_t& a, const tango_window_args_t& w, WindowGeom* g) {
+// Loops (tango_engine_denoise_ring): the same call with the canvas rows on a ring -- V = latent_h / stride views that wrap round it
+// (common.h ring_cover), the ring forms of the gather and of the update, and captured steps of their own (UNetPlan::rgraphs).
+static int check_window_args(const tango_denoise_args_t& a, const tango_window_args_t& w, WindowGeom* g, bool ring = false) {
   SchedArgs c;
   c.rule = a.rule; c.coef = a.coef; c.coef_w = a.coef_width ? a.coef_width : 8; c.num_rows = c.row1 = a.num_steps;
   c.noise = a.noise != nullptr; c.clip = a.clip_sample != 0;
   c.known = a.known_latents; c.mask = a.latent_mask; c.blend_coef = a.blend_coef; c.blend_noise = a.blend_noise;
+  if (ring) {
+    if (const char* why = ring_args_refusal(c, a.latent_h, w.window_h, w.stride, g)) TANGO_FAIL(std::string("denoise_ring: ") + why);
+    return 0;
+  }
   if (const char* why = window_args_refusal(c, a.latent_h, w.window_h, w.stride, g)) TANGO_FAIL(std::string("denoise_windows: ") + why);
   return 0;
 }
 
-int Engine::denoise_windows(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) {
+int Engine::denoise_windows(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) { return denoise_windowed(a, w, false, s); }
+int Engine::denoise_ring(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) { return denoise_windowed(a, w, true, s); }
+
+int Engine::denoise_windowed(const tango_denoise_args_t& a, const tango_window_args_t& w, bool ring, hipStream_t s) {
   WindowGeom g;
-  TANGO_TRY(check_window_args(a, w, &g));
-  if (a.batch <= 0) TANGO_FAIL("denoise_windows: batch must be positive");
+  TANGO_TRY(check_window_args(a, w, &g, ring));
+  if (a.batch <= 0) TANGO_FAIL(std::string(ring ? "denoise_ring" : "denoise_windows") + ": batch must be positive");
   int Hw;
   TANGO_TRY(resolve_h(w.window_h, true, &Hw));       // window_h is a UNet height of this configuration
   const bool cfg_on = a.guidance_scale > 1.0f;
@@ -1678,10 +1690,11 @@ int Engine::denoise_windows(const tango_denoise_args_t& a, const tango_window_ar
     TANGO_TRY(bind_conditions(*P, c, key0, s));
   }
   TANGO_TRY(launch_fill_zero(P->xin, (size_t)rows * Hw * W * 8 * esz, s));
-  TANGO_TRY(launch_window_gather(dt, a.latents, P->xin, 8, B, C, W, g, cfg_on ? 2 : 1, s));
+  if (ring) TANGO_TRY(launch_ring_gather(dt, a.latents, P->xin, 8, B, C, W, g, cfg_on ? 2 : 1, s));
+  else TANGO_TRY(launch_window_gather(dt, a.latents, P->xin, 8, B, C, W, g, cfg_on ? 2 : 1, s));
   StepKind k;
-  k.rule = a.rule; k.windowed = true;
-  return run_loop(*P, P->wgraphs, k, a.num_steps, a.use_graph != 0, s);
+  k.rule = a.rule; k.windowed = true; k.ring = ring;
+  return run_loop(*P, ring ? P->rgraphs : P->wgraphs, k, a.num_steps, a.use_graph != 0, s);
 }
 
 int Program::run_profiled(hipStream_t s, std::string& report) const {
@@ -1981,21 +1994,34 @@ int Engine::vae_decode(const float* lat, float* mel, int B, int latent_h, hipStr
 // latent windows of every sample go through the ordinary decoder plan of (B * V, window_h) in one run, then one blend kernel cross-fades
 // the decoded tiles into mel [B, 1, canvas_h << (levels - 1), F].  All V views are decoded, overlaps included: the decoder is about 1 %
 // of a pass, and its mid-block attention stays at the window's size whatever the clip length.
+// On a ring (vae_decode_ring, loops): the V = canvas_h / stride windows wrap round the canvas and every tile fades in and out
+// (sched.hip mel_ring_blend_kernel), so the decoded mel is as seamless at its wrap as anywhere else.
 int Engine::vae_decode_tiled(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s) {
+  return vae_decode_windowed(lat, mel, B, canvas_h, window_h, stride, false, s);
+}
+int Engine::vae_decode_ring(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s) {
+  return vae_decode_windowed(lat, mel, B, canvas_h, window_h, stride, true, s);
+}
+
+int Engine::vae_decode_windowed(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, bool ring, hipStream_t s) {
+  const std::string who = ring ? "vae_decode_ring" : "vae_decode_tiled";
   if (cfg.vae_levels <= 0) TANGO_FAIL("engine: VAE not configured");
   if (cfg.vae_out_ch != 1) TANGO_FAIL("engine: VAE out_ch must be 1 (NHWC == NCHW at the boundary)");
-  if (B <= 0) TANGO_FAIL("vae_decode_tiled: batch must be positive");
+  if (B <= 0) TANGO_FAIL(who + ": batch must be positive");
   WindowGeom g;
-  if (const char* why = window_geom_refusal(canvas_h, window_h, stride, &g)) TANGO_FAIL(std::string("vae_decode_tiled: ") + why);
+  if (const char* why = ring ? ring_geom_refusal(canvas_h, window_h, stride, &g) : window_geom_refusal(canvas_h, window_h, stride, &g))
+    TANGO_FAIL(who + ": " + why);
   int Hw;
   TANGO_TRY(resolve_h(window_h, false, &Hw));
   VaePlan* P;
   TANGO_TRY(get_vae_plan(B * g.V, Hw, &P));
-  TANGO_TRY(launch_window_gather_nchw(lat, (float*)P->in, B, cfg.vae_embed_dim, cfg.latent_w, g, s));
+  if (ring) TANGO_TRY(launch_ring_gather_nchw(lat, (float*)P->in, B, cfg.vae_embed_dim, cfg.latent_w, g, s));
+  else TANGO_TRY(launch_window_gather_nchw(lat, (float*)P->in, B, cfg.vae_embed_dim, cfg.latent_w, g, s));
   TANGO_TRY(P->prog.run(s));
   const int up = cfg.vae_levels - 1;
   WindowGeom gm;                                   // the same geometry in mel rows
   gm.H = g.H << up; gm.Hw = g.Hw << up; gm.s = g.s << up; gm.V = g.V;
+  if (ring) return launch_mel_ring_blend((const float*)P->out, mel, B, cfg.latent_w << up, gm, s);
   return launch_mel_tile_blend((const float*)P->out, mel, B, cfg.latent_w << up, gm, s);
 }
 
@@ -2185,6 +2211,50 @@ int Engine::vocode(const float* mel, int16_t* wav, int B, int frames, int* n_sam
   return 0;
 }
 
+// The vocoder on a ring of mel frames (loops).  HiFi-GAN zero-pads both ends of its input, so even a periodic mel vocodes to a waveform
+// whose ends do not join.  Here the mel is padded circularly by Cx frames on each side, the ordinary plan runs at T + 2 Cx frames, and the
+// samples that belong to the T frames are copied out: hop * T of them, hop = the product of the upsample rates, from offset
+// hop * Cx + (vocoder_samples(F) - hop * F) / 2 (the transposed convs' excess, 32 samples for the 16 kHz configuration, split evenly).
+// Cx is the vocoder's receptive field in frames, walked back from one output sample: each conv of k taps at dilation d widens the
+// half-width by (k - 1) d / 2 (a resblock stage by its widest branch), each transposed conv (k, u, p = (k - u) / 2) maps a half-width R of
+// its output to ceil((R + k - 1 - p) / u) of its input; rounded up to a multiple of 4 frames (one latent row).
+int Engine::vocoder_ring_context() const {
+  if (cfg.voc_n_ups <= 0) return 0;
+  int R = (voc_post.taps - 1) / 2;
+  for (int i = cfg.voc_n_ups - 1; i >= 0; --i) {
+    int widest = 0;
+    for (int j = 0; j < cfg.voc_n_resblocks; ++j) {
+      const int k = cfg.voc_res_kernels[j];
+      int r = 0;
+      for (int m = 0; m < 4 && cfg.voc_res_dilations[j][m] > 0; ++m) r += (k - 1) / 2 * cfg.voc_res_dilations[j][m] + (k - 1) / 2;   // convs1[m], convs2[m]
+      if (r > widest) widest = r;
+    }
+    R += widest;
+    const int u = cfg.voc_rates[i], k = cfg.voc_kernels[i], p = (k - u) / 2;
+    R = (R + k - 1 - p + u - 1) / u;
+  }
+  R += (voc_pre.taps - 1) / 2;
+  return (R + 3) / 4 * 4;
+}
+
+int Engine::vocode_ring(const float* mel, int16_t* wav, int B, int frames, int* n_samples, hipStream_t s) {
+  if (cfg.voc_n_ups <= 0) TANGO_FAIL("engine: vocoder not configured");
+  if (B <= 0 || frames <= 0) TANGO_FAIL("vocode_ring: batch and mel_frames must be positive");
+  const int ctx = vocoder_ring_context(), F = frames + 2 * ctx;
+  int hop = 1;
+  for (int i = 0; i < cfg.voc_n_ups; ++i) hop *= cfg.voc_rates[i];
+  VaePlan* P;
+  TANGO_TRY(get_voc_plan(B, F, &P));
+  const int off = hop * ctx + (P->n_out - hop * F) / 2;
+  if (off < 0 || off + hop * frames > P->n_out) TANGO_FAIL("vocode_ring: the vocoder makes fewer samples than its frames times its hop");
+  TANGO_TRY(launch_mel_ring_pad(mel, (float*)P->in, B, frames, cfg.voc_num_mels, ctx, s));
+  TANGO_TRY(P->prog.run(s));
+  TANGO_HIP(hipMemcpy2DAsync(wav, (size_t)hop * frames * 2, (const int16_t*)P->out + off, (size_t)P->n_out * 2, (size_t)hop * frames * 2, B,
+                             hipMemcpyDeviceToDevice, s));
+  if (n_samples) *n_samples = hop * frames;
+  return 0;
+}
+
 }  // namespace tango
 
 // ================================================================================================
@@ -2279,6 +2349,31 @@ int tango_engine_vae_decode_tiled_h(tango_engine_t* h, const float* latents, flo
                                     void* stream) {
   if (!h || !latents || !mel) { tango::set_error("vae_decode_tiled: null argument"); return -1; }
   return h->e->vae_decode_tiled(latents, mel, batch, canvas_h, window_h, stride, (hipStream_t)stream);
+}
+int tango_engine_denoise_ring(tango_engine_t* h, const tango_denoise_args_t* a, const tango_window_args_t* w, void* stream) {
+  if (!h || !a || !w) { tango::set_error("denoise_ring: null args"); return -1; }
+  return h->e->denoise_ring(*a, *w, (hipStream_t)stream);
+}
+const char* tango_debug_denoise_ring_check(const tango_denoise_args_t* a, const tango_window_args_t* w) {
+  static thread_local std::string msg;
+  msg.clear();
+  if (!a || !w) return "denoise_ring: null args";
+  tango::WindowGeom g;
+  if (tango::check_window_args(*a, *w, &g, true) != 0) msg = tango_last_error();
+  return msg.c_str();
+}
+int tango_engine_vae_decode_ring_h(tango_engine_t* h, const float* latents, float* mel, int batch, int canvas_h, int window_h, int stride,
+                                   void* stream) {
+  if (!h || !latents || !mel) { tango::set_error("vae_decode_ring: null argument"); return -1; }
+  return h->e->vae_decode_ring(latents, mel, batch, canvas_h, window_h, stride, (hipStream_t)stream);
+}
+int tango_engine_vocode_ring(tango_engine_t* h, const float* mel, int16_t* wav, int batch, int mel_frames, int* n_samples, void* stream) {
+  if (!h || !mel || !wav) { tango::set_error("vocode_ring: null argument"); return -1; }
+  return h->e->vocode_ring(mel, wav, batch, mel_frames, n_samples, (hipStream_t)stream);
+}
+int tango_engine_vocoder_ring_context(tango_engine_t* h) {
+  if (!h) { tango::set_error("vocoder_ring_context: null engine"); return -1; }
+  return h->e->vocoder_ring_context();
 }
 int tango_engine_unet_forward_h(tango_engine_t* h, const float* sample, int64_t timestep, const float* prompt_embeds,
                                 const uint8_t* prompt_mask, float* out, int batch2, int text_len, int latent_h, void* stream) {

@@ -1015,16 +1015,17 @@ int tango_op_sched_guided(float* latents, const float* model_out_nchw, const flo
   return op_sched(o);
 }
 
-int tango_op_sched_windows(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H, int W,
-                           int Hw, int sw, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
-                           int sample_offset, int step, void* stream) {
-  const std::string w("op_sched_windows");
+// the windowed update's hook, linear (tango_op_sched_windows) or on a ring (tango_op_sched_ring)
+static int op_sched_windowed(bool ring, float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H,
+                             int W, int Hw, int sw, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
+                             int sample_offset, int step, void* stream) {
+  const std::string w(ring ? "op_sched_ring" : "op_sched_windows");
   if (B <= 0 || C <= 0 || W <= 0 || step < 0 || sample_offset < 0) TANGO_FAIL(w + ": bad sizes");
   if (!latents || !model_out_nchw || !coef8) TANGO_FAIL(w + ": latents, model_out_nchw and coef8 are required");
   SchedArgs c;                      // the engine's own rules; the single row is the row of this step
   c.rule = rule; c.coef = coef8; c.coef_w = 8; c.num_rows = 1; c.row0 = 0; c.row1 = 1; c.noise = noise != nullptr; c.clip = clip != 0;
   WindowGeom g;
-  if (const char* why = window_args_refusal(c, H, Hw, sw, &g)) TANGO_FAIL(w + ": " + why);
+  if (const char* why = ring ? ring_args_refusal(c, H, Hw, sw, &g) : window_args_refusal(c, H, Hw, sw, &g)) TANGO_FAIL(w + ": " + why);
   if (!noise && C % 4 != 0) TANGO_FAIL(w + ": the Philox stream draws four channels at a time: C must be a multiple of 4");
   const int B2 = cfg ? 2 * B : B, rows = B2 * g.V, win = Hw * W;
   if ((int64_t)rows * win * C >= ((int64_t)1 << 31)) TANGO_FAIL(w + ": B2 * V * Hw * W * C must stay below 2^31");
@@ -1045,7 +1046,42 @@ int tango_op_sched_windows(float* latents, const float* model_out_nchw, const fl
   p.clip = clip; p.clip_range = clip_range; p.seed = seed; p.sample_offset = sample_offset; p.num_steps = step + 1;
   wp.g = g; wp.W = W; wp.noise_row0 = step;
   TANGO_HIP(hipMemcpyAsync(dp, &wp, sizeof(SchedWindowParams), hipMemcpyHostToDevice, s));
-  TANGO_TRY(launch_sched_windows(DT_F32, dp, B * H * W, s));
+  if (ring) TANGO_TRY(launch_sched_ring(DT_F32, dp, B * H * W, s));
+  else TANGO_TRY(launch_sched_windows(DT_F32, dp, B * H * W, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_sched_windows(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H, int W,
+                           int Hw, int sw, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
+                           int sample_offset, int step, void* stream) {
+  return op_sched_windowed(false, latents, model_out_nchw, noise, coef8, B, C, H, W, Hw, sw, cfg, guidance, pred_type, rule, clip, clip_range, seed,
+                           sample_offset, step, stream);
+}
+int tango_op_sched_ring(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H, int W,
+                        int Hw, int sw, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
+                        int sample_offset, int step, void* stream) {
+  return op_sched_windowed(true, latents, model_out_nchw, noise, coef8, B, C, H, W, Hw, sw, cfg, guidance, pred_type, rule, clip, clip_range, seed,
+                           sample_offset, step, stream);
+}
+
+int tango_op_mel_ring_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream) {
+  if (B <= 0 || V <= 0 || F <= 0 || !tiles || !out) TANGO_FAIL("op_mel_ring_blend: bad arguments");
+  if ((int64_t)V * Hw4 > ((int64_t)1 << 24)) TANGO_FAIL("op_mel_ring_blend: V * Hw4 too large");
+  WindowGeom g;
+  if (Hw4 <= 0 || s4 < 1 || s4 > Hw4) TANGO_FAIL("op_mel_ring_blend: 1 <= s4 <= Hw4 is required");
+  if (const char* why = ring_geom_refusal(V * s4, Hw4, s4, &g)) TANGO_FAIL(std::string("op_mel_ring_blend: ") + why);
+  hipStream_t s = (hipStream_t)stream;
+  TANGO_TRY(launch_mel_ring_blend(tiles, out, B, F, g, s));
+  TANGO_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int tango_op_mel_ring_pad(const float* mel, float* out, int B, int T, int F, int ctx, void* stream) {
+  if (!mel || !out) TANGO_FAIL("op_mel_ring_pad: null argument");
+  if (B <= 0 || T <= 0 || F <= 0 || ctx < 0 || (int64_t)B * (T + 2 * (int64_t)ctx) * F >= ((int64_t)1 << 31)) TANGO_FAIL("op_mel_ring_pad: bad sizes");
+  hipStream_t s = (hipStream_t)stream;
+  TANGO_TRY(launch_mel_ring_pad(mel, out, B, T, F, ctx, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
 }

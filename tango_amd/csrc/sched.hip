@@ -1,6 +1,6 @@
 // The denoise loop's own kernels (fused CFG combine + scheduler update for DDPM / DDIM and multistep DPM-Solver with its masked and guided
-// variants, guidance statistics, inpainting blend, step counter, Philox, fused latent encode, the windowed update of long clips with its
-// gathers and the mel tile blend), their launchers and their argument checkers.
+// variants, guidance statistics, inpainting blend, step counter, Philox, fused latent encode, the windowed update of long clips and of loops
+// with their gathers, the mel tile blends and the vocoder's ring padding), their launchers and their argument checkers.
 #include <cmath>
 #include "common.h"
 #include "tango_engine.h"
@@ -239,8 +239,12 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __re
 // floors and leaves a tail of rows with count == 0); (2) nz is ONE draw per canvas element -- injected noise[step][b, c, h, w] or Philox with
 // the canvas position as the counter's hw -- where the fork's loop would average V independent draws and shrink the variance of a
 // stochastic sampler's step noise by |cover(h)|.  With sig == 0 (DDIM eta = 0, the last DDPM step) it is the fork's loop.
+// RING (loops, tango_engine_denoise_ring): the canvas rows are a ring and the views wrap round it (common.h ring_cover): the same
+// per-view arithmetic over the views (v0 + j) mod V at local rows y0 - j s, the view that starts farthest below h first -- for a row
+// that no view wraps over, the ascending order above.  The order is relative to h, so the update commutes with a rotation of the ring
+// by a multiple of s: no row is special, the wrap point included.  The linear form walks its views as (v_lo + j, h - v_lo s - j s).
 // ------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool RING>
 __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowParams* __restrict__ pp) {
 #pragma clang fp contract(off)
   const SchedParams p = pp->p;
@@ -250,9 +254,15 @@ __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowPara
   if (idx >= p.B * p.HW) return;
   const int b = idx / p.HW, hw = idx - b * p.HW;
   const int h = hw / W, w = hw - h * W;
-  int v_lo, v_hi;
-  window_cover(g, h, &v_lo, &v_hi);
-  const float cnt = (float)(v_hi - v_lo + 1);
+  int n, v0, y0;                                    // the cover: n views from v0 at local row y0, then one view up and s rows down
+  if (RING) {
+    n = ring_cover(g, h, &v0, &y0);
+  } else {
+    int v_hi;
+    window_cover(g, h, &v0, &v_hi);
+    n = v_hi - v0 + 1; y0 = h - v0 * g.s;
+  }
+  const float cnt = (float)n;
   const int step = *p.step_ptr;
   const float* cf = p.coef + step * 8;
   const float sa = cf[0], sb = cf[1], c0 = cf[2], c1 = cf[3], sig = cf[4], sap = cf[5], dirc = cf[6];
@@ -264,8 +274,9 @@ __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowPara
     float* lp = p.lat + ((int64_t)b * C + c) * p.HW + hw;
     const float x = *lp;
     float acc = 0.0f;
-    for (int v = v_lo; v <= v_hi; ++v) {
-      const int64_t pos = ((int64_t)b * g.V + v) * win + (int64_t)(h - v * g.s) * W + w;
+    for (int j = 0, v = v0, y = y0; j < n; ++j, y -= g.s) {
+      const int64_t pos = ((int64_t)b * g.V + v) * win + (int64_t)y * W + w;
+      if (++v == g.V) v = 0;                          // (only a ring's views wrap)
       float o = p.eps[pos * C + c];
       if (p.cfg) { const float dlt = p.eps[(half + pos) * C + c] - o; const float gd = p.guidance * dlt; o = o + gd; }   // models.py:246
       float x0;
@@ -298,8 +309,9 @@ __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowPara
     }
     *lp = r;
     const T tv = from_f<T>(r);
-    for (int v = v_lo; v <= v_hi; ++v) {
-      const int64_t pos = ((int64_t)b * g.V + v) * win + (int64_t)(h - v * g.s) * W + w;
+    for (int j = 0, v = v0, y = y0; j < n; ++j, y -= g.s) {
+      const int64_t pos = ((int64_t)b * g.V + v) * win + (int64_t)y * W + w;
+      if (++v == g.V) v = 0;
       ((T*)p.xin)[pos * p.xin_ld + c] = tv;
       if (p.cfg) ((T*)p.xin)[(half + pos) * p.xin_ld + c] = tv;
     }
@@ -365,14 +377,130 @@ __global__ __launch_bounds__(256) void mel_tile_blend_kernel(const float* __rest
   out[idx] = num / den;
 }
 
-int launch_sched_windows(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
+// ---- loops: the gathers, the tile blend and the vocoder's context on a ring ----
+// window_gather_kernel with source row (v s + y) mod H
+template <typename T>
+__global__ __launch_bounds__(256) void ring_gather_kernel(const float* __restrict__ lat, T* __restrict__ xin, int64_t ld, int B, int C, int W,
+                                                          WindowGeom g, int rep) {
+  const int64_t win = (int64_t)g.Hw * W;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * g.V * win) return;
+  const int row = (int)(idx / win), pos = (int)(idx - (int64_t)row * win);
+  const int b = row / g.V, v = row - b * g.V;
+  const int y = pos / W, w = pos - y * W;
+  const int64_t HW = (int64_t)g.H * W;
+  const int64_t src = (int64_t)((v * g.s + y) % g.H) * W + w;
+  for (int c = 0; c < C; ++c) {
+    const T t = from_f<T>(lat[((int64_t)b * C + c) * HW + src]);
+    for (int r = 0; r < rep; ++r) xin[((int64_t)r * B * g.V * win + idx) * ld + c] = t;
+  }
+}
+
+// window_gather_nchw_kernel with source row (v s + y) mod H
+__global__ __launch_bounds__(256) void ring_gather_nchw_kernel(const float* __restrict__ lat, float* __restrict__ dst, int B, int C, int W,
+                                                               WindowGeom g) {
+  const int64_t win = (int64_t)g.Hw * W;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * g.V * C * win) return;
+  const int64_t rc = idx / win;                          // (b V + v) C + c
+  const int pos = (int)(idx - rc * win);
+  const int c = (int)(rc % C), row = (int)(rc / C);
+  const int b = row / g.V, v = row - b * g.V;
+  const int y = pos / W, w = pos - y * W;
+  dst[idx] = lat[((int64_t)b * C + c) * g.H * W + (int64_t)((v * g.s + y) % g.H) * W + w];
+}
+
+// mel_tile_blend_kernel on a ring: every tile has a predecessor and a successor, so every tile gets both ramps.  g counts mel rows; with
+// E = Hw - s the weight of a tile at its local row y is min(1, (y + 0.5) / E) * min(1, (Hw - y - 0.5) / E) (1 when E == 0), and
+//   out[r] = (sum w tile) / (sum w)   over the covering tiles in ring_cover's order, each sum from 0, in fp32 without FMA contraction.
+// For s == Hw / 2 the two weights at every row sum to 1.
+__global__ __launch_bounds__(256) void mel_ring_blend_kernel(const float* __restrict__ tiles, float* __restrict__ out, int B, int F, WindowGeom g) {
+#pragma clang fp contract(off)
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * g.H * F) return;
+  const int f = (int)(idx % F);
+  const int64_t br = idx / F;
+  const int r = (int)(br % g.H), b = (int)(br / g.H);
+  int t, y;
+  const int n = ring_cover(g, r, &t, &y);
+  const int E = g.Hw - g.s;
+  float num = 0.0f, den = 0.0f;
+  for (int j = 0; j < n; ++j, y -= g.s) {
+    float wt = 1.0f;
+    if (E > 0) {
+      const float a = (float)y + 0.5f; wt = fminf(1.0f, a / (float)E);
+      const float a2 = (float)(g.Hw - y) - 0.5f; const float u = fminf(1.0f, a2 / (float)E); wt = wt * u;
+    }
+    const float m = wt * tiles[(((int64_t)b * g.V + t) * g.Hw + y) * F + f];
+    if (++t == g.V) t = 0;
+    num = num + m;
+    den = den + wt;
+  }
+  out[idx] = num / den;
+}
+
+// the vocoder's context on a ring: dst frame j of [T + 2 ctx] is mel frame (j - ctx) mod T (ctx may exceed T: the ring is walked more than once)
+__global__ __launch_bounds__(256) void mel_ring_pad_kernel(const float* __restrict__ mel, float* __restrict__ dst, int B, int T, int F, int ctx) {
+  const int Tp = T + 2 * ctx;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * Tp * F) return;
+  const int f = (int)(idx % F);
+  const int64_t bj = idx / F;
+  const int j = (int)(bj % Tp), b = (int)(bj / Tp);
+  int t = (j - ctx) % T;
+  if (t < 0) t += T;
+  dst[idx] = mel[((int64_t)b * T + t) * F + f];
+}
+
+template <bool RING>
+static int launch_sched_windowed(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
   const dim3 grid((unsigned)((max_positions + 255) / 256));
   switch (dtype) {
-    case DT_F32: hipLaunchKernelGGL(sched_window_kernel<float>, grid, dim3(256), 0, s, dev_params); break;
-    case DT_F16: hipLaunchKernelGGL(sched_window_kernel<f16>, grid, dim3(256), 0, s, dev_params); break;
-    case DT_BF16: hipLaunchKernelGGL(sched_window_kernel<bf16>, grid, dim3(256), 0, s, dev_params); break;
-    default: TANGO_FAIL("sched_windows: bad dtype");
+    case DT_F32: hipLaunchKernelGGL((sched_window_kernel<float, RING>), grid, dim3(256), 0, s, dev_params); break;
+    case DT_F16: hipLaunchKernelGGL((sched_window_kernel<f16, RING>), grid, dim3(256), 0, s, dev_params); break;
+    case DT_BF16: hipLaunchKernelGGL((sched_window_kernel<bf16, RING>), grid, dim3(256), 0, s, dev_params); break;
+    default: TANGO_FAIL(RING ? "sched_ring: bad dtype" : "sched_windows: bad dtype");
   }
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+int launch_sched_windows(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
+  return launch_sched_windowed<false>(dtype, dev_params, max_positions, s);
+}
+int launch_sched_ring(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
+  return launch_sched_windowed<true>(dtype, dev_params, max_positions, s);
+}
+
+int launch_ring_gather(int dtype, const float* lat, void* xin, int64_t ld, int B, int C, int W, const WindowGeom& g, int rep, hipStream_t s) {
+  const dim3 grid((unsigned)(((int64_t)B * g.V * g.Hw * W + 255) / 256));
+  switch (dtype) {
+    case DT_F32: hipLaunchKernelGGL(ring_gather_kernel<float>, grid, dim3(256), 0, s, lat, (float*)xin, ld, B, C, W, g, rep); break;
+    case DT_F16: hipLaunchKernelGGL(ring_gather_kernel<f16>, grid, dim3(256), 0, s, lat, (f16*)xin, ld, B, C, W, g, rep); break;
+    case DT_BF16: hipLaunchKernelGGL(ring_gather_kernel<bf16>, grid, dim3(256), 0, s, lat, (bf16*)xin, ld, B, C, W, g, rep); break;
+    default: TANGO_FAIL("ring_gather: bad dtype");
+  }
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_ring_gather_nchw(const float* lat, float* dst, int B, int C, int W, const WindowGeom& g, hipStream_t s) {
+  const dim3 grid((unsigned)(((int64_t)B * g.V * C * g.Hw * W + 255) / 256));
+  hipLaunchKernelGGL(ring_gather_nchw_kernel, grid, dim3(256), 0, s, lat, dst, B, C, W, g);
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_mel_ring_blend(const float* tiles, float* out, int B, int F, const WindowGeom& g, hipStream_t s) {
+  const dim3 grid((unsigned)(((int64_t)B * g.H * F + 255) / 256));
+  hipLaunchKernelGGL(mel_ring_blend_kernel, grid, dim3(256), 0, s, tiles, out, B, F, g);
+  TANGO_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_mel_ring_pad(const float* mel, float* dst, int B, int T, int F, int ctx, hipStream_t s) {
+  if (B <= 0 || T <= 0 || F <= 0 || ctx < 0) TANGO_FAIL("mel_ring_pad: bad sizes");
+  const dim3 grid((unsigned)(((int64_t)B * (T + 2 * ctx) * F + 255) / 256));
+  hipLaunchKernelGGL(mel_ring_pad_kernel, grid, dim3(256), 0, s, mel, dst, B, T, F, ctx);
   TANGO_HIP(hipGetLastError());
   return 0;
 }
@@ -411,6 +539,18 @@ const char* window_geom_refusal(int canvas_h, int window_h, int stride, WindowGe
     return "the windows must cover the canvas exactly: (canvas height - window_h) must be a multiple of stride";
   const int V = (canvas_h - window_h) / stride + 1;
   if (V > kMaxWindows) return "at most 32 windows per clip";
+  if (g) { g->H = canvas_h; g->Hw = window_h; g->s = stride; g->V = V; }
+  return nullptr;
+}
+
+// a ring's conditions, one message each (common.h): H >= Hw, H % s == 0, 1 <= s <= Hw, V = H / s <= kMaxWindows
+const char* ring_geom_refusal(int canvas_h, int window_h, int stride, WindowGeom* g) {
+  if (window_h <= 0) return "window_h must be positive";
+  if (canvas_h < window_h) return "the ring must be at least window_h rows long";
+  if (stride >= 1 && canvas_h % stride != 0) return "the ring's height must be a multiple of stride";
+  if (stride < 1 || stride > window_h) return "stride must be in [1, window_h]";
+  const int V = canvas_h / stride;
+  if (V > kMaxWindows) return "at most 32 windows per ring";
   if (g) { g->H = canvas_h; g->Hw = window_h; g->s = stride; g->V = V; }
   return nullptr;
 }
@@ -735,6 +875,19 @@ const char* window_args_refusal(const SchedArgs& a, int canvas_h, int window_h, 
   if (a.guided && (a.table || a.rescale > 0.0f)) return "a guidance table or rescale is not supported with windows";
   if (canvas_h <= 0) return "a windowed call states its canvas height (latent_h > 0)";
   if (const char* why = window_geom_refusal(canvas_h, window_h, stride, g)) return why;
+  if (window_h % 8 != 0) return "window_h is not a UNet height";
+  return nullptr;
+}
+
+// Why the update on a ring refuses these arguments, in this order.
+const char* ring_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, WindowGeom* g) {
+  if (a.rule == TANGO_RULE_DPM_MULTISTEP)           // first: whatever its table looks like
+    return "the multistep rule is not supported on a ring: use DDPM or DDIM";
+  if (const char* why = sched_args_refusal(a)) return why;
+  if (a.known) return "known_latents (masked-latent inpainting) is not supported on a ring";
+  if (a.guided && (a.table || a.rescale > 0.0f)) return "a guidance table or rescale is not supported on a ring";
+  if (canvas_h <= 0) return "a ring call states its canvas height (latent_h > 0)";
+  if (const char* why = ring_geom_refusal(canvas_h, window_h, stride, g)) return why;
   if (window_h % 8 != 0) return "window_h is not a UNet height";
   return nullptr;
 }

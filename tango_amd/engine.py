@@ -390,10 +390,39 @@ class Engine:
             raise ValueError("%s of height %d needs %d windows: at most 32" % (what, H, V))
         return H, hw, stride, V
 
+    def _check_ring(self, what, x, channels, window_h, stride):
+        """a loop's ring canvas [B, channels, H, latent_w] against its windows: `window_h` a height of the duration grid, 1 <= stride <=
+        window_h <= H, H a multiple of stride and V = H / stride <= 32 views that wrap round the ring.  Returns (H, window_h, stride, V)."""
+        hw = check_latent_h(window_h)
+        if int(stride) != stride or not 1 <= stride <= hw:
+            raise ValueError("stride %r must be an integer in [1, window_h = %d]" % (stride, hw))
+        stride = int(stride)
+        if x.dim() != 4 or tuple(x.shape[1::2]) != (channels, self._cfg.latent_w):
+            raise ValueError("%s must be [B, %d, H, %d], got %s" % (what, channels, self._cfg.latent_w, tuple(x.shape)))
+        H = x.shape[2]
+        if H < hw:
+            raise ValueError("%s of height %d is shorter than its windows of %d rows: a window must not meet itself on the ring" % (what, H, hw))
+        if H % stride:
+            raise ValueError("%s of height %d is no ring of windows every %d rows: H must be a multiple of stride" % (what, H, stride))
+        V = H // stride
+        if V > 32:
+            raise ValueError("%s of height %d needs %d windows: at most 32" % (what, H, V))
+        return H, hw, stride, V
+
+    def denoise_ring(self, latents, prompt_embeds, prompt_mask, timesteps, coef, guidance_scale, *, window_h, stride, **kw):
+        """In-place denoise of a seamless loop: denoise_windows with the rows of `latents` [B, 8, H, 16] on a RING.  V = H / stride
+        windows of `window_h` rows, window v covering ring rows (v * stride + y) mod H, so every row of the clip is treated alike, the
+        wrap point included (include/tango_engine.h tango_engine_denoise_ring).  stride <= window_h <= H and H % stride == 0;
+        H == window_h is the common call (a loop of one window length: V rotated views of the whole ring).  `prompt_embeds` /
+        `prompt_mask` hold one row per window as in denoise_windows; every other argument is denoise_windows'.  With
+        H == window_h == stride the result is Engine.denoise's, bit for bit."""
+        return self.denoise_windows(latents, prompt_embeds, prompt_mask, timesteps, coef, guidance_scale, window_h=window_h, stride=stride,
+                                    _ring=True, **kw)
+
     def denoise_windows(self, latents, prompt_embeds, prompt_mask, timesteps, coef, guidance_scale, *, window_h, stride,
                         prediction_type="v_prediction", rule="ddpm", clip_sample=False, clip_sample_range=1.0, noise=None, seed=0,
                         sample_offset=0, use_graph=True, prompt_mask_host=None, known_latents=None, guidance_table=None,
-                        guidance_rescale=0.0):
+                        guidance_rescale=0.0, _ring=False):
         """In-place denoise of a long clip's canvas `latents` [B, 8, H, 16] (fp32 cuda) as V = (H - window_h) / stride + 1 overlapping
         windows of `window_h` rows (a height of the duration grid) every `stride` rows: MultiDiffusion in time (include/tango_engine.h
         tango_window_args_t).  Each step runs the UNet on the (2 if guidance_scale > 1 else 1) * B * V windows as one batch and averages
@@ -402,16 +431,18 @@ class Engine:
         element.  `rule`: "ddpm" or "ddim"; the multistep rule, `known_latents`, a guidance table and a rescale are refused.  The
         other arguments are Engine.denoise's.  With H == window_h the result is Engine.denoise's, bit for bit."""
         assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
+        how, name = ("on a ring", "denoise_ring") if _ring else ("with windows", "denoise_windows")
         if rule == "dpmsolver":
-            raise ValueError("the multistep DPM-Solver rule is not supported with windows (a per-view history has no reference "
+            raise ValueError("the multistep DPM-Solver rule is not supported on a ring: use DDPM or DDIM" if _ring else
+                             "the multistep DPM-Solver rule is not supported with windows (a per-view history has no reference "
                              "behaviour): use DDPM or DDIM")
         if known_latents is not None:
-            raise ValueError("known_latents (masked-latent inpainting) is not supported with windows")
+            raise ValueError("known_latents (masked-latent inpainting) is not supported " + how)
         if guidance_table is not None or float(guidance_rescale) != 0.0:
-            raise ValueError("a guidance table or rescale is not supported with windows")
+            raise ValueError("a guidance table or rescale is not supported " + how)
         if self.unet_cfg.get("music"):
-            raise ValueError("denoise_windows serves the plain UNet: the Music UNet's conditions are not windowed")
-        H, hw, stride, V = self._check_canvas("latents", latents, self.unet_cfg["in_channels"], window_h, stride)
+            raise ValueError(name + " serves the plain UNet: the Music UNet's conditions are not windowed")
+        H, hw, stride, V = (self._check_ring if _ring else self._check_canvas)("latents", latents, self.unet_cfg["in_channels"], window_h, stride)
         enc = self._f32(prompt_embeds)
         mask = self._u8(prompt_mask)
         mask_host = prompt_mask.to(torch.uint8).contiguous() if prompt_mask is not None and not prompt_mask.is_cuda else None
@@ -448,11 +479,13 @@ class Engine:
         a.use_graph = 1 if use_graph else 0
         a.latent_h = H
         w = _lib.WindowArgs(window_h=hw, stride=stride)
-        why = self.lib.tango_debug_denoise_windows_check(C.byref(a), C.byref(w))
+        check, run = ((self.lib.tango_debug_denoise_ring_check, self.lib.tango_engine_denoise_ring) if _ring else
+                      (self.lib.tango_debug_denoise_windows_check, self.lib.tango_engine_denoise_windows))
+        why = check(C.byref(a), C.byref(w))
         if why:
             raise ValueError(why.decode())
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.tango_engine_denoise_windows(self._h, C.byref(a), C.byref(w), _stream_ptr()), "denoise_windows")
+            _lib.check(run(self._h, C.byref(a), C.byref(w), _stream_ptr()), name)
         return latents
 
     def vae_decode_tiled(self, latents, window_h, stride):
@@ -467,6 +500,20 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.tango_engine_vae_decode_tiled_h(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(mel.data_ptr()), B, H, hw,
                                                                 stride, _stream_ptr()), "vae_decode_tiled")
+        return mel
+
+    def vae_decode_ring(self, latents, window_h, stride):
+        """a loop's latents [B, embed_dim, H, 16] on a ring -> mel [B, 1, 4H, 64] on the same ring: the V = H / stride wrapping windows are
+        decoded as one batch of B * V latents of height `window_h`, and every tile fades in and out over its overlaps with its two
+        neighbours (include/tango_engine.h tango_op_mel_ring_blend).  The same geometry rules as denoise_ring."""
+        z = self._f32(latents)
+        H, hw, stride, _ = self._check_ring("vae_decode_ring: latents", z, self.vae_cfg.get("embed_dim", 8), window_h, stride)
+        nl = len(self.vae_cfg["ch_mult"])
+        B = z.shape[0]
+        mel = torch.empty((B, self.vae_cfg["out_ch"], H << (nl - 1), z.shape[3] << (nl - 1)), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.tango_engine_vae_decode_ring_h(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(mel.data_ptr()), B, H, hw,
+                                                               stride, _stream_ptr()), "vae_decode_ring")
         return mel
 
     def _check_inpaint(self, latents, n, known_latents, latent_mask, blend_coef, blend_noise):
@@ -661,5 +708,27 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.tango_engine_vocode(self._h, C.c_void_p(m.data_ptr()), C.c_void_p(wav.data_ptr()), B, T,
                                                     C.byref(ns), _stream_ptr()), "vocode")
+        assert ns.value == n
+        return wav
+
+    def vocoder_ring_context(self) -> int:
+        """the mel frames of context vocode_ring pads each side with: the vocoder's receptive field, from its configuration"""
+        return self.lib.tango_engine_vocoder_ring_context(self._h)
+
+    def vocode_ring(self, mel):
+        """mel [B,1,T,num_mels] fp32 on a ring of T frames -> int16 cuda tensor [B, hop * T] (hop = 160): the vocoder runs on the mel
+        padded circularly by vocoder_ring_context() frames, and the samples of the T frames are cut out, so that the last sample
+        joins the first (include/tango_engine.h tango_engine_vocode_ring)"""
+        m = self._f32(mel)
+        nm = self.hifigan_cfg.get("num_mels", 64)
+        if m.dim() != 4 or m.shape[1] != 1 or m.shape[3] != nm or m.shape[2] < 1:
+            raise ValueError("vocode_ring: mel must be [B, 1, T, %d], got %s" % (nm, tuple(m.shape)))
+        B, T = m.shape[0], m.shape[2]
+        n = int(np.prod(self.hifigan_cfg["upsample_rates"])) * T
+        wav = torch.empty((B, n), device=self.device, dtype=torch.int16)
+        ns = C.c_int()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.tango_engine_vocode_ring(self._h, C.c_void_p(m.data_ptr()), C.c_void_p(wav.data_ptr()), B, T,
+                                                         C.byref(ns), _stream_ptr()), "vocode_ring")
         assert ns.value == n
         return wav

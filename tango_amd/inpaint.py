@@ -94,6 +94,49 @@ def long_geometry(duration, window=10.0, hop=5.0):
     return h, hw, s, v
 
 
+def loop_geometry(duration, window=None, hop=None):
+    """A seamless loop of `duration` seconds as windows on a ring in time: -> (H, Hw, s, V) in latent rows, the ring's height
+    H = duration * 25.6, the window height Hw = duration_geometry(window)[0] <= H, the stride s = hop * 25.6 -- an integer multiple
+    of 8 rows below Hw that divides H -- and V = H / s <= 32 views, view v covering ring rows (v s + y) mod H (common.h ring_cover).
+    `window` defaults to `duration` when that is a length of generate()'s grid of at most 10 s, else to 10 s; `hop` to window / 2.
+    A duration that is no whole number of strides is a ValueError naming the nearest valid durations on both sides."""
+    try:
+        d = float(duration)
+    except (TypeError, ValueError):
+        raise ValueError("duration must be a number of seconds, got %r" % (duration,))
+    if not abs(d) * LATENT_ROWS_PER_SECOND < 2 ** 31:              # (NaN and inf end here)
+        raise ValueError("duration %r s is not a clip length" % (duration,))
+    if window is None:
+        k = d / DURATION_STEP
+        window = d if (k == int(k) and 1 <= k <= DEFAULT_DURATION / DURATION_STEP) else DEFAULT_DURATION
+    hw = duration_geometry(window)[0]
+    if hop is None:
+        hop = float(window) / 2
+    try:
+        hp = float(hop)
+    except (TypeError, ValueError):
+        raise ValueError("hop must be a number of seconds, got %r" % (hop,))
+    s = hp * LATENT_ROWS_PER_SECOND
+    if not (s == int(s) and int(s) >= 8 and int(s) % 8 == 0):       # (NaN compares false)
+        raise ValueError("hop %r s is %r latent rows: the stride must be an integer multiple of 8 rows (0.3125 s)" % (hop, s))
+    s = int(s)
+    if s >= hw:
+        raise ValueError("hop %r s is not below the window of %r s: a loop needs overlapping windows" % (hop, window))
+    if d < float(window):
+        raise ValueError("duration %r s is shorter than the window of %r s: a window must not meet itself on the ring" % (duration, window))
+    h = int(d * LATENT_ROWS_PER_SECOND + 1e-6)                      # (25.6 is no binary fraction: 1e-6 rows absorb the product's rounding)
+    if h % s or abs(d * LATENT_ROWS_PER_SECOND - h) > 1e-6:         # a fraction of a row is not rounded away silently
+        k = min(max(h // s, -(-hw // s)), MAX_WINDOWS - 1)           # at either end of the range: the two durations next to it
+        lo, hi = k * s / LATENT_ROWS_PER_SECOND, (k + 1) * s / LATENT_ROWS_PER_SECOND
+        raise ValueError("duration %r s is not a whole number of hops of %r s: the neighbouring durations are %g and %g"
+                         % (duration, hop, lo, hi))
+    v = h // s
+    if v > MAX_WINDOWS:
+        raise ValueError("duration %r s needs %d windows of %r s every %r s: at most %d (%g s)"
+                         % (duration, v, window, hop, MAX_WINDOWS, MAX_WINDOWS * s / LATENT_ROWS_PER_SECOND))
+    return h, hw, s, v
+
+
 def clip_duration(n_samples):
     """the smallest grid duration whose mel frames hold a 16 kHz clip of `n_samples` samples; 20 s for anything longer (the clip is
     then cut).  Unlike the reference's round_up_duration (pipeline.py:49-50), which always adds one more 2.5 s block -- a 5 s clip

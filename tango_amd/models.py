@@ -14,7 +14,7 @@ from typing import List, Optional
 import torch
 
 from .engine import Engine, normalize_unet_config
-from .inpaint import check_latent_h, duration_geometry, long_geometry
+from .inpaint import check_latent_h, duration_geometry, long_geometry, loop_geometry
 from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler  # noqa: F401  (re-exported like `from models import DDPMScheduler`)
 from .scheduler import DDIMInverseScheduler, cfg_enabled, check_guidance_rescale, from_diffusers, guidance_table
 
@@ -353,13 +353,23 @@ class AudioDiffusion:
         `prompt_embeds` / `boolean_prompt_mask` as in inference_from_embeddings ([uncond; cond] with guidance): their rows are repeated
         per window here.  `noise` [N, B, 8, H, 16] is canvas-shaped.  DDPM and DDIM schedulers; a DPM-Solver scheduler, a guidance
         table and a rescale are refused."""
-        H, hw, stride, V = long_geometry(duration, window, hop)
+        return self._windowed_from_embeddings(False, long_geometry(duration, window, hop), prompt_embeds, boolean_prompt_mask,
+                                              inference_scheduler, num_steps, guidance_scale, duration, latents, noise, seed,
+                                              sample_offset, mask_host)
+
+    def _windowed_from_embeddings(self, ring, geometry, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale,
+                                  duration, latents, noise, seed, sample_offset, mask_host):
+        """inference_long_from_embeddings (ring False: Engine.denoise_windows) and inference_loop_from_embeddings (ring True:
+        Engine.denoise_ring) once the geometry is known"""
+        H, hw, stride, V = geometry
+        how = "on a ring" if ring else "with windows"
         if not isinstance(guidance_scale, (int, float)):
-            raise ValueError("a guidance table is not supported with windows: guidance_scale must be a scalar")
+            raise ValueError("a guidance table is not supported %s: guidance_scale must be a scalar" % how)
         if not hasattr(inference_scheduler, "coef_table"):
             inference_scheduler = from_diffusers(inference_scheduler)
         if inference_scheduler.rule == "dpmsolver":
-            raise ValueError("the multistep DPM-Solver rule is not supported with windows (a per-view history has no reference "
+            raise ValueError("the multistep DPM-Solver rule is not supported on a ring: use DDPM or DDIM" if ring else
+                             "the multistep DPM-Solver rule is not supported with windows (a per-view history has no reference "
                              "behaviour): use DDPM or DDIM")
         cfg_on = guidance_scale > 1.0
         B = prompt_embeds.shape[0] // 2 if cfg_on else prompt_embeds.shape[0]
@@ -379,11 +389,11 @@ class AudioDiffusion:
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.seed is None else (int(self.seed) << 20) + self._calls
         self._calls += 1
-        self.engine.denoise_windows(latents, pe, pm, inference_scheduler.timesteps.cpu().numpy(), inference_scheduler.coef_table(),
-                                    guidance_scale, window_h=hw, stride=stride, prediction_type=c.prediction_type,
-                                    rule=inference_scheduler.rule, clip_sample=c.clip_sample,
-                                    clip_sample_range=getattr(c, "clip_sample_range", 1.0), noise=noise, seed=seed,
-                                    sample_offset=sample_offset, use_graph=self.use_graph, prompt_mask_host=mask_host)
+        run = self.engine.denoise_ring if ring else self.engine.denoise_windows
+        run(latents, pe, pm, inference_scheduler.timesteps.cpu().numpy(), inference_scheduler.coef_table(), guidance_scale, window_h=hw,
+            stride=stride, prediction_type=c.prediction_type, rule=inference_scheduler.rule, clip_sample=c.clip_sample,
+            clip_sample_range=getattr(c, "clip_sample_range", 1.0), noise=noise, seed=seed, sample_offset=sample_offset,
+            use_graph=self.use_graph, prompt_mask_host=mask_host)
         return latents
 
     @torch.no_grad()
@@ -399,6 +409,34 @@ class AudioDiffusion:
             pe = pe.repeat_interleave(num_samples_per_prompt, 0)
             pm = pm.repeat_interleave(num_samples_per_prompt, 0)
         return self.inference_long_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, duration, window, hop,
+                                                   seed=seed, sample_offset=sample_offset, mask_host=host)
+
+    # ---- seamless loops: the same windows on a ring in time (include/tango_engine.h tango_engine_denoise_ring) ----------------------
+    @torch.no_grad()
+    def inference_loop_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3,
+                                       duration=10, window=None, hop=None, latents=None, noise=None, seed=None, sample_offset=0,
+                                       mask_host=None):
+        """inference_long_from_embeddings for a clip that is played in a loop: the canvas [B, 8, H, 16] (H = duration * 25.6) is a ring
+        in time, denoised as V = H / stride windows that wrap round it (tango_amd.inpaint.loop_geometry; Engine.denoise_ring), so row
+        H - 1 joins row 0 as any two neighbouring rows join.  `duration` >= `window`; by default one window of the clip's own length
+        (up to 10 s) every half window.  The other arguments and the refusals are inference_long_from_embeddings'."""
+        return self._windowed_from_embeddings(True, loop_geometry(duration, window, hop), prompt_embeds, boolean_prompt_mask,
+                                              inference_scheduler, num_steps, guidance_scale, duration, latents, noise, seed,
+                                              sample_offset, mask_host)
+
+    @torch.no_grad()
+    def inference_loop(self, prompt, inference_scheduler, num_steps=20, guidance_scale=3, num_samples_per_prompt=1, duration=10,
+                       window=None, hop=None, negative_prompt=None, seed=None, sample_offset=0):
+        """inference() for a seamless loop (inference_loop_from_embeddings): ring latents [B*S, 8, duration * 25.6, 16]"""
+        loop_geometry(duration, window, hop)
+        host = None
+        if cfg_enabled(guidance_scale):
+            pe, pm, host = self._encode_text_classifier_free(prompt, num_samples_per_prompt, negative_prompt)
+        else:
+            pe, pm = self.encode_text(prompt)
+            pe = pe.repeat_interleave(num_samples_per_prompt, 0)
+            pm = pm.repeat_interleave(num_samples_per_prompt, 0)
+        return self.inference_loop_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, duration, window, hop,
                                                    seed=seed, sample_offset=sample_offset, mask_host=host)
 
     # ---- masked-latent inpainting (audioldm/pipeline.py:249-301, ldm.py:724-818, ddim.py:207-233) ------------------------------

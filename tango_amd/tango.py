@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from .autoencoder import AutoencoderKL
-from .inpaint import clip_duration, duration_geometry, latent_mask, long_geometry, prepare_waveform
+from .inpaint import clip_duration, duration_geometry, latent_mask, long_geometry, loop_geometry, prepare_waveform
 from .models import AudioDiffusion
 from .scheduler import SD21_SCHEDULER_CONFIG, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 from .scheduler import cfg_enabled, check_guidance_rescale, guidance_is_table
@@ -132,6 +132,33 @@ class Tango:
                                                     negative_prompt=negative_prompt, seed=seed, sample_offset=k)
                 mel = self.vae.engine.vae_decode_tiled(latents, hw, stride)
                 waves.append(self.vae.decode_to_waveform(mel))
+        return np.concatenate(waves)
+
+    def generate_loop(self, prompt, duration, steps=100, guidance=3, samples=1, window=None, hop=None, negative_prompt=None, seed=None):
+        """ Generate `duration` seconds of audio that plays in a loop without a click or a jump at the wrap: MultiDiffusion on a ring in
+        time.  The latent canvas is a ring, denoised as V windows of `window` seconds every `hop` seconds that wrap round it
+        (AudioDiffusion.inference_loop), decoded window by window with every tile cross-faded into both neighbours
+        (Engine.vae_decode_ring) and vocoded with circular context (Engine.vocode_ring).  `window` defaults to `duration` when that is
+        a length of generate()'s grid of at most 10 s, else to 10; `hop` to window / 2; `duration` must be a whole number of hops
+        (tango_amd.inpaint.loop_geometry names the neighbours otherwise), at most 32 windows.  DDPM or DDIM scheduler; a DPM-Solver
+        scheduler and a guidance table are refused.  `seed` and the chunking of samples as in generate_long.
+        Returns np.int16 [samples, 640 * H]: exactly the ring's samples (163 840 for 10 s, where generate() returns 163 872). """
+        H, hw, stride, V = loop_geometry(duration, window, hop)
+        if not isinstance(guidance, (int, float)):
+            raise ValueError("a guidance table is not supported on a ring: guidance must be a scalar")
+        if getattr(self.scheduler, "rule", None) == "dpmsolver":
+            raise ValueError("the multistep DPM-Solver rule is not supported on a ring: use DDPM or DDIM")
+        per_call = max(1, self.LONG_MAX_ROWS // ((2 if cfg_enabled(guidance) else 1) * V))
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        waves = []
+        with torch.no_grad():
+            for k in range(0, samples, per_call):
+                n = min(per_call, samples - k)
+                latents = self.model.inference_loop([prompt], self.scheduler, steps, guidance, n, duration, window, hop,
+                                                    negative_prompt=negative_prompt, seed=seed, sample_offset=k)
+                mel = self.vae.engine.vae_decode_ring(latents, hw, stride)
+                waves.append(self.vae.engine.vocode_ring(mel).cpu().numpy())
         return np.concatenate(waves)
 
     def generate_for_batch(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, disable_progress=True, duration=10,
