@@ -273,6 +273,30 @@ int tango_engine_denoise_ring(tango_engine_t* h, const tango_denoise_args_t* arg
 /* host-side query, no GPU needed: "" when tango_engine_denoise_ring accepts these arguments as far as its argument checks go (window_h is
  * only asked to be a multiple of 8), else the message it fails with */
 const char* tango_debug_denoise_ring_check(const tango_denoise_args_t* args, const tango_window_args_t* win);
+
+/* Timed prompts: tango_engine_denoise_windows / tango_engine_denoise_ring with a TAPERED weight per window row (weighted MultiDiffusion,
+ * "Mixture of Diffusers", Jimenez 2023).  Both calls already take one text row per window (row half * B * V + b * V + v), so windows of one
+ * sample may run under different prompts; with equal weights every view would count in full up to the row where it ends and the canvas
+ * would see a step in the mixture at every window edge.  view_weights is a HOST table of window_h floats, one weight per local window row,
+ * shared by all views.  Per step and canvas element, over the covering views in exactly the unweighted call's order (ascending; on a ring,
+ * the ring's order), with d_v the unweighted call's per-view value:
+ *   acc = 0; wsum = 0;   t = w[y_v] * d_v; acc = acc + t; wsum = wsum + w[y_v];   r = acc / wsum (IEEE division);   + sigma * one draw
+ * in fp32 without FMA contraction.  With all weights 1.0 the result is the unweighted call's, bit for bit; with one covering view and
+ * w != 1, (w d) / w may differ from d in the last bit.  The profile of timed prompts is, with E = window_h - stride,
+ * w[y] = min(1, (y + 0.5) / E) * min(1, (window_h - y - 0.5) / E) (1 when E == 0): tango_op_mel_ring_blend's.  Any table is taken.
+ * Refused: whatever the unweighted call refuses, with the same messages under the prefix "denoise_windows_weighted: " /
+ * "denoise_ring_weighted: "; then a NULL table, and a table with a non-finite entry or an entry <= 0.  The table is copied into a buffer
+ * of the engine before the call returns to its loop; a weighted and an unweighted call of one shape share the UNet plan and replay
+ * captured steps of their own. */
+int tango_engine_denoise_windows_weighted(tango_engine_t* h, const tango_denoise_args_t* args, const tango_window_args_t* win,
+                                          const float* view_weights /* HOST [window_h] */, void* stream);
+int tango_engine_denoise_ring_weighted(tango_engine_t* h, const tango_denoise_args_t* args, const tango_window_args_t* win,
+                                       const float* view_weights /* HOST [window_h] */, void* stream);
+/* host-side queries, no GPU needed: "" when the weighted call accepts these arguments as far as its argument checks go, else its message */
+const char* tango_debug_denoise_windows_weighted_check(const tango_denoise_args_t* args, const tango_window_args_t* win,
+                                                       const float* view_weights);
+const char* tango_debug_denoise_ring_weighted_check(const tango_denoise_args_t* args, const tango_window_args_t* win,
+                                                    const float* view_weights);
 /* ring latents [B, embed_dim, canvas_h, latent_w] -> mel [B, 1, 4 canvas_h, 64] on the same ring: the V = canvas_h / stride wrapping windows
  * go through the decoder at batch B * V and height window_h, and the tiles are cross-faded as tango_op_mel_ring_blend says. */
 int tango_engine_vae_decode_ring_h(tango_engine_t* h, const float* latents, float* mel, int batch, int canvas_h, int window_h, int stride,
@@ -544,6 +568,14 @@ int tango_op_mel_tile_blend(const float* tiles, float* out, int B, int V, int Hw
 int tango_op_sched_ring(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H, int W,
                         int Hw, int s, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
                         int sample_offset, int step, void* stream);
+/* tango_op_sched_windows / tango_op_sched_ring with view_weights HOST [Hw] (tango_engine_denoise_windows_weighted): the weighted mean of
+ * the views.  They refuse what those refuse, then a NULL or bad table.  Synchronise. */
+int tango_op_sched_windows_weighted(float* latents, const float* model_out_nchw, const float* noise, const float* coef8,
+                                    const float* view_weights, int B, int C, int H, int W, int Hw, int s, int cfg, float guidance, int pred_type,
+                                    int rule, int clip, float clip_range, uint64_t seed, int sample_offset, int step, void* stream);
+int tango_op_sched_ring_weighted(float* latents, const float* model_out_nchw, const float* noise, const float* coef8,
+                                 const float* view_weights, int B, int C, int H, int W, int Hw, int s, int cfg, float guidance, int pred_type,
+                                 int rule, int clip, float clip_range, uint64_t seed, int sample_offset, int step, void* stream);
 /* cross-fade of decoded tiles on a ring: tiles DEVICE fp32 [B * V, 1, Hw4, F], tile t holding ring rows (t s4 + y) mod (V s4) -> out DEVICE
  * fp32 [B, 1, V s4, F].  Every tile has a predecessor and a successor: with E = Hw4 - s4 the weight at local row y is
  * min(1, (y + 0.5) / E) * min(1, (Hw4 - y - 0.5) / E) (1 when E == 0); out[r] = (sum w tile) / (sum w) over the covering tiles in the ring

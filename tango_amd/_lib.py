@@ -143,6 +143,8 @@ SYMBOLS = [
     "tango_op_sched_windows", "tango_op_mel_tile_blend",
     "tango_engine_denoise_ring", "tango_debug_denoise_ring_check", "tango_engine_vae_decode_ring_h", "tango_engine_vocode_ring",
     "tango_engine_vocoder_ring_context", "tango_op_sched_ring", "tango_op_mel_ring_blend", "tango_op_mel_ring_pad",
+    "tango_engine_denoise_windows_weighted", "tango_engine_denoise_ring_weighted", "tango_debug_denoise_windows_weighted_check",
+    "tango_debug_denoise_ring_weighted_check", "tango_op_sched_windows_weighted", "tango_op_sched_ring_weighted",
 ]
 
 _lib = None
@@ -189,6 +191,13 @@ def load():
     lib.tango_op_sched_ring.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci, cf, C.c_uint64, ci, ci, vp]
     lib.tango_op_mel_ring_blend.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
     lib.tango_op_mel_ring_pad.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+    for f in (lib.tango_engine_denoise_windows_weighted, lib.tango_engine_denoise_ring_weighted):
+        f.argtypes = [vp, C.POINTER(DenoiseArgs), C.POINTER(WindowArgs), vp, vp]
+    for f in (lib.tango_debug_denoise_windows_weighted_check, lib.tango_debug_denoise_ring_weighted_check):
+        f.argtypes = [C.POINTER(DenoiseArgs), C.POINTER(WindowArgs), vp]
+        f.restype = C.c_char_p
+    for f in (lib.tango_op_sched_windows_weighted, lib.tango_op_sched_ring_weighted):
+        f.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci, cf, C.c_uint64, ci, ci, vp]
     lib.tango_engine_unet_forward.argtypes = [vp, vp, i64, vp, vp, vp, ci, ci, vp]
     lib.tango_engine_unet_forward_music.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.tango_engine_vae_decode.argtypes = [vp, vp, vp, ci, vp]

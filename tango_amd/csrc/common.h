@@ -505,6 +505,7 @@ struct SchedWindowParams {
   WindowGeom g;
   int W = 0;
   int noise_row0 = 0;                // loop index of the first entry of p.noise (the one-step hook passes the row of its step alone)
+  const float* weights = nullptr;    // weighted kernels only: DEVICE [g.Hw] positive weights, one per local window row, shared by all views
 };
 static_assert(std::is_trivially_copyable<SchedWindowParams>::value, "SchedWindowParams is memcpy'd to the device");
 // sched_window_kernel (rules 0 / 1): one thread per canvas position; the grid covers max_positions >= B * H * W
@@ -534,6 +535,12 @@ __host__ __device__ inline int ring_cover(const WindowGeom& g, int h, int* v0, i
 }
 // sched_window_kernel's ring form (rules 0 / 1) on a SchedWindowParams block whose g is a ring; the grid covers max_positions >= B * H * W
 int launch_sched_ring(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s);
+// timed prompts: the WEIGHTED forms of both (the block's `weights` is set): r = (sum w[y_v] d_v) / (sum w[y_v]) over the same views in the
+// same order.  The unweighted launchers above never read `weights`.
+int launch_sched_windows_weighted(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s);
+int launch_sched_ring_weighted(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s);
+// why a weighted update refuses its HOST table of window_h floats (nullptr: it does not): NULL, a non-finite entry, an entry <= 0
+const char* view_weights_refusal(const float* weights, int window_h);
 // the two gathers with source row (v s + y) mod H
 int launch_ring_gather(int dtype, const float* lat, void* xin, int64_t ld, int B, int C, int W, const WindowGeom& g, int rep, hipStream_t s);
 int launch_ring_gather_nchw(const float* lat, float* dst, int B, int C, int W, const WindowGeom& g, hipStream_t s);

@@ -174,6 +174,9 @@ struct UNetPlan : Plan {
   StepGraphs wgraphs;
   // ... and a call on a ring (Engine::denoise_ring) the ring form of that kernel: plain, windowed and ring calls of one shape share the plan
   StepGraphs rgraphs;
+  // ... and the weighted forms of both (timed prompts, Engine::denoise_windows / denoise_ring with a table of view weights): a weighted and
+  // an unweighted call of one shape share the plan and each replays its own graphs
+  StepGraphs wwgraphs, rwgraphs;
   // Two independent chains (round 5; Engine::denoise): a "dual" plan owns only the UNet input / output buffers of the whole batch; its
   // two children run the first and the second half of the samples (no op of the UNet crosses samples) as two branches of the captured
   // graph, so that one branch's dispatch gaps and kernel tails are filled by the other's kernels.  A child takes xin / eps from its
@@ -228,6 +231,9 @@ class Engine {
   int vae_decode_tiled(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s);
   // loops: the same with the canvas rows on a ring (V = a.latent_h / w.stride views that wrap), and the vocoder on a ring of mel frames
   int denoise_ring(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s);
+  // timed prompts: both with view_weights HOST [w.window_h], a positive weight per local window row -- the update is the weighted mean
+  int denoise_windows_weighted(const tango_denoise_args_t& a, const tango_window_args_t& w, const float* view_weights, hipStream_t s);
+  int denoise_ring_weighted(const tango_denoise_args_t& a, const tango_window_args_t& w, const float* view_weights, hipStream_t s);
   int vae_decode_ring(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s);
   int vocode_ring(const float* mel, int16_t* wav, int B, int frames, int* n_samples, hipStream_t s);
   int vocoder_ring_context() const;     // mel frames of context vocode_ring pads each side with: the vocoder's receptive field
@@ -340,6 +346,7 @@ class Engine {
   unsigned* d_sync = nullptr;   // barrier words of the cooperative kernels (common.h: coop_sync_words()), zeroed once at init
   SchedParams* d_sched = nullptr;   // device copy of the current call's scheduler parameter block
   SchedWindowParams* d_wsched = nullptr;   // ... of the current windowed call's block (captured windowed steps read this one)
+  float* d_wweights = nullptr;   // [kMaxLatentH] the current weighted call's view weights (the block's `weights` points here)
   int64_t* d_ts = nullptr;       // [max_steps]
   float* d_coef = nullptr;       // [max_steps][16] (DDPM / DDIM rows use the first 8 floats of a packed [N][8] table)
   float* d_bcoef = nullptr;      // [max_steps][2] add_noise scalars of the masked loop's blend (tango_denoise_args_t.blend_coef)
@@ -415,8 +422,9 @@ class Engine {
   // how a guidance / plain batch of B2 UNet rows runs; profile_unet() asks with two_chains_ok = false
   UNetMode unet_mode_for(int B2, int n_short, bool cfg_on, bool two_chains_ok) const;
   // which update closes a step: the kernel is fixed when a step is captured
-  struct StepKind { int rule = 0; bool masked = false, guided = false, windowed = false, ring = false; };   // ring: a windowed step on a ring
-  int denoise_windowed(const tango_denoise_args_t& a, const tango_window_args_t& w, bool ring, hipStream_t s);
+  // ring: a windowed step on a ring; weighted: a windowed step that weights its views by the block's table
+  struct StepKind { int rule = 0; bool masked = false, guided = false, windowed = false, ring = false, weighted = false; };
+  int denoise_windowed(const tango_denoise_args_t& a, const tango_window_args_t& w, bool ring, const float* view_weights, bool weighted, hipStream_t s);
   int vae_decode_windowed(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, bool ring, hipStream_t s);
   int run_step(const UNetPlan& P, const StepKind& k, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
   int capture_steps(const UNetPlan& P, const StepKind& k, int n, hipGraph_t* g_out, hipGraphExec_t* x_out);

@@ -557,6 +557,8 @@ void Engine::free_plan(Plan& P) {
         for (StepGraphs& g : row) drop(g);
     drop(U.wgraphs);
     drop(U.rgraphs);
+    drop(U.wwgraphs);
+    drop(U.rwgraphs);
     for (auto& c : U.child) if (c) { free_plan(*c); c.reset(); }
   }
   // a slab may still be read by work queued on a stream: hipFree synchronises the device before it releases memory
@@ -1005,13 +1007,14 @@ int Engine::init() {
     d_step = (int*)dmalloc(256);
     d_sched = (SchedParams*)dmalloc(sizeof(SchedParams));
     d_wsched = (SchedWindowParams*)dmalloc(sizeof(SchedWindowParams));
+    d_wweights = (float*)dmalloc((size_t)kMaxLatentH * 4);
     d_ts = (int64_t*)dmalloc((size_t)max_steps * 8);
     d_coef = (float*)dmalloc((size_t)max_steps * 16 * 4);
     d_bcoef = (float*)dmalloc((size_t)max_steps * 2 * 4);
     d_sin = (float*)dmalloc((size_t)max_steps * cfg.unet_channels[0] * 4);
     d_t1 = (float*)dmalloc((size_t)max_steps * temb * 4);
     d_temb = (float*)dmalloc((size_t)max_steps * temb * 4);
-    if (!d_step || !d_sched || !d_ts || !d_coef || !d_sin || !d_t1 || !d_temb) return -1;
+    if (!d_step || !d_sched || !d_wsched || !d_wweights || !d_ts || !d_coef || !d_sin || !d_t1 || !d_temb) return -1;
   }
   if (cfg.vae_levels > 0) build_vae_weights();
   if (cfg.vae_levels > 0 && cfg.vae_encoder) {
@@ -1507,8 +1510,10 @@ int Engine::run_step(const UNetPlan& P, const StepKind& k, hipStream_t st, hipSt
   }
   if (k.windowed) {
     // (a ring of H = V s <= V Hw rows has no more positions than its window batch either)
-    if (k.ring) TANGO_TRY(launch_sched_ring(dt, d_wsched, P.B2 * P.H * cfg.latent_w, st));
-    else TANGO_TRY(launch_sched_windows(dt, d_wsched, P.B2 * P.H * cfg.latent_w, st));
+    const int np = P.B2 * P.H * cfg.latent_w;
+    if (k.weighted) TANGO_TRY(k.ring ? launch_sched_ring_weighted(dt, d_wsched, np, st) : launch_sched_windows_weighted(dt, d_wsched, np, st));
+    else if (k.ring) TANGO_TRY(launch_sched_ring(dt, d_wsched, np, st));
+    else TANGO_TRY(launch_sched_windows(dt, d_wsched, np, st));
     return launch_step_inc(d_step, st);
   }
   if (k.guided) TANGO_TRY(launch_guidance_stats(d_sched, P.B2 / 2, P.H * cfg.latent_w, st));
@@ -1640,26 +1645,37 @@ int Engine::run_loop(UNetPlan& P, StepGraphs& G, const StepKind& k, int num_step
 // single-key prefix and the condition binding are those of a plain call of that batch.
 // Loops (tango_engine_denoise_ring): the same call with the canvas rows on a ring -- V = latent_h / stride views that wrap round it
 // (common.h ring_cover), the ring forms of the gather and of the update, and captured steps of their own (UNetPlan::rgraphs).
-static int check_window_args(const tango_denoise_args_t& a, const tango_window_args_t& w, WindowGeom* g, bool ring = false) {
+// Timed prompts (tango_engine_denoise_windows_weighted / _ring_weighted): the same calls with a table of view weights, staged into
+// d_wweights; the update is the WEIGHTED form of the kernel, with captured steps of its own (UNetPlan::wwgraphs / rwgraphs).  `weighted`:
+// the messages carry the weighted call's prefix and the table is checked last.
+static int check_window_args(const tango_denoise_args_t& a, const tango_window_args_t& w, WindowGeom* g, bool ring = false,
+                             bool weighted = false, const float* view_weights = nullptr) {
+  const std::string who = std::string(ring ? "denoise_ring" : "denoise_windows") + (weighted ? "_weighted: " : ": ");
   SchedArgs c;
   c.rule = a.rule; c.coef = a.coef; c.coef_w = a.coef_width ? a.coef_width : 8; c.num_rows = c.row1 = a.num_steps;
   c.noise = a.noise != nullptr; c.clip = a.clip_sample != 0;
   c.known = a.known_latents; c.mask = a.latent_mask; c.blend_coef = a.blend_coef; c.blend_noise = a.blend_noise;
-  if (ring) {
-    if (const char* why = ring_args_refusal(c, a.latent_h, w.window_h, w.stride, g)) TANGO_FAIL(std::string("denoise_ring: ") + why);
-    return 0;
-  }
-  if (const char* why = window_args_refusal(c, a.latent_h, w.window_h, w.stride, g)) TANGO_FAIL(std::string("denoise_windows: ") + why);
+  if (const char* why = ring ? ring_args_refusal(c, a.latent_h, w.window_h, w.stride, g) : window_args_refusal(c, a.latent_h, w.window_h, w.stride, g))
+    TANGO_FAIL(who + why);
+  if (weighted)
+    if (const char* why = view_weights_refusal(view_weights, w.window_h)) TANGO_FAIL(who + why);
   return 0;
 }
 
-int Engine::denoise_windows(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) { return denoise_windowed(a, w, false, s); }
-int Engine::denoise_ring(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) { return denoise_windowed(a, w, true, s); }
+int Engine::denoise_windows(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) { return denoise_windowed(a, w, false, nullptr, false, s); }
+int Engine::denoise_ring(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) { return denoise_windowed(a, w, true, nullptr, false, s); }
+int Engine::denoise_windows_weighted(const tango_denoise_args_t& a, const tango_window_args_t& w, const float* view_weights, hipStream_t s) {
+  return denoise_windowed(a, w, false, view_weights, true, s);
+}
+int Engine::denoise_ring_weighted(const tango_denoise_args_t& a, const tango_window_args_t& w, const float* view_weights, hipStream_t s) {
+  return denoise_windowed(a, w, true, view_weights, true, s);
+}
 
-int Engine::denoise_windowed(const tango_denoise_args_t& a, const tango_window_args_t& w, bool ring, hipStream_t s) {
+int Engine::denoise_windowed(const tango_denoise_args_t& a, const tango_window_args_t& w, bool ring, const float* view_weights, bool weighted,
+                             hipStream_t s) {
   WindowGeom g;
-  TANGO_TRY(check_window_args(a, w, &g, ring));
-  if (a.batch <= 0) TANGO_FAIL(std::string(ring ? "denoise_ring" : "denoise_windows") + ": batch must be positive");
+  TANGO_TRY(check_window_args(a, w, &g, ring, weighted, view_weights));
+  if (a.batch <= 0) TANGO_FAIL(std::string(ring ? "denoise_ring" : "denoise_windows") + (weighted ? "_weighted" : "") + ": batch must be positive");
   int Hw;
   TANGO_TRY(resolve_h(w.window_h, true, &Hw));       // window_h is a UNet height of this configuration
   const bool cfg_on = a.guidance_scale > 1.0f;
@@ -1679,6 +1695,10 @@ int Engine::denoise_windowed(const tango_denoise_args_t& a, const tango_window_a
   sp.pred_type = a.prediction_type; sp.rule = a.rule; sp.clip = a.clip_sample; sp.clip_range = a.clip_sample_range;
   sp.seed = a.seed; sp.sample_offset = a.sample_offset; sp.num_steps = a.num_steps;
   wp.g = g; wp.W = W;
+  if (weighted) {
+    wp.weights = d_wweights;                          // Hw <= kMaxLatentH (resolve_h)
+    TANGO_TRY(stage_h2d(d_wweights, view_weights, (size_t)Hw * 4, s));
+  }
   TANGO_TRY(stage_h2d(d_coef, a.coef, (size_t)a.num_steps * 8 * 4, s));
   TANGO_TRY(stage_h2d(d_wsched, &wp, sizeof(SchedWindowParams), s));
   TANGO_HIP(hipMemsetAsync(d_step, 0, 4, s));
@@ -1693,8 +1713,9 @@ int Engine::denoise_windowed(const tango_denoise_args_t& a, const tango_window_a
   if (ring) TANGO_TRY(launch_ring_gather(dt, a.latents, P->xin, 8, B, C, W, g, cfg_on ? 2 : 1, s));
   else TANGO_TRY(launch_window_gather(dt, a.latents, P->xin, 8, B, C, W, g, cfg_on ? 2 : 1, s));
   StepKind k;
-  k.rule = a.rule; k.windowed = true; k.ring = ring;
-  return run_loop(*P, ring ? P->rgraphs : P->wgraphs, k, a.num_steps, a.use_graph != 0, s);
+  k.rule = a.rule; k.windowed = true; k.ring = ring; k.weighted = weighted;
+  StepGraphs& G = weighted ? (ring ? P->rwgraphs : P->wwgraphs) : (ring ? P->rgraphs : P->wgraphs);
+  return run_loop(*P, G, k, a.num_steps, a.use_graph != 0, s);
 }
 
 int Program::run_profiled(hipStream_t s, std::string& report) const {
@@ -2361,6 +2382,30 @@ const char* tango_debug_denoise_ring_check(const tango_denoise_args_t* a, const 
   tango::WindowGeom g;
   if (tango::check_window_args(*a, *w, &g, true) != 0) msg = tango_last_error();
   return msg.c_str();
+}
+int tango_engine_denoise_windows_weighted(tango_engine_t* h, const tango_denoise_args_t* a, const tango_window_args_t* w,
+                                          const float* view_weights, void* stream) {
+  if (!h || !a || !w) { tango::set_error("denoise_windows_weighted: null args"); return -1; }
+  return h->e->denoise_windows_weighted(*a, *w, view_weights, (hipStream_t)stream);
+}
+int tango_engine_denoise_ring_weighted(tango_engine_t* h, const tango_denoise_args_t* a, const tango_window_args_t* w,
+                                       const float* view_weights, void* stream) {
+  if (!h || !a || !w) { tango::set_error("denoise_ring_weighted: null args"); return -1; }
+  return h->e->denoise_ring_weighted(*a, *w, view_weights, (hipStream_t)stream);
+}
+static const char* weighted_check(const tango_denoise_args_t* a, const tango_window_args_t* w, const float* view_weights, bool ring) {
+  static thread_local std::string msg;
+  msg.clear();
+  if (!a || !w) return ring ? "denoise_ring_weighted: null args" : "denoise_windows_weighted: null args";
+  tango::WindowGeom g;
+  if (tango::check_window_args(*a, *w, &g, ring, true, view_weights) != 0) msg = tango_last_error();
+  return msg.c_str();
+}
+const char* tango_debug_denoise_windows_weighted_check(const tango_denoise_args_t* a, const tango_window_args_t* w, const float* view_weights) {
+  return weighted_check(a, w, view_weights, false);
+}
+const char* tango_debug_denoise_ring_weighted_check(const tango_denoise_args_t* a, const tango_window_args_t* w, const float* view_weights) {
+  return weighted_check(a, w, view_weights, true);
 }
 int tango_engine_vae_decode_ring_h(tango_engine_t* h, const float* latents, float* mel, int batch, int canvas_h, int window_h, int stride,
                                    void* stream) {

@@ -1015,17 +1015,20 @@ int tango_op_sched_guided(float* latents, const float* model_out_nchw, const flo
   return op_sched(o);
 }
 
-// the windowed update's hook, linear (tango_op_sched_windows) or on a ring (tango_op_sched_ring)
-static int op_sched_windowed(bool ring, float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H,
+// the windowed update's hook, linear (tango_op_sched_windows) or on a ring (tango_op_sched_ring); `weighted`: their _weighted forms, with
+// view_weights HOST [Hw]
+static int op_sched_windowed(bool ring, bool weighted, const float* view_weights, float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H,
                              int W, int Hw, int sw, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
                              int sample_offset, int step, void* stream) {
-  const std::string w(ring ? "op_sched_ring" : "op_sched_windows");
+  const std::string w(std::string(ring ? "op_sched_ring" : "op_sched_windows") + (weighted ? "_weighted" : ""));
   if (B <= 0 || C <= 0 || W <= 0 || step < 0 || sample_offset < 0) TANGO_FAIL(w + ": bad sizes");
   if (!latents || !model_out_nchw || !coef8) TANGO_FAIL(w + ": latents, model_out_nchw and coef8 are required");
   SchedArgs c;                      // the engine's own rules; the single row is the row of this step
   c.rule = rule; c.coef = coef8; c.coef_w = 8; c.num_rows = 1; c.row0 = 0; c.row1 = 1; c.noise = noise != nullptr; c.clip = clip != 0;
   WindowGeom g;
   if (const char* why = ring ? ring_args_refusal(c, H, Hw, sw, &g) : window_args_refusal(c, H, Hw, sw, &g)) TANGO_FAIL(w + ": " + why);
+  if (weighted)
+    if (const char* why = view_weights_refusal(view_weights, Hw)) TANGO_FAIL(w + ": " + why);
   if (!noise && C % 4 != 0) TANGO_FAIL(w + ": the Philox stream draws four channels at a time: C must be a multiple of 4");
   const int B2 = cfg ? 2 * B : B, rows = B2 * g.V, win = Hw * W;
   if ((int64_t)rows * win * C >= ((int64_t)1 << 31)) TANGO_FAIL(w + ": B2 * V * Hw * W * C must stay below 2^31");
@@ -1035,7 +1038,9 @@ static int op_sched_windowed(bool ring, float* latents, const float* model_out_n
   float* dcoef = (float*)sc.get((size_t)(step + 1) * 8 * 4);
   int* dstep = (int*)sc.get(256);
   SchedWindowParams* dp = (SchedWindowParams*)sc.get(sizeof(SchedWindowParams));
-  if (!eps || !xin || !dcoef || !dstep || !dp) TANGO_FAIL(w + ": alloc");
+  float* dwt = weighted ? (float*)sc.get((size_t)Hw * 4) : nullptr;
+  if (!eps || !xin || !dcoef || !dstep || !dp || (weighted && !dwt)) TANGO_FAIL(w + ": alloc");
+  if (weighted) TANGO_HIP(hipMemcpyAsync(dwt, view_weights, (size_t)Hw * 4, hipMemcpyHostToDevice, s));
   TANGO_TRY(launch_nchw_to_nhwc(DT_F32, model_out_nchw, eps, C, rows, C, win, 1, 1.0f, s));
   TANGO_HIP(hipMemcpyAsync(dcoef + (size_t)step * 8, coef8, 8 * 4, hipMemcpyHostToDevice, s));
   TANGO_HIP(hipMemcpyAsync(dstep, &step, 4, hipMemcpyHostToDevice, s));
@@ -1044,9 +1049,10 @@ static int op_sched_windowed(bool ring, float* latents, const float* model_out_n
   p.lat = latents; p.eps = eps; p.xin = xin; p.xin_ld = C; p.noise = noise; p.coef = dcoef; p.step_ptr = dstep;
   p.B = B; p.C = C; p.HW = H * W; p.cfg = cfg ? 1 : 0; p.guidance = guidance; p.pred_type = pred_type; p.rule = rule;
   p.clip = clip; p.clip_range = clip_range; p.seed = seed; p.sample_offset = sample_offset; p.num_steps = step + 1;
-  wp.g = g; wp.W = W; wp.noise_row0 = step;
+  wp.g = g; wp.W = W; wp.noise_row0 = step; wp.weights = dwt;
   TANGO_HIP(hipMemcpyAsync(dp, &wp, sizeof(SchedWindowParams), hipMemcpyHostToDevice, s));
-  if (ring) TANGO_TRY(launch_sched_ring(DT_F32, dp, B * H * W, s));
+  if (weighted) TANGO_TRY(ring ? launch_sched_ring_weighted(DT_F32, dp, B * H * W, s) : launch_sched_windows_weighted(DT_F32, dp, B * H * W, s));
+  else if (ring) TANGO_TRY(launch_sched_ring(DT_F32, dp, B * H * W, s));
   else TANGO_TRY(launch_sched_windows(DT_F32, dp, B * H * W, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
@@ -1055,14 +1061,26 @@ static int op_sched_windowed(bool ring, float* latents, const float* model_out_n
 int tango_op_sched_windows(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H, int W,
                            int Hw, int sw, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
                            int sample_offset, int step, void* stream) {
-  return op_sched_windowed(false, latents, model_out_nchw, noise, coef8, B, C, H, W, Hw, sw, cfg, guidance, pred_type, rule, clip, clip_range, seed,
-                           sample_offset, step, stream);
+  return op_sched_windowed(false, false, nullptr, latents, model_out_nchw, noise, coef8, B, C, H, W, Hw, sw, cfg, guidance, pred_type, rule, clip,
+                           clip_range, seed, sample_offset, step, stream);
 }
 int tango_op_sched_ring(float* latents, const float* model_out_nchw, const float* noise, const float* coef8, int B, int C, int H, int W,
                         int Hw, int sw, int cfg, float guidance, int pred_type, int rule, int clip, float clip_range, uint64_t seed,
                         int sample_offset, int step, void* stream) {
-  return op_sched_windowed(true, latents, model_out_nchw, noise, coef8, B, C, H, W, Hw, sw, cfg, guidance, pred_type, rule, clip, clip_range, seed,
-                           sample_offset, step, stream);
+  return op_sched_windowed(true, false, nullptr, latents, model_out_nchw, noise, coef8, B, C, H, W, Hw, sw, cfg, guidance, pred_type, rule, clip,
+                           clip_range, seed, sample_offset, step, stream);
+}
+int tango_op_sched_windows_weighted(float* latents, const float* model_out_nchw, const float* noise, const float* coef8,
+                                    const float* view_weights, int B, int C, int H, int W, int Hw, int sw, int cfg, float guidance, int pred_type,
+                                    int rule, int clip, float clip_range, uint64_t seed, int sample_offset, int step, void* stream) {
+  return op_sched_windowed(false, true, view_weights, latents, model_out_nchw, noise, coef8, B, C, H, W, Hw, sw, cfg, guidance, pred_type, rule,
+                           clip, clip_range, seed, sample_offset, step, stream);
+}
+int tango_op_sched_ring_weighted(float* latents, const float* model_out_nchw, const float* noise, const float* coef8,
+                                 const float* view_weights, int B, int C, int H, int W, int Hw, int sw, int cfg, float guidance, int pred_type,
+                                 int rule, int clip, float clip_range, uint64_t seed, int sample_offset, int step, void* stream) {
+  return op_sched_windowed(true, true, view_weights, latents, model_out_nchw, noise, coef8, B, C, H, W, Hw, sw, cfg, guidance, pred_type, rule,
+                           clip, clip_range, seed, sample_offset, step, stream);
 }
 
 int tango_op_mel_ring_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream) {

@@ -243,8 +243,14 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __re
 // per-view arithmetic over the views (v0 + j) mod V at local rows y0 - j s, the view that starts farthest below h first -- for a row
 // that no view wraps over, the ascending order above.  The order is relative to h, so the update commutes with a rotation of the ring
 // by a multiple of s: no row is special, the wrap point included.  The linear form walks its views as (v_lo + j, h - v_lo s - j s).
+// WEIGHTED (timed prompts, tango_engine_denoise_*_weighted): weighted MultiDiffusion / "Mixture of Diffusers" (Jimenez 2023).  The block's
+// `weights` is a device table of Hw positive floats, one per local window row, shared by all views; over the same views in the same order
+//   acc = 0; wsum = 0;   t = w[y_v] * d_v; acc = acc + t; wsum = wsum + w[y_v];   r = acc / wsum   (IEEE division);   + sig * nz as above
+// so a view fades in and out over its overlaps instead of counting in full up to its last row.  wsum does not depend on the channel and is
+// summed once per thread.  All weights 1: t = d and wsum = n are exact, the unweighted kernel's bits.  One view with w != 1: (w d) / w may
+// differ from d in the last bit; there is no special case.
 // ------------------------------------------------------------------------------------------
-template <typename T, bool RING>
+template <typename T, bool RING, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowParams* __restrict__ pp) {
 #pragma clang fp contract(off)
   const SchedParams p = pp->p;
@@ -262,7 +268,13 @@ __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowPara
     window_cover(g, h, &v0, &v_hi);
     n = v_hi - v0 + 1; y0 = h - v0 * g.s;
   }
-  const float cnt = (float)n;
+  float cnt = (float)n;
+  const float* wt = nullptr;
+  if constexpr (WEIGHTED) {
+    wt = pp->weights;
+    cnt = 0.0f;
+    for (int j = 0, y = y0; j < n; ++j, y -= g.s) cnt = cnt + wt[y];
+  }
   const int step = *p.step_ptr;
   const float* cf = p.coef + step * 8;
   const float sa = cf[0], sb = cf[1], c0 = cf[2], c1 = cf[3], sig = cf[4], sap = cf[5], dirc = cf[6];
@@ -294,6 +306,7 @@ __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowPara
         else { const float m0 = sa * o; const float m1 = sb * x; e = m0 + m1; }
         const float m0 = sap * x0; const float m1 = dirc * e; d = m0 + m1;
       }
+      if constexpr (WEIGHTED) d = wt[y] * d;
       acc = acc + d;
     }
     float r = acc / cnt;
@@ -452,17 +465,23 @@ __global__ __launch_bounds__(256) void mel_ring_pad_kernel(const float* __restri
   dst[idx] = mel[((int64_t)b * T + t) * F + f];
 }
 
-template <bool RING>
+template <bool RING, bool WEIGHTED = false>
 static int launch_sched_windowed(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
   const dim3 grid((unsigned)((max_positions + 255) / 256));
   switch (dtype) {
-    case DT_F32: hipLaunchKernelGGL((sched_window_kernel<float, RING>), grid, dim3(256), 0, s, dev_params); break;
-    case DT_F16: hipLaunchKernelGGL((sched_window_kernel<f16, RING>), grid, dim3(256), 0, s, dev_params); break;
-    case DT_BF16: hipLaunchKernelGGL((sched_window_kernel<bf16, RING>), grid, dim3(256), 0, s, dev_params); break;
+    case DT_F32: hipLaunchKernelGGL((sched_window_kernel<float, RING, WEIGHTED>), grid, dim3(256), 0, s, dev_params); break;
+    case DT_F16: hipLaunchKernelGGL((sched_window_kernel<f16, RING, WEIGHTED>), grid, dim3(256), 0, s, dev_params); break;
+    case DT_BF16: hipLaunchKernelGGL((sched_window_kernel<bf16, RING, WEIGHTED>), grid, dim3(256), 0, s, dev_params); break;
     default: TANGO_FAIL(RING ? "sched_ring: bad dtype" : "sched_windows: bad dtype");
   }
   TANGO_HIP(hipGetLastError());
   return 0;
+}
+int launch_sched_windows_weighted(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
+  return launch_sched_windowed<false, true>(dtype, dev_params, max_positions, s);
+}
+int launch_sched_ring_weighted(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
+  return launch_sched_windowed<true, true>(dtype, dev_params, max_positions, s);
 }
 int launch_sched_windows(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
   return launch_sched_windowed<false>(dtype, dev_params, max_positions, s);
@@ -889,6 +908,15 @@ const char* ring_args_refusal(const SchedArgs& a, int canvas_h, int window_h, in
   if (canvas_h <= 0) return "a ring call states its canvas height (latent_h > 0)";
   if (const char* why = ring_geom_refusal(canvas_h, window_h, stride, g)) return why;
   if (window_h % 8 != 0) return "window_h is not a UNet height";
+  return nullptr;
+}
+
+// Why a weighted update refuses its table (HOST [window_h]); asked after the unweighted call's own refusals.  The engine takes any
+// positive table; the taper of timed prompts is tango_amd/inpaint.py window_taper.
+const char* view_weights_refusal(const float* weights, int window_h) {
+  if (!weights) return "view_weights must not be NULL (the unweighted call takes no table)";
+  for (int y = 0; y < window_h; ++y)
+    if (!(weights[y] > 0.0f) || std::isinf(weights[y])) return "view_weights entries must be finite and > 0";
   return nullptr;
 }
 

@@ -422,14 +422,17 @@ class Engine:
     def denoise_windows(self, latents, prompt_embeds, prompt_mask, timesteps, coef, guidance_scale, *, window_h, stride,
                         prediction_type="v_prediction", rule="ddpm", clip_sample=False, clip_sample_range=1.0, noise=None, seed=0,
                         sample_offset=0, use_graph=True, prompt_mask_host=None, known_latents=None, guidance_table=None,
-                        guidance_rescale=0.0, _ring=False):
+                        guidance_rescale=0.0, view_weights=None, _ring=False):
         """In-place denoise of a long clip's canvas `latents` [B, 8, H, 16] (fp32 cuda) as V = (H - window_h) / stride + 1 overlapping
         windows of `window_h` rows (a height of the duration grid) every `stride` rows: MultiDiffusion in time (include/tango_engine.h
         tango_window_args_t).  Each step runs the UNet on the (2 if guidance_scale > 1 else 1) * B * V windows as one batch and averages
         the per-view updates on the canvas.  `prompt_embeds` / `prompt_mask` hold one row per WINDOW, row half * B * V + b * V + v
         (`repeat_interleave(V, 0)` of each half of a plain call's rows); `noise` [N, B, 8, H, 16] is canvas-shaped, one draw per canvas
         element.  `rule`: "ddpm" or "ddim"; the multistep rule, `known_latents`, a guidance table and a rescale are refused.  The
-        other arguments are Engine.denoise's.  With H == window_h the result is Engine.denoise's, bit for bit."""
+        other arguments are Engine.denoise's.  With H == window_h the result is Engine.denoise's, bit for bit.
+        `view_weights`: None, or a float32 [window_h] array of positive weights, one per local window row -- the update is then the
+        weighted mean of the views (tango_engine_denoise_windows_weighted; tango_amd.inpaint.window_taper is the profile of timed
+        prompts, where the windows of a sample run under different texts).  All ones give the bits of None."""
         assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
         how, name = ("on a ring", "denoise_ring") if _ring else ("with windows", "denoise_windows")
         if rule == "dpmsolver":
@@ -479,6 +482,18 @@ class Engine:
         a.use_graph = 1 if use_graph else 0
         a.latent_h = H
         w = _lib.WindowArgs(window_h=hw, stride=stride)
+        if view_weights is not None:
+            vw = np.ascontiguousarray(np.asarray(view_weights.cpu() if torch.is_tensor(view_weights) else view_weights, dtype=np.float32))
+            if vw.shape != (hw,):
+                raise ValueError("view_weights must be [window_h = %d], got %s" % (hw, vw.shape))
+            check, run = ((self.lib.tango_debug_denoise_ring_weighted_check, self.lib.tango_engine_denoise_ring_weighted) if _ring else
+                          (self.lib.tango_debug_denoise_windows_weighted_check, self.lib.tango_engine_denoise_windows_weighted))
+            why = check(C.byref(a), C.byref(w), C.c_void_p(vw.ctypes.data))
+            if why:
+                raise ValueError(why.decode())
+            with torch.cuda.device(self.device):
+                _lib.check(run(self._h, C.byref(a), C.byref(w), C.c_void_p(vw.ctypes.data), _stream_ptr()), name + "_weighted")
+            return latents
         check, run = ((self.lib.tango_debug_denoise_ring_check, self.lib.tango_engine_denoise_ring) if _ring else
                       (self.lib.tango_debug_denoise_windows_check, self.lib.tango_engine_denoise_windows))
         why = check(C.byref(a), C.byref(w))

@@ -137,6 +137,62 @@ def loop_geometry(duration, window=None, hop=None):
     return h, hw, s, v
 
 
+def window_taper(window_h, stride):
+    """The weight of a window's local row y in the weighted update of timed prompts (include/tango_engine.h
+    tango_engine_denoise_windows_weighted): np.float32 [window_h], with E = window_h - stride
+        w[y] = min(1, (y + 0.5) / E) * min(1, (window_h - y - 0.5) / E)        (all ones when E == 0)
+    computed in fp32 in mel_ring_blend_kernel's order of operations: a view fades in over its overlap with its predecessor and out
+    over the one with its successor.  Every weight is strictly positive."""
+    hw, s = int(window_h), int(stride)
+    if hw != window_h or s != stride or hw < 1 or not 1 <= s <= hw:
+        raise ValueError("window_taper takes integers 1 <= stride <= window_h, got window_h %r and stride %r" % (window_h, stride))
+    e = hw - s
+    if e == 0:
+        return np.ones(hw, dtype=np.float32)
+    y = np.arange(hw, dtype=np.float32)
+    one, ef = np.float32(1.0), np.float32(e)
+    up = np.minimum(one, (y + np.float32(0.5)) / ef)
+    down = np.minimum(one, ((np.float32(hw) - y) - np.float32(0.5)) / ef)
+    return (up * down).astype(np.float32)
+
+
+def timeline_geometry(segments, duration, window=10.0, hop=5.0, loop=False):
+    """Timed prompts: `segments` = [(prompt, start_seconds), ...] with ascending starts, the first at 0, on a clip of `duration` seconds
+    cut into windows as long_geometry (loop False) or loop_geometry (loop True) cuts it.  Segment i starts at canvas row
+    int(round(start_i * 25.6)) and ends where the next one starts (the last at H); window v runs under the prompt of the segment that
+    holds its centre row v * s + Hw // 2 (mod H on a ring).  -> (H, Hw, s, V, window_prompt) with window_prompt the list of V segment
+    indices.  Unsorted starts, a first start other than 0, a start at or beyond the duration and a segment that holds no window
+    centre are ValueErrors that name the numbers."""
+    H, hw, s, V = loop_geometry(duration, window, hop) if loop else long_geometry(duration, window, hop)
+    try:
+        starts = [float(st) for _, st in segments]
+    except (TypeError, ValueError):
+        raise ValueError("segments must be a list of (prompt, start_seconds) pairs, got %r" % (segments,))
+    if not starts:
+        raise ValueError("segments must hold at least one (prompt, start_seconds) pair")
+    if starts[0] != 0.0:
+        raise ValueError("the first segment must start at 0 s, got %r s" % (segments[0][1],))
+    for i in range(1, len(starts)):
+        if not starts[i] > starts[i - 1]:                            # (NaN compares false)
+            raise ValueError("segment starts must ascend: segment %d starts at %r s, segment %d at %r s"
+                             % (i - 1, segments[i - 1][1], i, segments[i][1]))
+    for i, st in enumerate(starts):
+        if not st < float(duration):
+            raise ValueError("segment %d starts at %r s, at or beyond the duration of %r s" % (i, segments[i][1], duration))
+    rows = [int(round(st * LATENT_ROWS_PER_SECOND)) for st in starts]
+    centres = [(v * s + hw // 2) % H if loop else v * s + hw // 2 for v in range(V)]
+    window_prompt = [max(i for i, r in enumerate(rows) if r <= c) for c in centres]
+    for i, r in enumerate(rows):
+        if i not in window_prompt:
+            end = rows[i + 1] if i + 1 < len(rows) else H
+            near = min(centres, key=lambda c: (abs(c - r), c))
+            raise ValueError("segment %d (rows %d to %d, %g s to %g s) holds no window centre: the %d centres are every %g s from %g s; "
+                             "the nearest is at %g s (row %d) -- start the segment there, or move its neighbour past it"
+                             % (i, r, end, r / LATENT_ROWS_PER_SECOND, end / LATENT_ROWS_PER_SECOND, V, s / LATENT_ROWS_PER_SECOND,
+                                min(centres) / LATENT_ROWS_PER_SECOND, near / LATENT_ROWS_PER_SECOND, near))
+    return H, hw, s, V, window_prompt
+
+
 def clip_duration(n_samples):
     """the smallest grid duration whose mel frames hold a 16 kHz clip of `n_samples` samples; 20 s for anything longer (the clip is
     then cut).  Unlike the reference's round_up_duration (pipeline.py:49-50), which always adds one more 2.5 s block -- a 5 s clip

@@ -14,7 +14,7 @@ from typing import List, Optional
 import torch
 
 from .engine import Engine, normalize_unet_config
-from .inpaint import check_latent_h, duration_geometry, long_geometry, loop_geometry
+from .inpaint import check_latent_h, duration_geometry, long_geometry, loop_geometry, timeline_geometry, window_taper
 from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler  # noqa: F401  (re-exported like `from models import DDPMScheduler`)
 from .scheduler import DDIMInverseScheduler, cfg_enabled, check_guidance_rescale, from_diffusers, guidance_table
 
@@ -358,9 +358,12 @@ class AudioDiffusion:
                                               sample_offset, mask_host)
 
     def _windowed_from_embeddings(self, ring, geometry, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale,
-                                  duration, latents, noise, seed, sample_offset, mask_host):
+                                  duration, latents, noise, seed, sample_offset, mask_host, window_prompt=None, num_samples=1,
+                                  view_weights=None):
         """inference_long_from_embeddings (ring False: Engine.denoise_windows) and inference_loop_from_embeddings (ring True:
-        Engine.denoise_ring) once the geometry is known"""
+        Engine.denoise_ring) once the geometry is known.  `window_prompt` (inference_timeline_from_embeddings): the embedding rows
+        are per SEGMENT, window v of each of the `num_samples` samples takes row window_prompt[v] of its half; `view_weights` goes to
+        the engine."""
         H, hw, stride, V = geometry
         how = "on a ring" if ring else "with windows"
         if not isinstance(guidance_scale, (int, float)):
@@ -373,6 +376,13 @@ class AudioDiffusion:
                              "behaviour): use DDPM or DDIM")
         cfg_on = guidance_scale > 1.0
         B = prompt_embeds.shape[0] // 2 if cfg_on else prompt_embeds.shape[0]
+        if window_prompt is not None:
+            S, B = B, int(num_samples)                # B counted the segments
+            window_prompt = [int(i) for i in window_prompt]
+            if len(window_prompt) != V or not all(0 <= i < S for i in window_prompt):
+                raise ValueError("window_prompt must hold %d segment indices below %d (one per window), got %r" % (V, S, window_prompt))
+            if B < 1:
+                raise ValueError("num_samples must be positive, got %r" % (num_samples,))
         inference_scheduler.set_timesteps(num_steps, device=self.device)
         if latents is None:
             latents = self.prepare_latents(B, inference_scheduler, self.unet.config.in_channels, torch.float32, self.device, long_h=H)
@@ -382,9 +392,15 @@ class AudioDiffusion:
         if boolean_prompt_mask is None:
             boolean_prompt_mask = torch.ones(prompt_embeds.shape[:2], dtype=torch.bool, device=prompt_embeds.device)
         pe, pm, mask_host = self._pad_text(prompt_embeds.to(self.device), boolean_prompt_mask, mask_host)
-        # one row per window, row half * B * V + b * V + v: each half's rows repeated V times in place
-        pe, pm = pe.repeat_interleave(V, 0), pm.repeat_interleave(V, 0)
-        mask_host = mask_host.repeat_interleave(V, 0) if mask_host is not None else None
+        if window_prompt is None:
+            # one row per window, row half * B * V + b * V + v: each half's rows repeated V times in place
+            pe, pm = pe.repeat_interleave(V, 0), pm.repeat_interleave(V, 0)
+            mask_host = mask_host.repeat_interleave(V, 0) if mask_host is not None else None
+        else:
+            # the same row order, gathered from the per-segment rows: row half * S + window_prompt[v] for every sample
+            idx = torch.tensor([half * S + i for half in range(2 if cfg_on else 1) for _ in range(B) for i in window_prompt])
+            pe, pm = pe.index_select(0, idx.to(pe.device)), pm.index_select(0, idx.to(pm.device))
+            mask_host = mask_host.index_select(0, idx) if mask_host is not None else None
         c = inference_scheduler.config
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.seed is None else (int(self.seed) << 20) + self._calls
@@ -393,7 +409,7 @@ class AudioDiffusion:
         run(latents, pe, pm, inference_scheduler.timesteps.cpu().numpy(), inference_scheduler.coef_table(), guidance_scale, window_h=hw,
             stride=stride, prediction_type=c.prediction_type, rule=inference_scheduler.rule, clip_sample=c.clip_sample,
             clip_sample_range=getattr(c, "clip_sample_range", 1.0), noise=noise, seed=seed, sample_offset=sample_offset,
-            use_graph=self.use_graph, prompt_mask_host=mask_host)
+            use_graph=self.use_graph, prompt_mask_host=mask_host, view_weights=view_weights)
         return latents
 
     @torch.no_grad()
@@ -438,6 +454,39 @@ class AudioDiffusion:
             pm = pm.repeat_interleave(num_samples_per_prompt, 0)
         return self.inference_loop_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, duration, window, hop,
                                                    seed=seed, sample_offset=sample_offset, mask_host=host)
+
+    # ---- timed prompts: a prompt per window and tapered view weights (include/tango_engine.h tango_engine_denoise_windows_weighted) ----
+    @torch.no_grad()
+    def inference_timeline_from_embeddings(self, prompt_embeds, boolean_prompt_mask, window_prompt, inference_scheduler, num_steps=20,
+                                           guidance_scale=3, duration=30, window=10, hop=5, loop=False, taper=True, num_samples=1,
+                                           latents=None, noise=None, seed=None, sample_offset=0, mask_host=None):
+        """inference_long_from_embeddings (`loop` False) or inference_loop_from_embeddings (`loop` True) with a prompt per window: the
+        region-based half of MultiDiffusion (Bar-Tal et al. 2023, section 4.2) in time.  `prompt_embeds` / `boolean_prompt_mask` hold
+        one row per SEGMENT ([uncond; cond] with guidance: 2 S rows), `window_prompt` the segment index of each of the V windows
+        (tango_amd.inpaint.timeline_geometry); each of the `num_samples` samples runs the same timeline.  `taper` True: the per-view
+        updates are averaged with tango_amd.inpaint.window_taper's weights, so a view fades out towards its edges and the prompts
+        cross-fade over the overlaps; False: the equal weights of the long clip and the loop.  The refusals are theirs."""
+        geometry = loop_geometry(duration, window, hop) if loop else long_geometry(duration, window, hop)
+        weights = window_taper(geometry[1], geometry[2]) if taper else None
+        return self._windowed_from_embeddings(bool(loop), geometry, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps,
+                                              guidance_scale, duration, latents, noise, seed, sample_offset, mask_host,
+                                              window_prompt=window_prompt, num_samples=num_samples, view_weights=weights)
+
+    @torch.no_grad()
+    def inference_timeline(self, segments, inference_scheduler, num_steps=20, guidance_scale=3, num_samples=1, duration=30, window=10,
+                           hop=5, loop=False, taper=True, negative_prompt=None, seed=None, sample_offset=0):
+        """inference() for a timeline of prompts: `segments` = [(prompt, start_seconds), ...] (tango_amd.inpaint.timeline_geometry).
+        `negative_prompt`: None, one str, or one str per segment.  Latents [num_samples, 8, duration * 25.6, 16]."""
+        window_prompt = timeline_geometry(segments, duration, window, hop, loop)[4]
+        prompts = [p for p, _ in segments]
+        host = None
+        if cfg_enabled(guidance_scale):
+            pe, pm, host = self._encode_text_classifier_free(prompts, 1, negative_prompt)
+        else:
+            pe, pm = self.encode_text(prompts)
+        return self.inference_timeline_from_embeddings(pe.float(), pm, window_prompt, inference_scheduler, num_steps, guidance_scale,
+                                                       duration, window, hop, loop, taper, num_samples, seed=seed,
+                                                       sample_offset=sample_offset, mask_host=host)
 
     # ---- masked-latent inpainting (audioldm/pipeline.py:249-301, ldm.py:724-818, ddim.py:207-233) ------------------------------
     @torch.no_grad()

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from .autoencoder import AutoencoderKL
-from .inpaint import clip_duration, duration_geometry, latent_mask, long_geometry, loop_geometry, prepare_waveform
+from .inpaint import clip_duration, duration_geometry, latent_mask, long_geometry, loop_geometry, prepare_waveform, timeline_geometry
 from .models import AudioDiffusion
 from .scheduler import SD21_SCHEDULER_CONFIG, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 from .scheduler import cfg_enabled, check_guidance_rescale, guidance_is_table
@@ -159,6 +159,42 @@ class Tango:
                                                     negative_prompt=negative_prompt, seed=seed, sample_offset=k)
                 mel = self.vae.engine.vae_decode_ring(latents, hw, stride)
                 waves.append(self.vae.engine.vocode_ring(mel).cpu().numpy())
+        return np.concatenate(waves)
+
+    def generate_timeline(self, segments, duration, steps=100, guidance=3, samples=1, window=10, hop=5, loop=False, taper=True,
+                          negative_prompt=None, seed=None):
+        """ Generate `duration` seconds of audio that follows a timeline of prompts, e.g. [("rain", 0), ("thunder rolls in", 12.5),
+        ("birds after the storm", 22)]: `segments` is a list of (prompt, start_seconds) with ascending starts, the first at 0.  The
+        clip is cut into windows as generate_long cuts it (`loop` False: tiled decode, then the vocoder) or as generate_loop does
+        (`loop` True: ring decode, then the ring vocoder); every window runs under the prompt of the segment that holds its centre
+        (tango_amd.inpaint.timeline_geometry refuses a segment that holds none), and with `taper` the per-view updates are averaged
+        with weights that fall off towards a window's edges (tango_amd.inpaint.window_taper), so that neighbouring prompts cross-fade
+        over the overlap instead of meeting in a step.  `negative_prompt`: None, one string, or one per segment.  One segment with
+        taper=False is generate_long / generate_loop, bit for bit.  The scheduler rules, `seed` and the chunking of samples are theirs.
+        Returns np.int16 [samples, n]: generate_long's or generate_loop's length. """
+        H, hw, stride, V, _ = timeline_geometry(segments, duration, window, hop, loop)
+        how = "on a ring" if loop else "with windows"
+        if not isinstance(guidance, (int, float)):
+            raise ValueError("a guidance table is not supported %s: guidance must be a scalar" % how)
+        if getattr(self.scheduler, "rule", None) == "dpmsolver":
+            raise ValueError("the multistep DPM-Solver rule is not supported on a ring: use DDPM or DDIM" if loop else
+                             "the multistep DPM-Solver rule is not supported with windows (a per-view history has no reference "
+                             "behaviour): use DDPM or DDIM")
+        per_call = max(1, self.LONG_MAX_ROWS // ((2 if cfg_enabled(guidance) else 1) * V))
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        waves = []
+        with torch.no_grad():
+            for k in range(0, samples, per_call):
+                n = min(per_call, samples - k)
+                latents = self.model.inference_timeline(segments, self.scheduler, steps, guidance, n, duration, window, hop, loop, taper,
+                                                        negative_prompt=negative_prompt, seed=seed, sample_offset=k)
+                if loop:
+                    mel = self.vae.engine.vae_decode_ring(latents, hw, stride)
+                    waves.append(self.vae.engine.vocode_ring(mel).cpu().numpy())
+                else:
+                    mel = self.vae.engine.vae_decode_tiled(latents, hw, stride)
+                    waves.append(self.vae.decode_to_waveform(mel))
         return np.concatenate(waves)
 
     def generate_for_batch(self, prompts, steps=100, guidance=3, samples=1, batch_size=8, disable_progress=True, duration=10,
