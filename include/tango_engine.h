@@ -261,8 +261,8 @@ int tango_engine_vae_decode_tiled_h(tango_engine_t* h, const float* latents, flo
 /* Seamless loops: the same windows on a RING in time.  The canvas args->latents [B, C_lat, H, latent_w] (H = args->latent_h > 0) is a ring
  * of H rows; V = H / s views, view v covers canvas rows (v s + y) mod H for y in [0, Hw).  1 <= s <= Hw <= H (a window never meets itself),
  * H % s == 0, V <= 32, Hw a UNet height.  H == Hw is a good call: V = Hw / s rotated views of the whole ring; H == Hw == s is one view
- * that does not wrap and computes tango_engine_denoise's bits.  The UNet batch, the row order of prompt_embeds / prompt_mask and the plan
- * are tango_engine_denoise_windows'.  Per step and canvas element of row h, with r = h % s: the n = ceil((Hw - r) / s) covering views are
+ * that does not wrap and computes tango_engine_denoise's bits.  The UNet batch, the row order of prompt_embeds / prompt_mask, the plan
+ * and the captured steps a call replays are tango_engine_denoise_windows' of that shape.  Per step and canvas element of row h, with r = h % s: the n = ceil((Hw - r) / s) covering views are
  * v_k = (h / s - k) mod V, k = 0 .. n - 1, the element at local row y_k = r + k s of view v_k; they are accumulated in DESCENDING k (the view
  * that starts farthest below h first: for a row no view wraps over, the linear call's ascending order), acc = 0 + d_.. + d_..; acc / n;
  * + sigma * one draw per canvas element, exactly as above.  The order is relative to h, so the update commutes with a rotation of the ring

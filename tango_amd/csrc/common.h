@@ -484,22 +484,40 @@ struct SchedParams {
 static_assert(std::is_trivially_copyable<SchedParams>::value && sizeof(SchedParams) == 200,
               "SchedParams is memcpy'd to the device and copied by value in the kernels: its layout is fixed");
 
-// ---- long clips: MultiDiffusion windows in time (sched.hip; include/tango_engine.h tango_window_args_t) ----
-// The canvas is lat [B, C, H, W]; view v of V = (H - Hw) / s + 1 covers canvas rows [v s, v s + Hw); the UNet batch row of window v of
-// sample b is half * B * V + b * V + v (unconditional half first).  One definition of the geometry for every layer:
-struct WindowGeom { int H = 0, Hw = 0, s = 0, V = 0; };
+// ---- long clips and loops: MultiDiffusion windows in time (sched.hip; include/tango_engine.h tango_window_args_t) ----
+// The canvas is lat [B, C, H, W] and a clip has V views of Hw rows, s rows apart; the UNet batch row of window v of sample b is
+// half * B * V + b * V + v (unconditional half first).  `ring` is the one fact that tells the two modes apart, for every layer:
+//   linear (ring = 0): V = (H - Hw) / s + 1, view v covers canvas rows [v s, v s + Hw)
+//   ring   (ring = 1): the canvas rows are a ring of H rows, V = H / s, view v covers rows (v s + y) mod H for y in [0, Hw), with
+//                      1 <= s <= Hw <= H (a window never meets itself) and H % s == 0.  The window batch's row order is the linear one.
+struct WindowGeom { int H = 0, Hw = 0, s = 0, V = 0, ring = 0; };
 constexpr int kMaxWindows = 32;
-// why (canvas_h, window_h, stride) is no exact cover of at most kMaxWindows views (nullptr: it is; *g is then filled in).  Host only.
-const char* window_geom_refusal(int canvas_h, int window_h, int stride, WindowGeom* g);
-// the views that cover canvas row h, ascending: [lo, hi]
-__host__ __device__ inline void window_cover(const WindowGeom& g, int h, int* lo, int* hi) {
-  *lo = h >= g.Hw ? (h - g.Hw) / g.s + 1 : 0;
-  const int top = h / g.s;
-  *hi = top < g.V - 1 ? top : g.V - 1;
+// why (canvas_h, window_h, stride) is no exact cover of the canvas (of the ring) by at most kMaxWindows views (nullptr: it is; *g is then
+// filled in, g->ring included).  One message per condition, in each mode's own wording and order.  Host only.
+const char* window_geom_refusal(int canvas_h, int window_h, int stride, bool ring, WindowGeom* g);
+// The n views that cover canvas row h, in accumulation order: the j-th is view (*v0 + j) mod V at its local row *y0 - j s.
+//   linear: the views [lo, hi] ascending, lo = max(0, (h - Hw) / s + 1), hi = min(h / s, V - 1): v0 = lo, y0 = h - lo s, n = hi - lo + 1
+//   ring:   n = ceil((Hw - h % s) / s), the view that starts farthest below h first (k = n - 1 - j of v_k = (h / s - k) mod V,
+//           y_k = h % s + k s).  The order is relative to h, so the update commutes with a rotation of the ring by a multiple of s;
+//           for a row no covering view wraps over it is the linear order.
+__host__ __device__ inline int window_cover(const WindowGeom& g, int h, int* v0, int* y0) {
+  if (g.ring) {
+    const int q = h / g.s, r = h - q * g.s;
+    const int n = (g.Hw - r + g.s - 1) / g.s;          // n <= ceil(Hw / s) <= V
+    const int v = q - (n - 1);
+    *v0 = v < 0 ? v + g.V : v;
+    *y0 = r + (n - 1) * g.s;
+    return n;
+  }
+  const int lo = h >= g.Hw ? (h - g.Hw) / g.s + 1 : 0;
+  const int top = h / g.s, hi = top < g.V - 1 ? top : g.V - 1;
+  *v0 = lo;
+  *y0 = h - lo * g.s;
+  return hi - lo + 1;
 }
 // The parameter block of a windowed call: the SchedParams of the canvas (B, HW = H * W, lat, noise: the canvas's; eps, xin: the window
 // batch's, B2 * V rows of Hw * W positions) beside the geometry.  A block of its own in device memory: SchedParams keeps its layout, and
-// a captured windowed step reads this block while a captured plain step reads the engine's SchedParams block.
+// a captured windowed step reads this block -- g.ring with everything else -- while a captured plain step reads the engine's SchedParams block.
 struct SchedWindowParams {
   SchedParams p;
   WindowGeom g;
@@ -508,44 +526,19 @@ struct SchedWindowParams {
   const float* weights = nullptr;    // weighted kernels only: DEVICE [g.Hw] positive weights, one per local window row, shared by all views
 };
 static_assert(std::is_trivially_copyable<SchedWindowParams>::value, "SchedWindowParams is memcpy'd to the device");
-// sched_window_kernel (rules 0 / 1): one thread per canvas position; the grid covers max_positions >= B * H * W
-int launch_sched_windows(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s);
+// sched_window_kernel (rules 0 / 1): one thread per canvas position; the grid covers max_positions >= B * H * W.  `weighted` (timed
+// prompts) picks the kernels that read the block's `weights`: r = (sum w[y_v] d_v) / (sum w[y_v]) over the same views in the same order;
+// the unweighted kernels never read it.
+int launch_sched_window(int dtype, const SchedWindowParams* dev_params, int max_positions, bool weighted, hipStream_t s);
+// why a weighted update refuses its HOST table of window_h floats (nullptr: it does not): NULL, a non-finite entry, an entry <= 0
+const char* view_weights_refusal(const float* weights, int window_h);
 // canvas fp32 NCHW [B, C, H, W] -> T NHWC [rep * B * V, Hw * W, ld]: the windowed form of launch_nchw_to_nhwc (before step 0)
 int launch_window_gather(int dtype, const float* lat, void* xin, int64_t ld, int B, int C, int W, const WindowGeom& g, int rep, hipStream_t s);
 // canvas fp32 NCHW [B, C, H, W] -> fp32 NCHW [B * V, C, Hw, W] (the tiled VAE decode's input)
 int launch_window_gather_nchw(const float* lat, float* dst, int B, int C, int W, const WindowGeom& g, hipStream_t s);
-// tiles fp32 [B * V, g.Hw, F] (tile t at output rows t * g.s ...) -> out fp32 [B, g.H, F], cross-faded over the overlaps (g in mel rows)
+// tiles fp32 [B * V, g.Hw, F] (tile t at output rows t g.s + y, mod g.H on a ring) -> out fp32 [B, g.H, F], cross-faded over the overlaps;
+// on a ring every tile fades in and out (g in mel rows)
 int launch_mel_tile_blend(const float* tiles, float* out, int B, int F, const WindowGeom& g, hipStream_t s);
-
-// ---- loops: the same windows on a ring in time (sched.hip; tango_engine_denoise_ring) ----
-// The canvas rows are a ring of H rows: V = H / s views, view v covers canvas rows (v s + y) mod H for y in [0, Hw), with
-// 1 <= s <= Hw <= H (a window never meets itself), H % s == 0 and V <= kMaxWindows.  The window batch's row order is the linear one.
-// why (canvas_h, window_h, stride) is no such ring (nullptr: it is; *g is then filled in).  Host only.
-const char* ring_geom_refusal(int canvas_h, int window_h, int stride, WindowGeom* g);
-// The n = ceil((Hw - h % s) / s) views that cover ring row h, in accumulation order: the view that starts farthest below h first.  The j-th
-// is view (*v0 + j) mod V at its local row *y0 - j s (k = n - 1 - j of v_k = (h / s - k) mod V, y_k = h % s + k s).  The order is relative
-// to h, so the update commutes with a rotation of the ring by a multiple of s; for a row no covering view wraps over it is window_cover's.
-__host__ __device__ inline int ring_cover(const WindowGeom& g, int h, int* v0, int* y0) {
-  const int q = h / g.s, r = h - q * g.s;
-  const int n = (g.Hw - r + g.s - 1) / g.s;          // n <= ceil(Hw / s) <= V
-  const int v = q - (n - 1);
-  *v0 = v < 0 ? v + g.V : v;
-  *y0 = r + (n - 1) * g.s;
-  return n;
-}
-// sched_window_kernel's ring form (rules 0 / 1) on a SchedWindowParams block whose g is a ring; the grid covers max_positions >= B * H * W
-int launch_sched_ring(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s);
-// timed prompts: the WEIGHTED forms of both (the block's `weights` is set): r = (sum w[y_v] d_v) / (sum w[y_v]) over the same views in the
-// same order.  The unweighted launchers above never read `weights`.
-int launch_sched_windows_weighted(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s);
-int launch_sched_ring_weighted(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s);
-// why a weighted update refuses its HOST table of window_h floats (nullptr: it does not): NULL, a non-finite entry, an entry <= 0
-const char* view_weights_refusal(const float* weights, int window_h);
-// the two gathers with source row (v s + y) mod H
-int launch_ring_gather(int dtype, const float* lat, void* xin, int64_t ld, int B, int C, int W, const WindowGeom& g, int rep, hipStream_t s);
-int launch_ring_gather_nchw(const float* lat, float* dst, int B, int C, int W, const WindowGeom& g, hipStream_t s);
-// tiles fp32 [B * V, g.Hw, F] (tile t at ring rows (t g.s + y) mod g.H) -> out fp32 [B, g.H, F]: every tile fades in and out (g in mel rows)
-int launch_mel_ring_blend(const float* tiles, float* out, int B, int F, const WindowGeom& g, hipStream_t s);
 // mel fp32 [B, T, F] on a ring -> dst fp32 [B, T + 2 ctx, F], dst frame j = mel frame (j - ctx) mod T
 int launch_mel_ring_pad(const float* mel, float* dst, int B, int T, int F, int ctx, hipStream_t s);
 
@@ -560,12 +553,10 @@ struct SchedArgs {
 };
 // the refusal without a prefix (the caller says "denoise: " or its own name), or nullptr.  Host only, no device needed.
 const char* sched_args_refusal(const SchedArgs& a);
-// the same for a windowed update (tango_engine_denoise_windows, tango_op_sched_windows): sched_args_refusal, then the multistep rule,
-// known latents, a guidance table or rescale, and a geometry that is no exact cover (*g is filled in when the answer is nullptr)
-const char* window_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, WindowGeom* g);
-// the same for an update on a ring (tango_engine_denoise_ring, tango_op_sched_ring): the multistep rule, sched_args_refusal, known latents,
-// a guidance table or rescale, a missing canvas height, then ring_geom_refusal and a window_h that is no multiple of 8
-const char* ring_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, WindowGeom* g);
+// the same for a windowed update, linear or on a ring (tango_engine_denoise_windows / _ring, tango_op_sched_windows / _ring): the multistep
+// rule, sched_args_refusal, known latents, a guidance table or rescale, a missing canvas height, then window_geom_refusal and a window_h
+// that is no multiple of 8, each in the mode's own wording (*g is filled in when the answer is nullptr)
+const char* window_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, bool ring, WindowGeom* g);
 // `dev_params` is a DEVICE copy of SchedParams; the grid covers max_positions >= B*HW (one thread per latent position).
 // `rule` (host copy of the block's rule) picks the kernel: 0 / 1 sched_step_kernel, 2 sched_multistep_kernel; `masked` their
 // inpainting variants (the blend for the next loop index fused after the update); `guided` the variants that read the guidance

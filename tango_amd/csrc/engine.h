@@ -169,14 +169,11 @@ struct UNetPlan : Plan {
   // cannot replay a loop that needs another; everything else is shared.  [guided]: the table / rescale variants, with the two
   // statistics launches in front of the update (a default call replays the [.][.][0] graphs: today's kernel sequence)
   StepGraphs graphs[2][2][2];
-  // a windowed call (Engine::denoise_windows) runs this plan's step program with sched_window_kernel as its update: graphs of its own,
-  // so that a plain call and a windowed call of one shape share the plan and each replays the graph that holds its own update kernel
-  StepGraphs wgraphs;
-  // ... and a call on a ring (Engine::denoise_ring) the ring form of that kernel: plain, windowed and ring calls of one shape share the plan
-  StepGraphs rgraphs;
-  // ... and the weighted forms of both (timed prompts, Engine::denoise_windows / denoise_ring with a table of view weights): a weighted and
-  // an unweighted call of one shape share the plan and each replays its own graphs
-  StepGraphs wwgraphs, rwgraphs;
+  // a windowed call (Engine::denoise_windowed) runs this plan's step program with sched_window_kernel as its update: graphs of its own,
+  // so that a plain call and a windowed call of one shape share the plan and each replays the graph that holds its own update kernel.
+  // [weighted]: the kernel that weights its views by the block's table (timed prompts).  A linear and a ring call of one shape replay the
+  // same graphs: the kernel reads g.ring from the call's block as it reads everything else, and the grid is the plan's in both modes.
+  StepGraphs wgraphs[2];
   // Two independent chains (round 5; Engine::denoise): a "dual" plan owns only the UNet input / output buffers of the whole batch; its
   // two children run the first and the second half of the samples (no op of the UNet crosses samples) as two branches of the captured
   // graph, so that one branch's dispatch gaps and kernel tails are filled by the other's kernels.  A child takes xin / eps from its
@@ -226,15 +223,12 @@ class Engine {
   int set_weight(const char* name, const float* dev, const int64_t* shape, int ndim);
   int finalize_weights();
   int denoise(const tango_denoise_args_t& a, const tango_guidance_args_t* g, hipStream_t s);   // g may be null: scalar guidance, no rescale
-  // long clips: a.latent_h is the canvas height, the UNet runs (cfg ? 2 : 1) * a.batch * V windows of height w.window_h per step
-  int denoise_windows(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s);
-  int vae_decode_tiled(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s);
-  // loops: the same with the canvas rows on a ring (V = a.latent_h / w.stride views that wrap), and the vocoder on a ring of mel frames
-  int denoise_ring(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s);
-  // timed prompts: both with view_weights HOST [w.window_h], a positive weight per local window row -- the update is the weighted mean
-  int denoise_windows_weighted(const tango_denoise_args_t& a, const tango_window_args_t& w, const float* view_weights, hipStream_t s);
-  int denoise_ring_weighted(const tango_denoise_args_t& a, const tango_window_args_t& w, const float* view_weights, hipStream_t s);
-  int vae_decode_ring(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s);
+  // long clips: a.latent_h is the canvas height, the UNet runs (cfg ? 2 : 1) * a.batch * V windows of height w.window_h per step.
+  // ring (loops): the canvas rows are a ring (V = a.latent_h / w.stride views that wrap).  weighted (timed prompts): view_weights is a
+  // HOST [w.window_h] table, a positive weight per local window row, and the update is the weighted mean; otherwise it is not read.
+  int denoise_windowed(const tango_denoise_args_t& a, const tango_window_args_t& w, bool ring, const float* view_weights, bool weighted, hipStream_t s);
+  // the tiled decode of such a canvas, cross-faded over the overlaps (round a ring's wrap point too); the vocoder on a ring of mel frames
+  int vae_decode_windowed(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, bool ring, hipStream_t s);
   int vocode_ring(const float* mel, int16_t* wav, int B, int frames, int* n_samples, hipStream_t s);
   int vocoder_ring_context() const;     // mel frames of context vocode_ring pads each side with: the vocoder's receptive field
   struct Cond { const float* emb = nullptr; const uint8_t* mask = nullptr; int len = 0; const uint8_t* mask_host = nullptr; };
@@ -422,10 +416,8 @@ class Engine {
   // how a guidance / plain batch of B2 UNet rows runs; profile_unet() asks with two_chains_ok = false
   UNetMode unet_mode_for(int B2, int n_short, bool cfg_on, bool two_chains_ok) const;
   // which update closes a step: the kernel is fixed when a step is captured
-  // ring: a windowed step on a ring; weighted: a windowed step that weights its views by the block's table
-  struct StepKind { int rule = 0; bool masked = false, guided = false, windowed = false, ring = false, weighted = false; };
-  int denoise_windowed(const tango_denoise_args_t& a, const tango_window_args_t& w, bool ring, const float* view_weights, bool weighted, hipStream_t s);
-  int vae_decode_windowed(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, bool ring, hipStream_t s);
+  // weighted: a windowed step that weights its views by the block's table (linear or ring is the block's to say, not the kernel's)
+  struct StepKind { int rule = 0; bool masked = false, guided = false, windowed = false, weighted = false; };
   int run_step(const UNetPlan& P, const StepKind& k, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join);
   int capture_steps(const UNetPlan& P, const StepKind& k, int n, hipGraph_t* g_out, hipGraphExec_t* x_out);
   // the loop of a denoise call once its blocks, conditions and first UNet input are in place: captures what G lacks, replays or runs eagerly

@@ -555,10 +555,7 @@ void Engine::free_plan(Plan& P) {
     for (auto& plane : U.graphs)
       for (auto& row : plane)
         for (StepGraphs& g : row) drop(g);
-    drop(U.wgraphs);
-    drop(U.rgraphs);
-    drop(U.wwgraphs);
-    drop(U.rwgraphs);
+    for (StepGraphs& g : U.wgraphs) drop(g);
     for (auto& c : U.child) if (c) { free_plan(*c); c.reset(); }
   }
   // a slab may still be read by work queued on a stream: hipFree synchronises the device before it releases memory
@@ -1496,7 +1493,7 @@ static int grow_device_buffer(T** buf, size_t* have, size_t need, size_t unit, c
 // one denoise step = UNet forward, fused CFG combine + scheduler update (writes the next UNet input), step counter++
 // (two chains: fork after the previous step's update, join before this step's); guided: the statistics of the rescale in between
 // windowed: the update is sched_window_kernel on the engine's windowed block (one thread per canvas position, never more than the window
-// batch has positions, so one grid serves every (batch, views, stride) split of the plan's rows)
+// batch has positions, so one grid serves every (batch, views, stride) split of the plan's rows, linear or on a ring: the block says which)
 int Engine::run_step(const UNetPlan& P, const StepKind& k, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join) {
   if (P.mode != UNetMode::TwoChains) {
     TANGO_TRY(P.step.run(st));
@@ -1511,9 +1508,7 @@ int Engine::run_step(const UNetPlan& P, const StepKind& k, hipStream_t st, hipSt
   if (k.windowed) {
     // (a ring of H = V s <= V Hw rows has no more positions than its window batch either)
     const int np = P.B2 * P.H * cfg.latent_w;
-    if (k.weighted) TANGO_TRY(k.ring ? launch_sched_ring_weighted(dt, d_wsched, np, st) : launch_sched_windows_weighted(dt, d_wsched, np, st));
-    else if (k.ring) TANGO_TRY(launch_sched_ring(dt, d_wsched, np, st));
-    else TANGO_TRY(launch_sched_windows(dt, d_wsched, np, st));
+    TANGO_TRY(launch_sched_window(dt, d_wsched, np, k.weighted, st));
     return launch_step_inc(d_step, st);
   }
   if (k.guided) TANGO_TRY(launch_guidance_stats(d_sched, P.B2 / 2, P.H * cfg.latent_w, st));
@@ -1644,31 +1639,22 @@ int Engine::run_loop(UNetPlan& P, StepGraphs& G, const StepKind& k, int num_step
 // input of every window.  prompt_embeds / prompt_mask hold B2 * V rows in the window batch's order (row half * B * V + b * V + v), so the
 // single-key prefix and the condition binding are those of a plain call of that batch.
 // Loops (tango_engine_denoise_ring): the same call with the canvas rows on a ring -- V = latent_h / stride views that wrap round it
-// (common.h ring_cover), the ring forms of the gather and of the update, and captured steps of their own (UNetPlan::rgraphs).
+// (common.h window_cover).  `ring` goes into the call's block (WindowGeom::ring) and nowhere else: the gather and the update read it
+// there, and a linear and a ring call of one shape replay the same captured steps (UNetPlan::wgraphs).
 // Timed prompts (tango_engine_denoise_windows_weighted / _ring_weighted): the same calls with a table of view weights, staged into
-// d_wweights; the update is the WEIGHTED form of the kernel, with captured steps of its own (UNetPlan::wwgraphs / rwgraphs).  `weighted`:
+// d_wweights; the update is the WEIGHTED form of the kernel, with captured steps of its own (UNetPlan::wgraphs[1]).  `weighted`:
 // the messages carry the weighted call's prefix and the table is checked last.
-static int check_window_args(const tango_denoise_args_t& a, const tango_window_args_t& w, WindowGeom* g, bool ring = false,
-                             bool weighted = false, const float* view_weights = nullptr) {
+static int check_window_args(const tango_denoise_args_t& a, const tango_window_args_t& w, WindowGeom* g, bool ring, bool weighted,
+                             const float* view_weights) {
   const std::string who = std::string(ring ? "denoise_ring" : "denoise_windows") + (weighted ? "_weighted: " : ": ");
   SchedArgs c;
   c.rule = a.rule; c.coef = a.coef; c.coef_w = a.coef_width ? a.coef_width : 8; c.num_rows = c.row1 = a.num_steps;
   c.noise = a.noise != nullptr; c.clip = a.clip_sample != 0;
   c.known = a.known_latents; c.mask = a.latent_mask; c.blend_coef = a.blend_coef; c.blend_noise = a.blend_noise;
-  if (const char* why = ring ? ring_args_refusal(c, a.latent_h, w.window_h, w.stride, g) : window_args_refusal(c, a.latent_h, w.window_h, w.stride, g))
-    TANGO_FAIL(who + why);
+  if (const char* why = window_args_refusal(c, a.latent_h, w.window_h, w.stride, ring, g)) TANGO_FAIL(who + why);
   if (weighted)
     if (const char* why = view_weights_refusal(view_weights, w.window_h)) TANGO_FAIL(who + why);
   return 0;
-}
-
-int Engine::denoise_windows(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) { return denoise_windowed(a, w, false, nullptr, false, s); }
-int Engine::denoise_ring(const tango_denoise_args_t& a, const tango_window_args_t& w, hipStream_t s) { return denoise_windowed(a, w, true, nullptr, false, s); }
-int Engine::denoise_windows_weighted(const tango_denoise_args_t& a, const tango_window_args_t& w, const float* view_weights, hipStream_t s) {
-  return denoise_windowed(a, w, false, view_weights, true, s);
-}
-int Engine::denoise_ring_weighted(const tango_denoise_args_t& a, const tango_window_args_t& w, const float* view_weights, hipStream_t s) {
-  return denoise_windowed(a, w, true, view_weights, true, s);
 }
 
 int Engine::denoise_windowed(const tango_denoise_args_t& a, const tango_window_args_t& w, bool ring, const float* view_weights, bool weighted,
@@ -1710,12 +1696,10 @@ int Engine::denoise_windowed(const tango_denoise_args_t& a, const tango_window_a
     TANGO_TRY(bind_conditions(*P, c, key0, s));
   }
   TANGO_TRY(launch_fill_zero(P->xin, (size_t)rows * Hw * W * 8 * esz, s));
-  if (ring) TANGO_TRY(launch_ring_gather(dt, a.latents, P->xin, 8, B, C, W, g, cfg_on ? 2 : 1, s));
-  else TANGO_TRY(launch_window_gather(dt, a.latents, P->xin, 8, B, C, W, g, cfg_on ? 2 : 1, s));
+  TANGO_TRY(launch_window_gather(dt, a.latents, P->xin, 8, B, C, W, g, cfg_on ? 2 : 1, s));
   StepKind k;
-  k.rule = a.rule; k.windowed = true; k.ring = ring; k.weighted = weighted;
-  StepGraphs& G = weighted ? (ring ? P->rwgraphs : P->wwgraphs) : (ring ? P->rgraphs : P->wgraphs);
-  return run_loop(*P, G, k, a.num_steps, a.use_graph != 0, s);
+  k.rule = a.rule; k.windowed = true; k.weighted = weighted;
+  return run_loop(*P, P->wgraphs[weighted], k, a.num_steps, a.use_graph != 0, s);
 }
 
 int Program::run_profiled(hipStream_t s, std::string& report) const {
@@ -2015,34 +1999,24 @@ int Engine::vae_decode(const float* lat, float* mel, int B, int latent_h, hipStr
 // latent windows of every sample go through the ordinary decoder plan of (B * V, window_h) in one run, then one blend kernel cross-fades
 // the decoded tiles into mel [B, 1, canvas_h << (levels - 1), F].  All V views are decoded, overlaps included: the decoder is about 1 %
 // of a pass, and its mid-block attention stays at the window's size whatever the clip length.
-// On a ring (vae_decode_ring, loops): the V = canvas_h / stride windows wrap round the canvas and every tile fades in and out
-// (sched.hip mel_ring_blend_kernel), so the decoded mel is as seamless at its wrap as anywhere else.
-int Engine::vae_decode_tiled(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s) {
-  return vae_decode_windowed(lat, mel, B, canvas_h, window_h, stride, false, s);
-}
-int Engine::vae_decode_ring(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, hipStream_t s) {
-  return vae_decode_windowed(lat, mel, B, canvas_h, window_h, stride, true, s);
-}
-
+// On a ring (tango_engine_vae_decode_ring_h, loops): the V = canvas_h / stride windows wrap round the canvas and every tile fades in and
+// out (sched.hip mel_tile_blend_kernel with g.ring), so the decoded mel is as seamless at its wrap as anywhere else.
 int Engine::vae_decode_windowed(const float* lat, float* mel, int B, int canvas_h, int window_h, int stride, bool ring, hipStream_t s) {
   const std::string who = ring ? "vae_decode_ring" : "vae_decode_tiled";
   if (cfg.vae_levels <= 0) TANGO_FAIL("engine: VAE not configured");
   if (cfg.vae_out_ch != 1) TANGO_FAIL("engine: VAE out_ch must be 1 (NHWC == NCHW at the boundary)");
   if (B <= 0) TANGO_FAIL(who + ": batch must be positive");
   WindowGeom g;
-  if (const char* why = ring ? ring_geom_refusal(canvas_h, window_h, stride, &g) : window_geom_refusal(canvas_h, window_h, stride, &g))
-    TANGO_FAIL(who + ": " + why);
+  if (const char* why = window_geom_refusal(canvas_h, window_h, stride, ring, &g)) TANGO_FAIL(who + ": " + why);
   int Hw;
   TANGO_TRY(resolve_h(window_h, false, &Hw));
   VaePlan* P;
   TANGO_TRY(get_vae_plan(B * g.V, Hw, &P));
-  if (ring) TANGO_TRY(launch_ring_gather_nchw(lat, (float*)P->in, B, cfg.vae_embed_dim, cfg.latent_w, g, s));
-  else TANGO_TRY(launch_window_gather_nchw(lat, (float*)P->in, B, cfg.vae_embed_dim, cfg.latent_w, g, s));
+  TANGO_TRY(launch_window_gather_nchw(lat, (float*)P->in, B, cfg.vae_embed_dim, cfg.latent_w, g, s));
   TANGO_TRY(P->prog.run(s));
   const int up = cfg.vae_levels - 1;
-  WindowGeom gm;                                   // the same geometry in mel rows
-  gm.H = g.H << up; gm.Hw = g.Hw << up; gm.s = g.s << up; gm.V = g.V;
-  if (ring) return launch_mel_ring_blend((const float*)P->out, mel, B, cfg.latent_w << up, gm, s);
+  WindowGeom gm = g;                               // the same geometry in mel rows
+  gm.H = g.H << up; gm.Hw = g.Hw << up; gm.s = g.s << up;
   return launch_mel_tile_blend((const float*)P->out, mel, B, cfg.latent_w << up, gm, s);
 }
 
@@ -2356,61 +2330,52 @@ const char* tango_debug_denoise_guided_check(const tango_denoise_args_t* a, cons
 }
 int tango_engine_denoise_windows(tango_engine_t* h, const tango_denoise_args_t* a, const tango_window_args_t* w, void* stream) {
   if (!h || !a || !w) { tango::set_error("denoise_windows: null args"); return -1; }
-  return h->e->denoise_windows(*a, *w, (hipStream_t)stream);
-}
-const char* tango_debug_denoise_windows_check(const tango_denoise_args_t* a, const tango_window_args_t* w) {
-  static thread_local std::string msg;
-  msg.clear();
-  if (!a || !w) return "denoise_windows: null args";
-  tango::WindowGeom g;
-  if (tango::check_window_args(*a, *w, &g) != 0) msg = tango_last_error();
-  return msg.c_str();
+  return h->e->denoise_windowed(*a, *w, false, nullptr, false, (hipStream_t)stream);
 }
 int tango_engine_vae_decode_tiled_h(tango_engine_t* h, const float* latents, float* mel, int batch, int canvas_h, int window_h, int stride,
                                     void* stream) {
   if (!h || !latents || !mel) { tango::set_error("vae_decode_tiled: null argument"); return -1; }
-  return h->e->vae_decode_tiled(latents, mel, batch, canvas_h, window_h, stride, (hipStream_t)stream);
+  return h->e->vae_decode_windowed(latents, mel, batch, canvas_h, window_h, stride, false, (hipStream_t)stream);
 }
 int tango_engine_denoise_ring(tango_engine_t* h, const tango_denoise_args_t* a, const tango_window_args_t* w, void* stream) {
   if (!h || !a || !w) { tango::set_error("denoise_ring: null args"); return -1; }
-  return h->e->denoise_ring(*a, *w, (hipStream_t)stream);
-}
-const char* tango_debug_denoise_ring_check(const tango_denoise_args_t* a, const tango_window_args_t* w) {
-  static thread_local std::string msg;
-  msg.clear();
-  if (!a || !w) return "denoise_ring: null args";
-  tango::WindowGeom g;
-  if (tango::check_window_args(*a, *w, &g, true) != 0) msg = tango_last_error();
-  return msg.c_str();
+  return h->e->denoise_windowed(*a, *w, true, nullptr, false, (hipStream_t)stream);
 }
 int tango_engine_denoise_windows_weighted(tango_engine_t* h, const tango_denoise_args_t* a, const tango_window_args_t* w,
                                           const float* view_weights, void* stream) {
   if (!h || !a || !w) { tango::set_error("denoise_windows_weighted: null args"); return -1; }
-  return h->e->denoise_windows_weighted(*a, *w, view_weights, (hipStream_t)stream);
+  return h->e->denoise_windowed(*a, *w, false, view_weights, true, (hipStream_t)stream);
 }
 int tango_engine_denoise_ring_weighted(tango_engine_t* h, const tango_denoise_args_t* a, const tango_window_args_t* w,
                                        const float* view_weights, void* stream) {
   if (!h || !a || !w) { tango::set_error("denoise_ring_weighted: null args"); return -1; }
-  return h->e->denoise_ring_weighted(*a, *w, view_weights, (hipStream_t)stream);
+  return h->e->denoise_windowed(*a, *w, true, view_weights, true, (hipStream_t)stream);
 }
-static const char* weighted_check(const tango_denoise_args_t* a, const tango_window_args_t* w, const float* view_weights, bool ring) {
+// why a windowed call would be refused ("" if it would not): the four public checks are this one with the call's mode
+static const char* windowed_check(const tango_denoise_args_t* a, const tango_window_args_t* w, bool ring, bool weighted, const float* view_weights) {
   static thread_local std::string msg;
   msg.clear();
-  if (!a || !w) return ring ? "denoise_ring_weighted: null args" : "denoise_windows_weighted: null args";
   tango::WindowGeom g;
-  if (tango::check_window_args(*a, *w, &g, ring, true, view_weights) != 0) msg = tango_last_error();
+  if (!a || !w) msg = std::string(ring ? "denoise_ring" : "denoise_windows") + (weighted ? "_weighted" : "") + ": null args";
+  else if (tango::check_window_args(*a, *w, &g, ring, weighted, view_weights) != 0) msg = tango_last_error();
   return msg.c_str();
 }
+const char* tango_debug_denoise_windows_check(const tango_denoise_args_t* a, const tango_window_args_t* w) {
+  return windowed_check(a, w, false, false, nullptr);
+}
+const char* tango_debug_denoise_ring_check(const tango_denoise_args_t* a, const tango_window_args_t* w) {
+  return windowed_check(a, w, true, false, nullptr);
+}
 const char* tango_debug_denoise_windows_weighted_check(const tango_denoise_args_t* a, const tango_window_args_t* w, const float* view_weights) {
-  return weighted_check(a, w, view_weights, false);
+  return windowed_check(a, w, false, true, view_weights);
 }
 const char* tango_debug_denoise_ring_weighted_check(const tango_denoise_args_t* a, const tango_window_args_t* w, const float* view_weights) {
-  return weighted_check(a, w, view_weights, true);
+  return windowed_check(a, w, true, true, view_weights);
 }
 int tango_engine_vae_decode_ring_h(tango_engine_t* h, const float* latents, float* mel, int batch, int canvas_h, int window_h, int stride,
                                    void* stream) {
   if (!h || !latents || !mel) { tango::set_error("vae_decode_ring: null argument"); return -1; }
-  return h->e->vae_decode_ring(latents, mel, batch, canvas_h, window_h, stride, (hipStream_t)stream);
+  return h->e->vae_decode_windowed(latents, mel, batch, canvas_h, window_h, stride, true, (hipStream_t)stream);
 }
 int tango_engine_vocode_ring(tango_engine_t* h, const float* mel, int16_t* wav, int batch, int mel_frames, int* n_samples, void* stream) {
   if (!h || !mel || !wav) { tango::set_error("vocode_ring: null argument"); return -1; }

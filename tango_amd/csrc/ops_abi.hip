@@ -1026,7 +1026,7 @@ static int op_sched_windowed(bool ring, bool weighted, const float* view_weights
   SchedArgs c;                      // the engine's own rules; the single row is the row of this step
   c.rule = rule; c.coef = coef8; c.coef_w = 8; c.num_rows = 1; c.row0 = 0; c.row1 = 1; c.noise = noise != nullptr; c.clip = clip != 0;
   WindowGeom g;
-  if (const char* why = ring ? ring_args_refusal(c, H, Hw, sw, &g) : window_args_refusal(c, H, Hw, sw, &g)) TANGO_FAIL(w + ": " + why);
+  if (const char* why = window_args_refusal(c, H, Hw, sw, ring, &g)) TANGO_FAIL(w + ": " + why);
   if (weighted)
     if (const char* why = view_weights_refusal(view_weights, Hw)) TANGO_FAIL(w + ": " + why);
   if (!noise && C % 4 != 0) TANGO_FAIL(w + ": the Philox stream draws four channels at a time: C must be a multiple of 4");
@@ -1051,9 +1051,7 @@ static int op_sched_windowed(bool ring, bool weighted, const float* view_weights
   p.clip = clip; p.clip_range = clip_range; p.seed = seed; p.sample_offset = sample_offset; p.num_steps = step + 1;
   wp.g = g; wp.W = W; wp.noise_row0 = step; wp.weights = dwt;
   TANGO_HIP(hipMemcpyAsync(dp, &wp, sizeof(SchedWindowParams), hipMemcpyHostToDevice, s));
-  if (weighted) TANGO_TRY(ring ? launch_sched_ring_weighted(DT_F32, dp, B * H * W, s) : launch_sched_windows_weighted(DT_F32, dp, B * H * W, s));
-  else if (ring) TANGO_TRY(launch_sched_ring(DT_F32, dp, B * H * W, s));
-  else TANGO_TRY(launch_sched_windows(DT_F32, dp, B * H * W, s));
+  TANGO_TRY(launch_sched_window(DT_F32, dp, B * H * W, weighted, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
 }
@@ -1083,16 +1081,24 @@ int tango_op_sched_ring_weighted(float* latents, const float* model_out_nchw, co
                            clip, clip_range, seed, sample_offset, step, stream);
 }
 
-int tango_op_mel_ring_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream) {
-  if (B <= 0 || V <= 0 || F <= 0 || !tiles || !out) TANGO_FAIL("op_mel_ring_blend: bad arguments");
-  if ((int64_t)V * Hw4 > ((int64_t)1 << 24)) TANGO_FAIL("op_mel_ring_blend: V * Hw4 too large");
+// the tile blend's hook, linear (tango_op_mel_tile_blend: V tiles span (V - 1) s4 + Hw4 mel rows) or on a ring (tango_op_mel_ring_blend: V s4)
+static int op_mel_blend(bool ring, const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream) {
+  const std::string w(ring ? "op_mel_ring_blend" : "op_mel_tile_blend");
+  if (B <= 0 || V <= 0 || F <= 0 || !tiles || !out) TANGO_FAIL(w + ": bad arguments");
+  if ((int64_t)V * Hw4 > ((int64_t)1 << 24)) TANGO_FAIL(w + ": V * Hw4 too large");
   WindowGeom g;
-  if (Hw4 <= 0 || s4 < 1 || s4 > Hw4) TANGO_FAIL("op_mel_ring_blend: 1 <= s4 <= Hw4 is required");
-  if (const char* why = ring_geom_refusal(V * s4, Hw4, s4, &g)) TANGO_FAIL(std::string("op_mel_ring_blend: ") + why);
+  if (Hw4 <= 0 || s4 < 1 || s4 > Hw4) TANGO_FAIL(w + ": 1 <= s4 <= Hw4 is required");
+  if (const char* why = window_geom_refusal(ring ? V * s4 : (V - 1) * s4 + Hw4, Hw4, s4, ring, &g)) TANGO_FAIL(w + ": " + why);
   hipStream_t s = (hipStream_t)stream;
-  TANGO_TRY(launch_mel_ring_blend(tiles, out, B, F, g, s));
+  TANGO_TRY(launch_mel_tile_blend(tiles, out, B, F, g, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
+}
+int tango_op_mel_tile_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream) {
+  return op_mel_blend(false, tiles, out, B, V, Hw4, F, s4, stream);
+}
+int tango_op_mel_ring_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream) {
+  return op_mel_blend(true, tiles, out, B, V, Hw4, F, s4, stream);
 }
 
 int tango_op_mel_ring_pad(const float* mel, float* out, int B, int T, int F, int ctx, void* stream) {
@@ -1100,18 +1106,6 @@ int tango_op_mel_ring_pad(const float* mel, float* out, int B, int T, int F, int
   if (B <= 0 || T <= 0 || F <= 0 || ctx < 0 || (int64_t)B * (T + 2 * (int64_t)ctx) * F >= ((int64_t)1 << 31)) TANGO_FAIL("op_mel_ring_pad: bad sizes");
   hipStream_t s = (hipStream_t)stream;
   TANGO_TRY(launch_mel_ring_pad(mel, out, B, T, F, ctx, s));
-  TANGO_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-int tango_op_mel_tile_blend(const float* tiles, float* out, int B, int V, int Hw4, int F, int s4, void* stream) {
-  if (B <= 0 || V <= 0 || F <= 0 || !tiles || !out) TANGO_FAIL("op_mel_tile_blend: bad arguments");
-  if ((int64_t)V * Hw4 > ((int64_t)1 << 24)) TANGO_FAIL("op_mel_tile_blend: V * Hw4 too large");
-  WindowGeom g;
-  if (Hw4 <= 0 || s4 < 1 || s4 > Hw4) TANGO_FAIL("op_mel_tile_blend: 1 <= s4 <= Hw4 is required");
-  if (const char* why = window_geom_refusal((V - 1) * s4 + Hw4, Hw4, s4, &g)) TANGO_FAIL(std::string("op_mel_tile_blend: ") + why);
-  hipStream_t s = (hipStream_t)stream;
-  TANGO_TRY(launch_mel_tile_blend(tiles, out, B, F, g, s));
   TANGO_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -239,10 +239,11 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __re
 // floors and leaves a tail of rows with count == 0); (2) nz is ONE draw per canvas element -- injected noise[step][b, c, h, w] or Philox with
 // the canvas position as the counter's hw -- where the fork's loop would average V independent draws and shrink the variance of a
 // stochastic sampler's step noise by |cover(h)|.  With sig == 0 (DDIM eta = 0, the last DDPM step) it is the fork's loop.
-// RING (loops, tango_engine_denoise_ring): the canvas rows are a ring and the views wrap round it (common.h ring_cover): the same
-// per-view arithmetic over the views (v0 + j) mod V at local rows y0 - j s, the view that starts farthest below h first -- for a row
-// that no view wraps over, the ascending order above.  The order is relative to h, so the update commutes with a rotation of the ring
-// by a multiple of s: no row is special, the wrap point included.  The linear form walks its views as (v_lo + j, h - v_lo s - j s).
+// g.ring (loops, tango_engine_denoise_ring): the canvas rows are a ring and the views wrap round it.  The mode is data of the block: it
+// changes only the three integers of the cover (common.h window_cover), computed once per thread; both modes then walk the views
+// (v0 + j) mod V at local rows y0 - j s with the same per-view arithmetic.  On a ring the view that starts farthest below h comes first
+// -- for a row that no view wraps over, the ascending order above.  The order is relative to h, so the update commutes with a rotation
+// of the ring by a multiple of s: no row is special, the wrap point included.
 // WEIGHTED (timed prompts, tango_engine_denoise_*_weighted): weighted MultiDiffusion / "Mixture of Diffusers" (Jimenez 2023).  The block's
 // `weights` is a device table of Hw positive floats, one per local window row, shared by all views; over the same views in the same order
 //   acc = 0; wsum = 0;   t = w[y_v] * d_v; acc = acc + t; wsum = wsum + w[y_v];   r = acc / wsum   (IEEE division);   + sig * nz as above
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(256) void sched_step_kernel(const SchedParams* __re
 // summed once per thread.  All weights 1: t = d and wsum = n are exact, the unweighted kernel's bits.  One view with w != 1: (w d) / w may
 // differ from d in the last bit; there is no special case.
 // ------------------------------------------------------------------------------------------
-template <typename T, bool RING, bool WEIGHTED = false>
+template <typename T, bool WEIGHTED>
 __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowParams* __restrict__ pp) {
 #pragma clang fp contract(off)
   const SchedParams p = pp->p;
@@ -260,14 +261,8 @@ __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowPara
   if (idx >= p.B * p.HW) return;
   const int b = idx / p.HW, hw = idx - b * p.HW;
   const int h = hw / W, w = hw - h * W;
-  int n, v0, y0;                                    // the cover: n views from v0 at local row y0, then one view up and s rows down
-  if (RING) {
-    n = ring_cover(g, h, &v0, &y0);
-  } else {
-    int v_hi;
-    window_cover(g, h, &v0, &v_hi);
-    n = v_hi - v0 + 1; y0 = h - v0 * g.s;
-  }
+  int v0, y0;                                       // the cover: n views from v0 at local row y0, then one view up and s rows down
+  const int n = window_cover(g, h, &v0, &y0);
   float cnt = (float)n;
   const float* wt = nullptr;
   if constexpr (WEIGHTED) {
@@ -332,7 +327,8 @@ __global__ __launch_bounds__(256) void sched_window_kernel(const SchedWindowPara
 }
 
 // canvas fp32 NCHW -> the window batch T NHWC before step 0: the windowed form of nchw_to_nhwc_kernel with rep CFG halves.  One
-// thread per (window row, position); a canvas element that V' views cover is read V' times.
+// thread per (window row, position); a canvas element that V' views cover is read V' times.  Window position (y, w) of view v is
+// canvas position (v s + y, w), minus H rows when v s + y reaches H: only a ring's views get there, and v s + y < H + Hw <= 2 H.
 template <typename T>
 __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ lat, T* __restrict__ xin, int64_t ld, int B, int C, int W,
                                                             WindowGeom g, int rep) {
@@ -342,7 +338,8 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restr
   const int row = (int)(idx / win), pos = (int)(idx - (int64_t)row * win);
   const int b = row / g.V, v = row - b * g.V;
   const int64_t HW = (int64_t)g.H * W;
-  const int64_t src = (int64_t)v * g.s * W + pos;       // window position (y, w) is canvas position (v s + y, w)
+  int64_t src = (int64_t)v * g.s * W + pos;             // (v s + y) W + w
+  if (src >= HW) src -= HW;                             // v s + y >= H: the view wraps
   for (int c = 0; c < C; ++c) {
     const T t = from_f<T>(lat[((int64_t)b * C + c) * HW + src]);
     for (int r = 0; r < rep; ++r) xin[((int64_t)r * B * g.V * win + idx) * ld + c] = t;
@@ -359,13 +356,17 @@ __global__ __launch_bounds__(256) void window_gather_nchw_kernel(const float* __
   const int pos = (int)(idx - rc * win);
   const int c = (int)(rc % C), row = (int)(rc / C);
   const int b = row / g.V, v = row - b * g.V;
-  dst[idx] = lat[((int64_t)b * C + c) * g.H * W + (int64_t)v * g.s * W + pos];
+  const int64_t HW = (int64_t)g.H * W;
+  int64_t src = (int64_t)v * g.s * W + pos;
+  if (src >= HW) src -= HW;
+  dst[idx] = lat[((int64_t)b * C + c) * HW + src];
 }
 
 // Cross-fade of the V decoded tiles of a clip (the fork's tiled VAE decode, mustango/diffusers/src/diffusers/models/autoencoder_kl.py
-// :198-201 blend_v, :255-296).  g counts mel rows: tile t holds output rows [t s, t s + Hw), E = Hw - s rows overlap.  The weight of
-// tile t at its local row y is min(1, (y + 0.5) / E) if t > 0, times min(1, (Hw - y - 0.5) / E) if t < V - 1 (both 1 when E == 0), and
-//   out[r] = (sum_t w_t tile_t) / (sum_t w_t)   over the covering tiles, ascending, each sum from 0, in fp32 without FMA contraction.
+// :198-201 blend_v, :255-296).  g counts mel rows: tile t holds output rows t s + y for y in [0, Hw) (mod H on a ring), E = Hw - s rows
+// overlap.  The weight of tile t at its local row y is min(1, (y + 0.5) / E) if it has a predecessor (t > 0, or a ring), times
+// min(1, (Hw - y - 0.5) / E) if it has a successor (t < V - 1, or a ring); both 1 when E == 0.  Then
+//   out[r] = (sum_t w_t tile_t) / (sum_t w_t)   over the covering tiles in window_cover's order, each sum from 0, in fp32 without FMA contraction.
 // For s >= Hw / 2 two overlapping weights sum to 1: blend_v's linear ramp sampled at half-pixel centres; deeper overlaps use the same formula.
 __global__ __launch_bounds__(256) void mel_tile_blend_kernel(const float* __restrict__ tiles, float* __restrict__ out, int B, int F, WindowGeom g) {
 #pragma clang fp contract(off)
@@ -374,78 +375,16 @@ __global__ __launch_bounds__(256) void mel_tile_blend_kernel(const float* __rest
   const int f = (int)(idx % F);
   const int64_t br = idx / F;
   const int r = (int)(br % g.H), b = (int)(br / g.H);
-  int t_lo, t_hi;
-  window_cover(g, r, &t_lo, &t_hi);
-  const int E = g.Hw - g.s;
-  float num = 0.0f, den = 0.0f;
-  for (int t = t_lo; t <= t_hi; ++t) {
-    const int y = r - t * g.s;
-    float wt = 1.0f;
-    if (E > 0 && t > 0) { const float a = (float)y + 0.5f; wt = fminf(1.0f, a / (float)E); }
-    if (E > 0 && t < g.V - 1) { const float a = (float)(g.Hw - y) - 0.5f; const float u = fminf(1.0f, a / (float)E); wt = wt * u; }
-    const float m = wt * tiles[(((int64_t)b * g.V + t) * g.Hw + y) * F + f];
-    num = num + m;
-    den = den + wt;
-  }
-  out[idx] = num / den;
-}
-
-// ---- loops: the gathers, the tile blend and the vocoder's context on a ring ----
-// window_gather_kernel with source row (v s + y) mod H
-template <typename T>
-__global__ __launch_bounds__(256) void ring_gather_kernel(const float* __restrict__ lat, T* __restrict__ xin, int64_t ld, int B, int C, int W,
-                                                          WindowGeom g, int rep) {
-  const int64_t win = (int64_t)g.Hw * W;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (int64_t)B * g.V * win) return;
-  const int row = (int)(idx / win), pos = (int)(idx - (int64_t)row * win);
-  const int b = row / g.V, v = row - b * g.V;
-  const int y = pos / W, w = pos - y * W;
-  const int64_t HW = (int64_t)g.H * W;
-  const int64_t src = (int64_t)((v * g.s + y) % g.H) * W + w;
-  for (int c = 0; c < C; ++c) {
-    const T t = from_f<T>(lat[((int64_t)b * C + c) * HW + src]);
-    for (int r = 0; r < rep; ++r) xin[((int64_t)r * B * g.V * win + idx) * ld + c] = t;
-  }
-}
-
-// window_gather_nchw_kernel with source row (v s + y) mod H
-__global__ __launch_bounds__(256) void ring_gather_nchw_kernel(const float* __restrict__ lat, float* __restrict__ dst, int B, int C, int W,
-                                                               WindowGeom g) {
-  const int64_t win = (int64_t)g.Hw * W;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (int64_t)B * g.V * C * win) return;
-  const int64_t rc = idx / win;                          // (b V + v) C + c
-  const int pos = (int)(idx - rc * win);
-  const int c = (int)(rc % C), row = (int)(rc / C);
-  const int b = row / g.V, v = row - b * g.V;
-  const int y = pos / W, w = pos - y * W;
-  dst[idx] = lat[((int64_t)b * C + c) * g.H * W + (int64_t)((v * g.s + y) % g.H) * W + w];
-}
-
-// mel_tile_blend_kernel on a ring: every tile has a predecessor and a successor, so every tile gets both ramps.  g counts mel rows; with
-// E = Hw - s the weight of a tile at its local row y is min(1, (y + 0.5) / E) * min(1, (Hw - y - 0.5) / E) (1 when E == 0), and
-//   out[r] = (sum w tile) / (sum w)   over the covering tiles in ring_cover's order, each sum from 0, in fp32 without FMA contraction.
-// For s == Hw / 2 the two weights at every row sum to 1.
-__global__ __launch_bounds__(256) void mel_ring_blend_kernel(const float* __restrict__ tiles, float* __restrict__ out, int B, int F, WindowGeom g) {
-#pragma clang fp contract(off)
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (int64_t)B * g.H * F) return;
-  const int f = (int)(idx % F);
-  const int64_t br = idx / F;
-  const int r = (int)(br % g.H), b = (int)(br / g.H);
   int t, y;
-  const int n = ring_cover(g, r, &t, &y);
+  const int n = window_cover(g, r, &t, &y);
   const int E = g.Hw - g.s;
   float num = 0.0f, den = 0.0f;
   for (int j = 0; j < n; ++j, y -= g.s) {
     float wt = 1.0f;
-    if (E > 0) {
-      const float a = (float)y + 0.5f; wt = fminf(1.0f, a / (float)E);
-      const float a2 = (float)(g.Hw - y) - 0.5f; const float u = fminf(1.0f, a2 / (float)E); wt = wt * u;
-    }
+    if (E > 0 && (g.ring || t > 0)) { const float a = (float)y + 0.5f; wt = fminf(1.0f, a / (float)E); }
+    if (E > 0 && (g.ring || t < g.V - 1)) { const float a = (float)(g.Hw - y) - 0.5f; const float u = fminf(1.0f, a / (float)E); wt = wt * u; }
     const float m = wt * tiles[(((int64_t)b * g.V + t) * g.Hw + y) * F + f];
-    if (++t == g.V) t = 0;
+    if (++t == g.V) t = 0;                              // (only a ring's tiles wrap)
     num = num + m;
     den = den + wt;
   }
@@ -463,57 +402,6 @@ __global__ __launch_bounds__(256) void mel_ring_pad_kernel(const float* __restri
   int t = (j - ctx) % T;
   if (t < 0) t += T;
   dst[idx] = mel[((int64_t)b * T + t) * F + f];
-}
-
-template <bool RING, bool WEIGHTED = false>
-static int launch_sched_windowed(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
-  const dim3 grid((unsigned)((max_positions + 255) / 256));
-  switch (dtype) {
-    case DT_F32: hipLaunchKernelGGL((sched_window_kernel<float, RING, WEIGHTED>), grid, dim3(256), 0, s, dev_params); break;
-    case DT_F16: hipLaunchKernelGGL((sched_window_kernel<f16, RING, WEIGHTED>), grid, dim3(256), 0, s, dev_params); break;
-    case DT_BF16: hipLaunchKernelGGL((sched_window_kernel<bf16, RING, WEIGHTED>), grid, dim3(256), 0, s, dev_params); break;
-    default: TANGO_FAIL(RING ? "sched_ring: bad dtype" : "sched_windows: bad dtype");
-  }
-  TANGO_HIP(hipGetLastError());
-  return 0;
-}
-int launch_sched_windows_weighted(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
-  return launch_sched_windowed<false, true>(dtype, dev_params, max_positions, s);
-}
-int launch_sched_ring_weighted(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
-  return launch_sched_windowed<true, true>(dtype, dev_params, max_positions, s);
-}
-int launch_sched_windows(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
-  return launch_sched_windowed<false>(dtype, dev_params, max_positions, s);
-}
-int launch_sched_ring(int dtype, const SchedWindowParams* dev_params, int max_positions, hipStream_t s) {
-  return launch_sched_windowed<true>(dtype, dev_params, max_positions, s);
-}
-
-int launch_ring_gather(int dtype, const float* lat, void* xin, int64_t ld, int B, int C, int W, const WindowGeom& g, int rep, hipStream_t s) {
-  const dim3 grid((unsigned)(((int64_t)B * g.V * g.Hw * W + 255) / 256));
-  switch (dtype) {
-    case DT_F32: hipLaunchKernelGGL(ring_gather_kernel<float>, grid, dim3(256), 0, s, lat, (float*)xin, ld, B, C, W, g, rep); break;
-    case DT_F16: hipLaunchKernelGGL(ring_gather_kernel<f16>, grid, dim3(256), 0, s, lat, (f16*)xin, ld, B, C, W, g, rep); break;
-    case DT_BF16: hipLaunchKernelGGL(ring_gather_kernel<bf16>, grid, dim3(256), 0, s, lat, (bf16*)xin, ld, B, C, W, g, rep); break;
-    default: TANGO_FAIL("ring_gather: bad dtype");
-  }
-  TANGO_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_ring_gather_nchw(const float* lat, float* dst, int B, int C, int W, const WindowGeom& g, hipStream_t s) {
-  const dim3 grid((unsigned)(((int64_t)B * g.V * C * g.Hw * W + 255) / 256));
-  hipLaunchKernelGGL(ring_gather_nchw_kernel, grid, dim3(256), 0, s, lat, dst, B, C, W, g);
-  TANGO_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_mel_ring_blend(const float* tiles, float* out, int B, int F, const WindowGeom& g, hipStream_t s) {
-  const dim3 grid((unsigned)(((int64_t)B * g.H * F + 255) / 256));
-  hipLaunchKernelGGL(mel_ring_blend_kernel, grid, dim3(256), 0, s, tiles, out, B, F, g);
-  TANGO_HIP(hipGetLastError());
-  return 0;
 }
 
 int launch_mel_ring_pad(const float* mel, float* dst, int B, int T, int F, int ctx, hipStream_t s) {
@@ -550,27 +438,24 @@ int launch_mel_tile_blend(const float* tiles, float* out, int B, int F, const Wi
   return 0;
 }
 
-const char* window_geom_refusal(int canvas_h, int window_h, int stride, WindowGeom* g) {
+// One message per condition; a ring's are H >= Hw, H % s == 0, 1 <= s <= Hw, V = H / s <= kMaxWindows, asked in that order.
+const char* window_geom_refusal(int canvas_h, int window_h, int stride, bool ring, WindowGeom* g) {
   if (window_h <= 0) return "window_h must be positive";
-  if (stride < 1 || stride > window_h) return "stride must be in [1, window_h]";
-  if (canvas_h < window_h) return "the canvas height must be at least window_h";
-  if ((canvas_h - window_h) % stride != 0)
-    return "the windows must cover the canvas exactly: (canvas height - window_h) must be a multiple of stride";
-  const int V = (canvas_h - window_h) / stride + 1;
-  if (V > kMaxWindows) return "at most 32 windows per clip";
-  if (g) { g->H = canvas_h; g->Hw = window_h; g->s = stride; g->V = V; }
-  return nullptr;
-}
-
-// a ring's conditions, one message each (common.h): H >= Hw, H % s == 0, 1 <= s <= Hw, V = H / s <= kMaxWindows
-const char* ring_geom_refusal(int canvas_h, int window_h, int stride, WindowGeom* g) {
-  if (window_h <= 0) return "window_h must be positive";
-  if (canvas_h < window_h) return "the ring must be at least window_h rows long";
-  if (stride >= 1 && canvas_h % stride != 0) return "the ring's height must be a multiple of stride";
-  if (stride < 1 || stride > window_h) return "stride must be in [1, window_h]";
-  const int V = canvas_h / stride;
-  if (V > kMaxWindows) return "at most 32 windows per ring";
-  if (g) { g->H = canvas_h; g->Hw = window_h; g->s = stride; g->V = V; }
+  int V;
+  if (ring) {
+    if (canvas_h < window_h) return "the ring must be at least window_h rows long";
+    if (stride >= 1 && canvas_h % stride != 0) return "the ring's height must be a multiple of stride";
+    if (stride < 1 || stride > window_h) return "stride must be in [1, window_h]";
+    V = canvas_h / stride;
+  } else {
+    if (stride < 1 || stride > window_h) return "stride must be in [1, window_h]";
+    if (canvas_h < window_h) return "the canvas height must be at least window_h";
+    if ((canvas_h - window_h) % stride != 0)
+      return "the windows must cover the canvas exactly: (canvas height - window_h) must be a multiple of stride";
+    V = (canvas_h - window_h) / stride + 1;
+  }
+  if (V > kMaxWindows) return ring ? "at most 32 windows per ring" : "at most 32 windows per clip";
+  if (g) { g->H = canvas_h; g->Hw = window_h; g->s = stride; g->V = V; g->ring = ring; }
   return nullptr;
 }
 
@@ -826,6 +711,9 @@ static const SchedKernel kSchedKernels[2][2][2][3] = {
     {{TANGO_SCHED_DTYPES(sched_multistep_kernel, false, false), TANGO_SCHED_DTYPES(sched_multistep_kernel, false, true)},
      {TANGO_SCHED_DTYPES(sched_multistep_kernel, true, false), TANGO_SCHED_DTYPES(sched_multistep_kernel, true, true)}}};
 static const SchedKernel kBlend0Kernels[3] = TANGO_SCHED_DTYPES(inpaint_blend0_kernel);
+typedef void (*SchedWindowKernel)(const SchedWindowParams*);
+static const SchedWindowKernel kSchedWindowKernels[2][3] = {TANGO_SCHED_DTYPES(sched_window_kernel, false),   // [weighted][dtype]
+                                                            TANGO_SCHED_DTYPES(sched_window_kernel, true)};
 #undef TANGO_SCHED_DTYPES
 
 // one thread per latent position: the grid covers max_positions >= B * HW of the block, surplus threads exit
@@ -843,6 +731,13 @@ int launch_inpaint_blend0(int dtype, const SchedParams* dev_params, int max_posi
 int launch_sched_step(int dtype, const SchedParams* dev_params, int max_positions, hipStream_t s, int rule, bool masked, bool guided) {
   if (dtype < DT_F32 || dtype > DT_BF16) TANGO_FAIL("sched_step: bad dtype");
   return launch_sched_kernel(kSchedKernels[rule == TANGO_RULE_DPM_MULTISTEP][masked][guided][dtype], dev_params, max_positions, s);
+}
+
+int launch_sched_window(int dtype, const SchedWindowParams* dev_params, int max_positions, bool weighted, hipStream_t s) {
+  if (dtype < DT_F32 || dtype > DT_BF16) TANGO_FAIL("sched_window: bad dtype");
+  hipLaunchKernelGGL(kSchedWindowKernels[weighted][dtype], dim3((unsigned)((max_positions + 255) / 256)), dim3(256), 0, s, dev_params);
+  TANGO_HIP(hipGetLastError());
+  return 0;
 }
 
 __global__ void step_inc_kernel(int* sp) { if (threadIdx.x == 0 && blockIdx.x == 0) *sp = *sp + 1; }
@@ -885,28 +780,19 @@ const char* sched_args_refusal(const SchedArgs& a) {
   return nullptr;
 }
 
-// Why the windowed update refuses these arguments: the multistep rule, what the plain update refuses, what else windows leave out, the geometry.
-const char* window_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, WindowGeom* g) {
+// Why the windowed update refuses these arguments, in this order: the multistep rule, what the plain update refuses, what else windows leave
+// out, the geometry.  A ring says "on a ring" where a linear canvas says "with windows".
+const char* window_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, bool ring, WindowGeom* g) {
   if (a.rule == TANGO_RULE_DPM_MULTISTEP)           // first: whatever its table looks like
-    return "the multistep rule is not supported with windows (a per-view history has no reference behaviour): use DDPM or DDIM";
+    return ring ? "the multistep rule is not supported on a ring: use DDPM or DDIM"
+                : "the multistep rule is not supported with windows (a per-view history has no reference behaviour): use DDPM or DDIM";
   if (const char* why = sched_args_refusal(a)) return why;
-  if (a.known) return "known_latents (masked-latent inpainting) is not supported with windows";
-  if (a.guided && (a.table || a.rescale > 0.0f)) return "a guidance table or rescale is not supported with windows";
-  if (canvas_h <= 0) return "a windowed call states its canvas height (latent_h > 0)";
-  if (const char* why = window_geom_refusal(canvas_h, window_h, stride, g)) return why;
-  if (window_h % 8 != 0) return "window_h is not a UNet height";
-  return nullptr;
-}
-
-// Why the update on a ring refuses these arguments, in this order.
-const char* ring_args_refusal(const SchedArgs& a, int canvas_h, int window_h, int stride, WindowGeom* g) {
-  if (a.rule == TANGO_RULE_DPM_MULTISTEP)           // first: whatever its table looks like
-    return "the multistep rule is not supported on a ring: use DDPM or DDIM";
-  if (const char* why = sched_args_refusal(a)) return why;
-  if (a.known) return "known_latents (masked-latent inpainting) is not supported on a ring";
-  if (a.guided && (a.table || a.rescale > 0.0f)) return "a guidance table or rescale is not supported on a ring";
-  if (canvas_h <= 0) return "a ring call states its canvas height (latent_h > 0)";
-  if (const char* why = ring_geom_refusal(canvas_h, window_h, stride, g)) return why;
+  if (a.known) return ring ? "known_latents (masked-latent inpainting) is not supported on a ring"
+                           : "known_latents (masked-latent inpainting) is not supported with windows";
+  if (a.guided && (a.table || a.rescale > 0.0f)) return ring ? "a guidance table or rescale is not supported on a ring"
+                                                             : "a guidance table or rescale is not supported with windows";
+  if (canvas_h <= 0) return ring ? "a ring call states its canvas height (latent_h > 0)" : "a windowed call states its canvas height (latent_h > 0)";
+  if (const char* why = window_geom_refusal(canvas_h, window_h, stride, ring, g)) return why;
   if (window_h % 8 != 0) return "window_h is not a UNet height";
   return nullptr;
 }

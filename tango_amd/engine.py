@@ -371,10 +371,11 @@ class Engine:
                 _lib.check(self.lib.tango_engine_denoise_guided(self._h, C.byref(a), C.byref(g), _stream_ptr()), "denoise")
         return latents
 
-    def _check_canvas(self, what, x, channels, window_h, stride):
-        """a long clip's canvas [B, channels, H, latent_w] against its windows, as _check_latents checks a plain call: `window_h` a
-        height of the duration grid, 1 <= stride <= window_h, and the V = (H - window_h) / stride + 1 <= 32 views cover the H rows
-        exactly.  Returns (H, window_h, stride, V)."""
+    def _check_windows(self, what, x, channels, window_h, stride, ring):
+        """a canvas [B, channels, H, latent_w] against its windows, as _check_latents checks a plain call: `window_h` a height of the
+        duration grid and 1 <= stride <= window_h <= H.  A long clip (ring False): the V = (H - window_h) / stride + 1 <= 32 views cover
+        the H rows exactly.  A loop (ring True): H a multiple of stride and V = H / stride <= 32 views that wrap round the ring.
+        Returns (H, window_h, stride, V)."""
         hw = check_latent_h(window_h)
         if int(stride) != stride or not 1 <= stride <= hw:
             raise ValueError("stride %r must be an integer in [1, window_h = %d]" % (stride, hw))
@@ -382,29 +383,15 @@ class Engine:
         if x.dim() != 4 or tuple(x.shape[1::2]) != (channels, self._cfg.latent_w):
             raise ValueError("%s must be [B, %d, H, %d], got %s" % (what, channels, self._cfg.latent_w, tuple(x.shape)))
         H = x.shape[2]
-        if H < hw or (H - hw) % stride:
+        if ring:
+            if H < hw:
+                raise ValueError("%s of height %d is shorter than its windows of %d rows: a window must not meet itself on the ring" % (what, H, hw))
+            if H % stride:
+                raise ValueError("%s of height %d is no ring of windows every %d rows: H must be a multiple of stride" % (what, H, stride))
+        elif H < hw or (H - hw) % stride:
             raise ValueError("%s of height %d is not covered exactly by windows of %d rows every %d rows: (H - window_h) must be a "
                              "multiple of stride" % (what, H, hw, stride))
-        V = (H - hw) // stride + 1
-        if V > 32:
-            raise ValueError("%s of height %d needs %d windows: at most 32" % (what, H, V))
-        return H, hw, stride, V
-
-    def _check_ring(self, what, x, channels, window_h, stride):
-        """a loop's ring canvas [B, channels, H, latent_w] against its windows: `window_h` a height of the duration grid, 1 <= stride <=
-        window_h <= H, H a multiple of stride and V = H / stride <= 32 views that wrap round the ring.  Returns (H, window_h, stride, V)."""
-        hw = check_latent_h(window_h)
-        if int(stride) != stride or not 1 <= stride <= hw:
-            raise ValueError("stride %r must be an integer in [1, window_h = %d]" % (stride, hw))
-        stride = int(stride)
-        if x.dim() != 4 or tuple(x.shape[1::2]) != (channels, self._cfg.latent_w):
-            raise ValueError("%s must be [B, %d, H, %d], got %s" % (what, channels, self._cfg.latent_w, tuple(x.shape)))
-        H = x.shape[2]
-        if H < hw:
-            raise ValueError("%s of height %d is shorter than its windows of %d rows: a window must not meet itself on the ring" % (what, H, hw))
-        if H % stride:
-            raise ValueError("%s of height %d is no ring of windows every %d rows: H must be a multiple of stride" % (what, H, stride))
-        V = H // stride
+        V = H // stride if ring else (H - hw) // stride + 1
         if V > 32:
             raise ValueError("%s of height %d needs %d windows: at most 32" % (what, H, V))
         return H, hw, stride, V
@@ -445,7 +432,7 @@ class Engine:
             raise ValueError("a guidance table or rescale is not supported " + how)
         if self.unet_cfg.get("music"):
             raise ValueError(name + " serves the plain UNet: the Music UNet's conditions are not windowed")
-        H, hw, stride, V = (self._check_ring if _ring else self._check_canvas)("latents", latents, self.unet_cfg["in_channels"], window_h, stride)
+        H, hw, stride, V = self._check_windows("latents", latents, self.unet_cfg["in_channels"], window_h, stride, _ring)
         enc = self._f32(prompt_embeds)
         mask = self._u8(prompt_mask)
         mask_host = prompt_mask.to(torch.uint8).contiguous() if prompt_mask is not None and not prompt_mask.is_cuda else None
@@ -482,54 +469,50 @@ class Engine:
         a.use_graph = 1 if use_graph else 0
         a.latent_h = H
         w = _lib.WindowArgs(window_h=hw, stride=stride)
+        extra = ()
         if view_weights is not None:
             vw = np.ascontiguousarray(np.asarray(view_weights.cpu() if torch.is_tensor(view_weights) else view_weights, dtype=np.float32))
             if vw.shape != (hw,):
                 raise ValueError("view_weights must be [window_h = %d], got %s" % (hw, vw.shape))
-            check, run = ((self.lib.tango_debug_denoise_ring_weighted_check, self.lib.tango_engine_denoise_ring_weighted) if _ring else
-                          (self.lib.tango_debug_denoise_windows_weighted_check, self.lib.tango_engine_denoise_windows_weighted))
-            why = check(C.byref(a), C.byref(w), C.c_void_p(vw.ctypes.data))
-            if why:
-                raise ValueError(why.decode())
-            with torch.cuda.device(self.device):
-                _lib.check(run(self._h, C.byref(a), C.byref(w), C.c_void_p(vw.ctypes.data), _stream_ptr()), name + "_weighted")
-            return latents
-        check, run = ((self.lib.tango_debug_denoise_ring_check, self.lib.tango_engine_denoise_ring) if _ring else
-                      (self.lib.tango_debug_denoise_windows_check, self.lib.tango_engine_denoise_windows))
-        why = check(C.byref(a), C.byref(w))
+            extra = (C.c_void_p(vw.ctypes.data),)
+        L = self.lib
+        check, run, name = {
+            (False, False): (L.tango_debug_denoise_windows_check, L.tango_engine_denoise_windows, "denoise_windows"),
+            (True, False): (L.tango_debug_denoise_ring_check, L.tango_engine_denoise_ring, "denoise_ring"),
+            (False, True): (L.tango_debug_denoise_windows_weighted_check, L.tango_engine_denoise_windows_weighted, "denoise_windows_weighted"),
+            (True, True): (L.tango_debug_denoise_ring_weighted_check, L.tango_engine_denoise_ring_weighted, "denoise_ring_weighted"),
+        }[bool(_ring), view_weights is not None]
+        why = check(C.byref(a), C.byref(w), *extra)
         if why:
             raise ValueError(why.decode())
         with torch.cuda.device(self.device):
-            _lib.check(run(self._h, C.byref(a), C.byref(w), _stream_ptr()), name)
+            _lib.check(run(self._h, C.byref(a), C.byref(w), *extra, _stream_ptr()), name)
         return latents
+
+    def _vae_decode_windowed(self, latents, window_h, stride, ring):
+        """the body of vae_decode_tiled / vae_decode_ring"""
+        name = "vae_decode_ring" if ring else "vae_decode_tiled"
+        z = self._f32(latents)
+        H, hw, stride, _ = self._check_windows(name + ": latents", z, self.vae_cfg.get("embed_dim", 8), window_h, stride, ring)
+        nl = len(self.vae_cfg["ch_mult"])
+        B = z.shape[0]
+        mel = torch.empty((B, self.vae_cfg["out_ch"], H << (nl - 1), z.shape[3] << (nl - 1)), device=self.device, dtype=torch.float32)
+        run = self.lib.tango_engine_vae_decode_ring_h if ring else self.lib.tango_engine_vae_decode_tiled_h
+        with torch.cuda.device(self.device):
+            _lib.check(run(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(mel.data_ptr()), B, H, hw, stride, _stream_ptr()), name)
+        return mel
 
     def vae_decode_tiled(self, latents, window_h, stride):
         """a long clip's latents [B, embed_dim, H, 16] -> mel [B, 1, 4H, 64]: the V = (H - window_h) / stride + 1 windows are decoded as
         one batch of B * V latents of height `window_h` and the decoded tiles cross-faded over their overlaps (include/tango_engine.h
         tango_op_mel_tile_blend).  The same geometry rules as denoise_windows."""
-        z = self._f32(latents)
-        H, hw, stride, _ = self._check_canvas("vae_decode_tiled: latents", z, self.vae_cfg.get("embed_dim", 8), window_h, stride)
-        nl = len(self.vae_cfg["ch_mult"])
-        B = z.shape[0]
-        mel = torch.empty((B, self.vae_cfg["out_ch"], H << (nl - 1), z.shape[3] << (nl - 1)), device=self.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.tango_engine_vae_decode_tiled_h(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(mel.data_ptr()), B, H, hw,
-                                                                stride, _stream_ptr()), "vae_decode_tiled")
-        return mel
+        return self._vae_decode_windowed(latents, window_h, stride, False)
 
     def vae_decode_ring(self, latents, window_h, stride):
         """a loop's latents [B, embed_dim, H, 16] on a ring -> mel [B, 1, 4H, 64] on the same ring: the V = H / stride wrapping windows are
         decoded as one batch of B * V latents of height `window_h`, and every tile fades in and out over its overlaps with its two
         neighbours (include/tango_engine.h tango_op_mel_ring_blend).  The same geometry rules as denoise_ring."""
-        z = self._f32(latents)
-        H, hw, stride, _ = self._check_ring("vae_decode_ring: latents", z, self.vae_cfg.get("embed_dim", 8), window_h, stride)
-        nl = len(self.vae_cfg["ch_mult"])
-        B = z.shape[0]
-        mel = torch.empty((B, self.vae_cfg["out_ch"], H << (nl - 1), z.shape[3] << (nl - 1)), device=self.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.tango_engine_vae_decode_ring_h(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(mel.data_ptr()), B, H, hw,
-                                                               stride, _stream_ptr()), "vae_decode_ring")
-        return mel
+        return self._vae_decode_windowed(latents, window_h, stride, True)
 
     def _check_inpaint(self, latents, n, known_latents, latent_mask, blend_coef, blend_noise):
         """host-side validation of denoise()'s masking arguments: None when the call is not masked, else the device / host copies the

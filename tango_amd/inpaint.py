@@ -97,7 +97,7 @@ def long_geometry(duration, window=10.0, hop=5.0):
 def loop_geometry(duration, window=None, hop=None):
     """A seamless loop of `duration` seconds as windows on a ring in time: -> (H, Hw, s, V) in latent rows, the ring's height
     H = duration * 25.6, the window height Hw = duration_geometry(window)[0] <= H, the stride s = hop * 25.6 -- an integer multiple
-    of 8 rows below Hw that divides H -- and V = H / s <= 32 views, view v covering ring rows (v s + y) mod H (common.h ring_cover).
+    of 8 rows below Hw that divides H -- and V = H / s <= 32 views, view v covering ring rows (v s + y) mod H (common.h window_cover).
     `window` defaults to `duration` when that is a length of generate()'s grid of at most 10 s, else to 10 s; `hop` to window / 2.
     A duration that is no whole number of strides is a ValueError naming the nearest valid durations on both sides."""
     try:

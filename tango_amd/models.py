@@ -203,6 +203,16 @@ class AudioDiffusion:
                           batch.attention_mask.repeat_interleave(num_samples_per_prompt, 0)]) == 1      # tokenizer outputs: CPU tensors
         return torch.cat([ne, pe]), (torch.cat([uam, am]) == 1).to(dev), host.cpu()
 
+    def _encode_prompts(self, prompt, samples_per_prompt, guidance_scale, negative_prompt):
+        """what every string-level entry point hands its *_from_embeddings form: fp32 embeddings and the mask, [uncond; cond] with the
+        tokenizer's HOST mask when guidance is on (`negative_prompt` is read only then), the conditional rows alone and None
+        otherwise; each prompt's rows repeated `samples_per_prompt` times"""
+        if cfg_enabled(guidance_scale):
+            pe, pm, host = self._encode_text_classifier_free(prompt, samples_per_prompt, negative_prompt)
+            return pe.float(), pm, host
+        pe, pm = self.encode_text(prompt)
+        return pe.repeat_interleave(samples_per_prompt, 0).float(), pm.repeat_interleave(samples_per_prompt, 0), None
+
     def _encode_text_pair(self, prompt, negative_prompt, num_samples_per_prompt):
         """[negative; cond] with both halves at one length: each is tokenised on its own (padding=True: its longest row), then the
         shorter one again with padding="max_length" at the longer one's length -- no row of either is truncated below the
@@ -241,7 +251,9 @@ class AudioDiffusion:
     # ---- the hot path ------------------------------------------------------------------------
     def _pad_text(self, embeds, mask, mask_host=None):
         """Static plan shapes: pad L up to a bucket with masked tokens.  Numerically exact: a masked
-        key's weight is exp(-10000) == 0 in fp32 (SURVEY.md section 4 differential check)."""
+        key's weight is exp(-10000) == 0 in fp32 (SURVEY.md section 4 differential check).  No mask: every key is valid."""
+        if mask is None:
+            mask = torch.ones(embeds.shape[:2], dtype=torch.bool, device=embeds.device)
         L = embeds.shape[1]
         if not self.bucket_text_len:
             return embeds, mask, mask_host
@@ -258,6 +270,15 @@ class AudioDiffusion:
             mask_host = ph
         return pe, pm, mask_host
 
+    def _philox_seed(self, seed):
+        """the Philox key of one engine call; counts the call.  The reference draws step noise from torch's global generator
+        (randn_tensor in scheduler.step): with no seed given the key is drawn from that generator, so torch.manual_seed() fixes the
+        whole trajectory and calls differ -- after the call's latents, which prepare_latents draws from the same generator."""
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.seed is None else (int(self.seed) << 20) + self._calls
+        self._calls += 1
+        return seed
+
     def _denoise(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
                  sample_offset, mask_host=None, known_latents=None, latent_mask=None, blend_noise=None, start=0, count=None,
                  latent_h=256, guidance_rescale=0.0, **extra_conditions):
@@ -271,9 +292,7 @@ class AudioDiffusion:
         cfg_on = cfg_enabled(guidance_scale)
         guidance_rescale = check_guidance_rescale(guidance_scale, guidance_rescale)
         B = prompt_embeds.shape[0] // 2 if cfg_on else prompt_embeds.shape[0]
-        if not hasattr(inference_scheduler, "coef_table"):
-            # a diffusers / fork scheduler object (the reference's loop takes any): the engine's class of the same name and config
-            inference_scheduler = from_diffusers(inference_scheduler)
+        inference_scheduler = _own_scheduler(inference_scheduler)
         inference_scheduler.set_timesteps(num_steps, device=self.device)
         if count is not None:
             timesteps, coef, window = inference_scheduler.timesteps[:count], inference_scheduler.coef_table(count=count), {}
@@ -289,16 +308,10 @@ class AudioDiffusion:
         latents = latents.to(self.device, torch.float32).contiguous().clone()
         if latents.dim() != 4:
             raise ValueError("latents must be [B, C, H, W], got %s" % (tuple(latents.shape),))
-        if boolean_prompt_mask is None:
-            boolean_prompt_mask = torch.ones(prompt_embeds.shape[:2], dtype=torch.bool, device=prompt_embeds.device)
         # (the mask is NOT moved here: a host mask reaches the engine as a host pointer too, which spares the call its only host sync)
         pe, pm, mask_host = self._pad_text(prompt_embeds.to(self.device), boolean_prompt_mask, mask_host)
         c = inference_scheduler.config
-        if seed is None:
-            # the reference draws step noise from torch's global generator (randn_tensor in scheduler.step): derive the
-            # Philox key from that generator, so torch.manual_seed() fixes the whole trajectory and calls differ
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.seed is None else (int(self.seed) << 20) + self._calls
-        self._calls += 1
+        seed = self._philox_seed(seed)
         masking = {}
         if known_latents is not None or latent_mask is not None:
             masking = dict(known_latents=known_latents, latent_mask=latent_mask, blend_coef=inference_scheduler.blend_table(**window),
@@ -332,14 +345,8 @@ class AudioDiffusion:
         """models.py:210-257 (same signature, same return: latents [B*S, 8, 256, 16]); `duration` seconds of audio instead of 10:
         latents [B*S, 8, int(duration * 25.6), 16] (audioldm/pipeline.py:94-95,113-126).  `negative_prompt` (None, a str or one str per
         prompt) replaces the empty unconditional text; it is read only when guidance is on."""
-        host = None
-        if cfg_enabled(guidance_scale):
-            pe, pm, host = self._encode_text_classifier_free(prompt, num_samples_per_prompt, negative_prompt)
-        else:
-            pe, pm = self.encode_text(prompt)
-            pe = pe.repeat_interleave(num_samples_per_prompt, 0)
-            pm = pm.repeat_interleave(num_samples_per_prompt, 0)
-        return self.inference_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, mask_host=host,
+        pe, pm, host = self._encode_prompts(prompt, num_samples_per_prompt, guidance_scale, negative_prompt)
+        return self.inference_from_embeddings(pe, pm, inference_scheduler, num_steps, guidance_scale, mask_host=host,
                                               duration=duration, guidance_rescale=guidance_rescale)
 
     # ---- clips longer than 20 s: MultiDiffusion windows in time (the fork's pipeline_stable_diffusion_panorama.py:442-456, 614-652) ----
@@ -368,8 +375,7 @@ class AudioDiffusion:
         how = "on a ring" if ring else "with windows"
         if not isinstance(guidance_scale, (int, float)):
             raise ValueError("a guidance table is not supported %s: guidance_scale must be a scalar" % how)
-        if not hasattr(inference_scheduler, "coef_table"):
-            inference_scheduler = from_diffusers(inference_scheduler)
+        inference_scheduler = _own_scheduler(inference_scheduler)
         if inference_scheduler.rule == "dpmsolver":
             raise ValueError("the multistep DPM-Solver rule is not supported on a ring: use DDPM or DDIM" if ring else
                              "the multistep DPM-Solver rule is not supported with windows (a per-view history has no reference "
@@ -389,8 +395,6 @@ class AudioDiffusion:
         latents = latents.to(self.device, torch.float32).contiguous().clone()
         if latents.dim() != 4 or latents.shape[0] != B or latents.shape[2] != H:
             raise ValueError("latents must be [%d, C, %d, W] for %r s, got %s" % (B, H, duration, tuple(latents.shape)))
-        if boolean_prompt_mask is None:
-            boolean_prompt_mask = torch.ones(prompt_embeds.shape[:2], dtype=torch.bool, device=prompt_embeds.device)
         pe, pm, mask_host = self._pad_text(prompt_embeds.to(self.device), boolean_prompt_mask, mask_host)
         if window_prompt is None:
             # one row per window, row half * B * V + b * V + v: each half's rows repeated V times in place
@@ -402,9 +406,7 @@ class AudioDiffusion:
             pe, pm = pe.index_select(0, idx.to(pe.device)), pm.index_select(0, idx.to(pm.device))
             mask_host = mask_host.index_select(0, idx) if mask_host is not None else None
         c = inference_scheduler.config
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.seed is None else (int(self.seed) << 20) + self._calls
-        self._calls += 1
+        seed = self._philox_seed(seed)
         run = self.engine.denoise_ring if ring else self.engine.denoise_windows
         run(latents, pe, pm, inference_scheduler.timesteps.cpu().numpy(), inference_scheduler.coef_table(), guidance_scale, window_h=hw,
             stride=stride, prediction_type=c.prediction_type, rule=inference_scheduler.rule, clip_sample=c.clip_sample,
@@ -417,14 +419,8 @@ class AudioDiffusion:
                        window=10, hop=5, negative_prompt=None, seed=None, sample_offset=0):
         """inference() for a clip longer than `window` seconds (inference_long_from_embeddings): latents [B*S, 8, int(duration * 25.6), 16]"""
         long_geometry(duration, window, hop)
-        host = None
-        if cfg_enabled(guidance_scale):
-            pe, pm, host = self._encode_text_classifier_free(prompt, num_samples_per_prompt, negative_prompt)
-        else:
-            pe, pm = self.encode_text(prompt)
-            pe = pe.repeat_interleave(num_samples_per_prompt, 0)
-            pm = pm.repeat_interleave(num_samples_per_prompt, 0)
-        return self.inference_long_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, duration, window, hop,
+        pe, pm, host = self._encode_prompts(prompt, num_samples_per_prompt, guidance_scale, negative_prompt)
+        return self.inference_long_from_embeddings(pe, pm, inference_scheduler, num_steps, guidance_scale, duration, window, hop,
                                                    seed=seed, sample_offset=sample_offset, mask_host=host)
 
     # ---- seamless loops: the same windows on a ring in time (include/tango_engine.h tango_engine_denoise_ring) ----------------------
@@ -445,14 +441,8 @@ class AudioDiffusion:
                        window=None, hop=None, negative_prompt=None, seed=None, sample_offset=0):
         """inference() for a seamless loop (inference_loop_from_embeddings): ring latents [B*S, 8, duration * 25.6, 16]"""
         loop_geometry(duration, window, hop)
-        host = None
-        if cfg_enabled(guidance_scale):
-            pe, pm, host = self._encode_text_classifier_free(prompt, num_samples_per_prompt, negative_prompt)
-        else:
-            pe, pm = self.encode_text(prompt)
-            pe = pe.repeat_interleave(num_samples_per_prompt, 0)
-            pm = pm.repeat_interleave(num_samples_per_prompt, 0)
-        return self.inference_loop_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, duration, window, hop,
+        pe, pm, host = self._encode_prompts(prompt, num_samples_per_prompt, guidance_scale, negative_prompt)
+        return self.inference_loop_from_embeddings(pe, pm, inference_scheduler, num_steps, guidance_scale, duration, window, hop,
                                                    seed=seed, sample_offset=sample_offset, mask_host=host)
 
     # ---- timed prompts: a prompt per window and tapered view weights (include/tango_engine.h tango_engine_denoise_windows_weighted) ----
@@ -479,12 +469,8 @@ class AudioDiffusion:
         `negative_prompt`: None, one str, or one str per segment.  Latents [num_samples, 8, duration * 25.6, 16]."""
         window_prompt = timeline_geometry(segments, duration, window, hop, loop)[4]
         prompts = [p for p, _ in segments]
-        host = None
-        if cfg_enabled(guidance_scale):
-            pe, pm, host = self._encode_text_classifier_free(prompts, 1, negative_prompt)
-        else:
-            pe, pm = self.encode_text(prompts)
-        return self.inference_timeline_from_embeddings(pe.float(), pm, window_prompt, inference_scheduler, num_steps, guidance_scale,
+        pe, pm, host = self._encode_prompts(prompts, 1, guidance_scale, negative_prompt)
+        return self.inference_timeline_from_embeddings(pe, pm, window_prompt, inference_scheduler, num_steps, guidance_scale,
                                                        duration, window, hop, loop, taper, num_samples, seed=seed,
                                                        sample_offset=sample_offset, mask_host=host)
 
@@ -511,14 +497,8 @@ class AudioDiffusion:
         if known_latents.shape[0] != len(prompt) or latent_mask.shape[0] != len(prompt):
             raise ValueError("known_latents and latent_mask need one row per prompt (%d), got %d and %d"
                              % (len(prompt), known_latents.shape[0], latent_mask.shape[0]))
-        host = None
-        if cfg_enabled(guidance_scale):
-            pe, pm, host = self._encode_text_classifier_free(prompt, S, negative_prompt)
-        else:
-            pe, pm = self.encode_text(prompt)
-            pe = pe.repeat_interleave(S, 0)
-            pm = pm.repeat_interleave(S, 0)
-        return self.inpaint_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale,
+        pe, pm, host = self._encode_prompts(prompt, S, guidance_scale, negative_prompt)
+        return self.inpaint_from_embeddings(pe, pm, inference_scheduler, num_steps, guidance_scale,
                                             known_latents=known_latents.repeat_interleave(S, 0),
                                             latent_mask=latent_mask.repeat_interleave(S, 0), mask_host=host,
                                             guidance_rescale=guidance_rescale)
@@ -527,21 +507,22 @@ class AudioDiffusion:
     @torch.no_grad()
     def edit_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
                              start_latents, strength, known_latents=None, latent_mask=None, noise=None, blend_noise=None, seed=None,
-                             sample_offset=0, mask_host=None, guidance_rescale=0.0):
+                             sample_offset=0, mask_host=None, guidance_rescale=0.0, **conditions):
         """The last k = int(strength * num_steps) steps of the loop of inference_from_embeddings, from `start_latents` [B, 8, 256,
         16]: an existing clip's latents noised (AutoencoderKL.encode_start_latents) or inverted (invert_from_embeddings) to the
         level `inference_scheduler.edit_plan(num_steps, strength)` names.  The engine runs `timesteps[start:]` with the scheduler's
         truncated tables; the multistep DPM-Solver restarts its order ramp at the first executed step.  `noise` / `blend_noise`
         hold one entry per EXECUTED step ([k, B, 8, 256, 16]).  With `known_latents` / `latent_mask` it is a regional edit: the
-        region where the mask is 1 keeps the clip's audio (the masked loop of inpaint_from_embeddings), the rest is edited."""
-        if not hasattr(inference_scheduler, "coef_table"):
-            inference_scheduler = from_diffusers(inference_scheduler)
+        region where the mask is 1 keeps the clip's audio (the masked loop of inpaint_from_embeddings), the rest is edited.
+        `conditions`: what a subclass's UNet takes beside the text (_extra_conditions)."""
+        inference_scheduler = _own_scheduler(inference_scheduler)
         if start_latents is None:
             raise ValueError("an edit starts from start_latents")
         start, _ = inference_scheduler.edit_plan(num_steps, strength)
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, start_latents, noise,
                              seed, sample_offset, mask_host=mask_host, known_latents=known_latents, latent_mask=latent_mask,
-                             blend_noise=blend_noise, start=start, guidance_rescale=guidance_rescale)
+                             blend_noise=blend_noise, start=start, guidance_rescale=guidance_rescale,
+                             **self._extra_conditions(**conditions))
 
     @torch.no_grad()
     def edit(self, prompt, start_latents, inference_scheduler, num_steps=20, guidance_scale=3, strength=0.5, num_samples_per_prompt=1,
@@ -551,20 +532,14 @@ class AudioDiffusion:
         S = num_samples_per_prompt
         if start_latents.shape[0] != len(prompt) * S:
             raise ValueError("start_latents need one row per prompt and sample (%d), got %d" % (len(prompt) * S, start_latents.shape[0]))
-        host = None
-        if cfg_enabled(guidance_scale):
-            pe, pm, host = self._encode_text_classifier_free(prompt, S, negative_prompt)
-        else:
-            pe, pm = self.encode_text(prompt)
-            pe = pe.repeat_interleave(S, 0)
-            pm = pm.repeat_interleave(S, 0)
-        return self.edit_from_embeddings(pe.float(), pm, inference_scheduler, num_steps, guidance_scale, start_latents=start_latents,
+        pe, pm, host = self._encode_prompts(prompt, S, guidance_scale, negative_prompt)
+        return self.edit_from_embeddings(pe, pm, inference_scheduler, num_steps, guidance_scale, start_latents=start_latents,
                                          strength=strength, known_latents=known_latents, latent_mask=latent_mask, seed=seed,
                                          mask_host=host, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def invert_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, *, latents, count,
-                               guidance_scale=1.0, mask_host=None):
+                               guidance_scale=1.0, mask_host=None, **conditions):
         """DDIM inversion, the deterministic encoder of an edit: `count` steps of DDIMInverseScheduler (ascending timesteps, the
         inverse coefficient table, no step noise) from clean `latents` through the same fused loop, under the text the clip is
         described by (`guidance_scale` 1: no CFG, `prompt_embeds` hold the B conditional rows only).  `inference_scheduler`: a
@@ -576,12 +551,20 @@ class AudioDiffusion:
         if latents is None:
             raise ValueError("inversion starts from the clip's clean latents")
         return self._denoise(prompt_embeds, boolean_prompt_mask, inv, num_steps, guidance_scale, latents, None, 0, 0,
-                             mask_host=mask_host, count=int(count))
+                             mask_host=mask_host, count=int(count), **self._extra_conditions(**conditions))
+
+    def _extra_conditions(self):
+        """the engine's keywords for what the UNet takes beside the text: nothing here (a keyword given is a TypeError)"""
+        return {}
+
+
+def _own_scheduler(scheduler):
+    """a diffusers / fork scheduler object (the reference's loop takes any) -> the engine's class of the same name and config"""
+    return scheduler if hasattr(scheduler, "coef_table") else from_diffusers(scheduler)
 
 
 def _inverse_scheduler(scheduler):
-    if not hasattr(scheduler, "coef_table"):
-        scheduler = from_diffusers(scheduler)
+    scheduler = _own_scheduler(scheduler)
     if isinstance(scheduler, DDIMInverseScheduler):
         return scheduler
     return DDIMInverseScheduler.from_scheduler(scheduler)
@@ -612,12 +595,10 @@ class MusicAudioDiffusion(AudioDiffusion):
         """mustango/models.py:540-598 given the three encoder outputs ([uncond; cond] when guidance > 1); with `known_latents` /
         `latent_mask` (/ `blend_noise`) the masked loop of AudioDiffusion.inpaint_from_embeddings.  `duration` sizes the initial
         latents when none are given, as in AudioDiffusion.inference_from_embeddings."""
-        if encoded_beats is None or encoded_chords is None:
-            raise ValueError("encoded_beats and encoded_chords are required (mustango/models.py:548-550)")
+        conditions = self._extra_conditions(encoded_beats, beat_mask, encoded_chords, chord_mask)
         return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, latents, noise, seed,
                              sample_offset, known_latents=known_latents, latent_mask=latent_mask, blend_noise=blend_noise,
-                             latent_h=duration_geometry(duration)[0], guidance_rescale=guidance_rescale,
-                             beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
+                             latent_h=duration_geometry(duration)[0], guidance_rescale=guidance_rescale, **conditions)
 
     @torch.no_grad()
     def inpaint_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
@@ -629,10 +610,10 @@ class MusicAudioDiffusion(AudioDiffusion):
                                               encoded_chords=encoded_chords, chord_mask=chord_mask, known_latents=known_latents,
                                               latent_mask=latent_mask, blend_noise=blend_noise, guidance_rescale=guidance_rescale)
 
-    @staticmethod
-    def _need_music(encoded_beats, encoded_chords):
+    def _extra_conditions(self, encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None):
         if encoded_beats is None or encoded_chords is None:
             raise ValueError("encoded_beats and encoded_chords are required (mustango/models.py:548-550)")
+        return dict(beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
 
     @torch.no_grad()
     def edit_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, guidance_scale=3, *,
@@ -640,27 +621,19 @@ class MusicAudioDiffusion(AudioDiffusion):
                              sample_offset=0, encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None,
                              guidance_rescale=0.0):
         """AudioDiffusion.edit_from_embeddings with the beat / chord streams of inference_from_embeddings"""
-        if not hasattr(inference_scheduler, "coef_table"):
-            inference_scheduler = from_diffusers(inference_scheduler)
-        if start_latents is None:
-            raise ValueError("an edit starts from start_latents")
-        start, _ = inference_scheduler.edit_plan(num_steps, strength)
-        self._need_music(encoded_beats, encoded_chords)
-        return self._denoise(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale, start_latents, noise,
-                             seed, sample_offset, known_latents=known_latents, latent_mask=latent_mask, blend_noise=blend_noise,
-                             start=start, guidance_rescale=guidance_rescale,
-                             beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
+        return super().edit_from_embeddings(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, guidance_scale,
+                                            start_latents=start_latents, strength=strength, known_latents=known_latents,
+                                            latent_mask=latent_mask, noise=noise, blend_noise=blend_noise, seed=seed,
+                                            sample_offset=sample_offset, guidance_rescale=guidance_rescale, encoded_beats=encoded_beats,
+                                            beat_mask=beat_mask, encoded_chords=encoded_chords, chord_mask=chord_mask)
 
     @torch.no_grad()
     def invert_from_embeddings(self, prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps=20, *, latents, count,
                                guidance_scale=1.0, encoded_beats=None, beat_mask=None, encoded_chords=None, chord_mask=None):
         """AudioDiffusion.invert_from_embeddings with the beat / chord streams of inference_from_embeddings"""
-        if latents is None:
-            raise ValueError("inversion starts from the clip's clean latents")
-        self._need_music(encoded_beats, encoded_chords)
-        return self._denoise(prompt_embeds, boolean_prompt_mask, _inverse_scheduler(inference_scheduler), num_steps, guidance_scale,
-                             latents, None, 0, 0, count=int(count),
-                             beat_embeds=encoded_beats, beat_mask=beat_mask, chord_embeds=encoded_chords, chord_mask=chord_mask)
+        return super().invert_from_embeddings(prompt_embeds, boolean_prompt_mask, inference_scheduler, num_steps, latents=latents,
+                                              count=count, guidance_scale=guidance_scale, encoded_beats=encoded_beats,
+                                              beat_mask=beat_mask, encoded_chords=encoded_chords, chord_mask=chord_mask)
 
     def edit(self, *a, **k):
         raise NotImplementedError("strings / beat and chord annotations are encoded by the caller's Mustango front-end modules; "

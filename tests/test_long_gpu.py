@@ -93,7 +93,7 @@ def _canvas_inputs(H, B=2, L=9, N=10):
     return _cache[("in", H, B)]
 
 
-def _run_windows(e, rule, N, inputs, Hw, s, use_graph=True, noise=True, seed=0, offset=0):
+def _run_windows(e, rule, N, inputs, Hw, s, use_graph=True, noise=True, seed=0, offset=0, weights=None):
     enc, mask, lat0, noises = inputs
     V = (lat0.shape[2] - Hw) // s + 1
     sch = _sched(rule)
@@ -101,7 +101,7 @@ def _run_windows(e, rule, N, inputs, Hw, s, use_graph=True, noise=True, seed=0, 
     lat = lat0.clone().cuda()
     e.denoise_windows(lat, enc.repeat_interleave(V, 0).cuda(), mask.repeat_interleave(V, 0).cuda(), sch.timesteps.numpy(), sch.coef_table(), 3.0,
                       window_h=Hw, stride=s, prediction_type=sch.config.prediction_type, rule=sch.rule,
-                      noise=noises[:N].cuda() if noise else None, seed=seed, sample_offset=offset, use_graph=use_graph)
+                      noise=noises[:N].cuda() if noise else None, seed=seed, sample_offset=offset, use_graph=use_graph, view_weights=weights)
     torch.cuda.synchronize()
     return lat.cpu()
 

@@ -77,7 +77,7 @@ def test_op_ring_commutes_with_a_rotation_by_one_stride(lib, H, Hw, s):
 
 
 # ---- tiny-UNet loops ----------------------------------------------------------------------------------------------------------------------
-def _run_ring(e, rule, N, inputs, Hw, s, use_graph=True, noise=True, seed=0, offset=0):
+def _run_ring(e, rule, N, inputs, Hw, s, use_graph=True, noise=True, seed=0, offset=0, weights=None):
     enc, mask, lat0, noises = inputs
     V = lat0.shape[2] // s
     sch = LG._sched(rule)
@@ -85,7 +85,7 @@ def _run_ring(e, rule, N, inputs, Hw, s, use_graph=True, noise=True, seed=0, off
     lat = lat0.clone().cuda()
     e.denoise_ring(lat, enc.repeat_interleave(V, 0).cuda(), mask.repeat_interleave(V, 0).cuda(), sch.timesteps.numpy(), sch.coef_table(), 3.0,
                    window_h=Hw, stride=s, prediction_type=sch.config.prediction_type, rule=sch.rule,
-                   noise=noises[:N].cuda() if noise else None, seed=seed, sample_offset=offset, use_graph=use_graph)
+                   noise=noises[:N].cuda() if noise else None, seed=seed, sample_offset=offset, use_graph=use_graph, view_weights=weights)
     torch.cuda.synchronize()
     return lat.cpu()
 
@@ -161,9 +161,13 @@ def test_ring_loop_commutes_with_a_rotation(dtype):
 
 
 # ---- 6. state isolation -------------------------------------------------------------------------------------------------------------------
-def test_plain_windowed_ring_plain_on_one_plan(lib):
-    """a plain call of batch B * V at H = 64, a windowed call and a ring call of V = 4 views share one plan; each replays its own graph and
-    gives the bits it gives alone (on a fresh engine)"""
+@pytest.mark.parametrize("weighted", [False, True], ids=["equal", "weighted"])
+@pytest.mark.parametrize("first", ["windows", "ring"])
+def test_plain_windowed_ring_plain_on_one_plan(lib, first, weighted):
+    """a plain call of batch B * V at H = 64, a windowed call and a ring call of V = 4 views share one plan; each gives the bits it gives
+    alone (on a fresh engine).  The windowed and the ring call replay the SAME captured steps (UNetPlan::wgraphs[weighted]: the kernel
+    reads linear-or-ring from the call's block), so whichever of the two captures them must serve the other: `first` runs first on the
+    shared engine.  weighted: the same pair with a non-constant positive table of view weights (wgraphs[1])."""
     N, V = 3, 4
     ring_in = LG._canvas_inputs(H4)                            # (96, 64, 24): V = 4
     enc, mask, _, _ = ring_in
@@ -171,27 +175,38 @@ def test_plain_windowed_ring_plain_on_one_plan(lib):
     g = torch.Generator().manual_seed(8)
     plain = (enc.repeat_interleave(V, 0), mask.repeat_interleave(V, 0), torch.randn(2 * V, 8, 64, 16, generator=g), torch.randn(N, 2 * V, 8, 64, 16, generator=g))
     win_in = (enc, mask) + tuple(win_in[2:])                   # the same text rows: the same single-key prefix, the same plan key
+    wts = np.linspace(0.5, 1.5, 64, dtype=np.float32) if weighted else None
 
     def fresh():
         e = Engine(unet=O.UNET_CONFIG_TINY, dtype="fp32")
         e.load_synthetic(1234)
         return e
 
-    alone = (LG._run_plain(fresh(), "ddpm", N, *plain, 64), LG._run_windows(fresh(), "ddpm", N, win_in, 64, 24), _run_ring(fresh(), "ddpm", N, ring_in, 64, 24))
+    def run_w(e):
+        return LG._run_windows(e, "ddpm", N, win_in, 64, 24, weights=wts)
+
+    def run_r(e):
+        return _run_ring(e, "ddpm", N, ring_in, 64, 24, weights=wts)
+
+    alone = (LG._run_plain(fresh(), "ddpm", N, *plain, 64), run_w(fresh()), run_r(fresh()))
     e = fresh()
     a = LG._run_plain(e, "ddpm", N, *plain, 64)
     plans = e.plan_stats()[1]
-    w = LG._run_windows(e, "ddpm", N, win_in, 64, 24)
-    r = _run_ring(e, "ddpm", N, ring_in, 64, 24)
+    if first == "windows":
+        w = run_w(e)
+        r = run_r(e)
+    else:
+        r = run_r(e)
+        w = run_w(e)
     b = LG._run_plain(e, "ddpm", N, *plain, 64)
     assert e.plan_stats()[1] == plans, "the windowed and the ring call run the plain call's plan"
     assert torch.equal(a, alone[0]) and torch.equal(w, alone[1]) and torch.equal(r, alone[2]) and torch.equal(b, alone[0])
-    assert torch.equal(r, _run_ring(e, "ddpm", N, ring_in, 64, 24)) and torch.equal(w, LG._run_windows(e, "ddpm", N, win_in, 64, 24))
+    assert torch.equal(r, run_r(e)) and torch.equal(w, run_w(e))
     with TI.tuning(lib, TANGO_GRAPH_STEPS=2):                 # k steps per graph: a 2-step replay plus a remainder
-        assert torch.equal(r, _run_ring(e, "ddpm", N, ring_in, 64, 24))
-    e.drop_plans()                                            # the plan goes with graphs in its ring slot
+        assert torch.equal(r, run_r(e)) and torch.equal(w, run_w(e))
+    e.drop_plans()                                            # the plan goes with graphs in its windowed slots
     assert e.plan_stats() == (0, 0)
-    assert torch.equal(r, _run_ring(e, "ddpm", N, ring_in, 64, 24))
+    assert torch.equal(r, run_r(e))
 
 
 # ---- 7. the ring tile blend ---------------------------------------------------------------------------------------------------------------
